@@ -4,9 +4,20 @@ metric is quoted on (N = 10 k, 1 %-sparse interference graph from the journal ge
 wall-clock of the whole binary search to a converged colouring on the same instance.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--instances-per-gpu M] [--expm lanczos|taylor]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one MMW iteration (DUAL, LOSS, EXPM + X on the pattern, averaging) on a synthetic instance
 that is resident in HBM before the timed region starts; the sketches are generated on the device.
+
+A plain run does only what the headline needs: set-up, W untimed warm-up steps, exactly K timed steps (one timed region),
+the outputs if --dump-outputs is given, and the JSON line.  --full adds everything else described below (the median of
+--repeats regions, the roofline passes, the strictly-fp32 run, the colourings and the CPU baseline).
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step -- per instance the averaged
+iterate X_avg and Y_avg the caller factors, X and Y of the last step, exp(L/2)R of the last step (x_half) and the largest
+constraint violation -- as DIR/<name>.npy (float32 for the fp32 path, float64 for fp64; prefixed i<id>_ with several
+instances per rank).  At most 64 MB in all: past that, each array above its even share is cut to a fixed, seeded sample
+of its entries.  The inputs (instances, seeds) depend only on the arguments, so two builds can be compared file by file.
 
 N > 1: one process per GPU.  Either an external launcher started the ranks (torchrun: RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment), or -- with WORLD_SIZE unset -- this process starts them itself:
@@ -18,13 +29,13 @@ gathered with one RCCL all_gather that closes the timed region.
 --instances-per-gpu M (BASELINE configs[3]: 64 N=2000 graphs, 8 per GPU: `--workload er-5pct-2k
 --instances-per-gpu 8`): M resident handles per rank, their iterations enqueued round-robin on M HIP streams.
 
-`value` is the MEDIAN of --repeats (7) timed regions -- each: back to the initial point, W untimed warm-up steps, exactly K
-steps between two barriers (+ device synchronisation), closed by the gather of the objective records -- with `value_min` /
+`value` is the MEDIAN of --repeats (1; 7 with --full) timed regions -- each: back to the initial point, W untimed warm-up steps,
+exactly K steps between two barriers (+ device synchronisation), closed by the gather of the objective records -- with `value_min` /
 `value_max`, the tail of the median region (`region_tail_ms`: read-back, gather, barrier) and the rate without it.
 `config.operand_precision` says what the fp32 headline multiplies in (16-bit operands on the matrix cores, fp32 accumulation,
-certified against the tolerance); `value_fp32_operands` is the same loop on strictly-fp32 operands (N = 1).
+certified against the tolerance); with --full, `value_fp32_operands` is the same loop on strictly-fp32 operands (N = 1).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the CSR SpMM inside exp(L/2)R -- algorithmic bytes per launch
                  divided by its mean launch duration, measured with HIP events on the solver's stream
                  in a second pass over the same steps (matrix-core product: the start / stop events its launch
@@ -147,6 +158,32 @@ def spawn_ranks(n, cmd, env=None, timeout=None):
     return rc, out0
 
 
+DUMP_BYTES = 64 * 10**6
+NPY_HEADER = 4096  # room for one .npy header (the format pads it to 64 or 128 bytes)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Write {name: array} as path/<name>.npy.  If the files would exceed `budget` bytes, every array larger than its even share
+    of it is replaced by a sample of its flat entries: positions drawn by a generator seeded with the array's size, so the same
+    positions from run to run and from build to build."""
+    os.makedirs(path, exist_ok=True)
+    over = sum(a.nbytes + NPY_HEADER for a in arrays.values()) > budget
+    share = budget // max(len(arrays), 1) - NPY_HEADER
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def solver_outputs(s, dtype):
+    """What the timed path hands its caller after its last step, read back from the handle."""
+    from sig_sdp_mmw_amd import _lib
+    fields = (("x_avg", _lib.F_XAVG), ("y_avg", _lib.F_YAVG), ("x", _lib.F_XVAL), ("y", _lib.F_Y), ("x_half", _lib.F_XHALF),
+              ("e_max", _lib.F_E_MAX))
+    return {name: np.ascontiguousarray(s.read(f), dtype=dtype) for name, f in fields}
+
+
 def coloring_block(state, dtype_name, nit, eta, warm, geometry=None, speculate=False, device_state=False):
     """Wall-clock of the whole binary search (binary_search_relaxation.run) to a feasible colouring, with the device-RNG /
     batched-rounding fast path of the drop-in class (the flow of sim_script/journal_version/sim_mmw_time.py:30-36)."""
@@ -207,7 +244,12 @@ def main():
     ap.add_argument("--workload", default="journal-1pct", choices=sorted(WORKLOADS))
     ap.add_argument("--instances-per-gpu", type=int, default=None,
                     help="resident handles per rank (default 1; 8 for `--workload er-5pct-2k --gpus 8`, BASELINE configs[3])")
-    ap.add_argument("--repeats", type=int, default=7, help="timed regions (each: reset, W untimed warm-up steps, K timed steps); value = median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions (each: reset, W untimed warm-up steps, K timed steps); value = median (default 1; 7 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: median of 7 regions, roofline passes, strictly-fp32 operands, colourings, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--instance-threads", action="store_true", help="(default with --instances-per-gpu M > 1) one host thread per instance")
     ap.add_argument("--no-instance-threads", action="store_true", help="with --instances-per-gpu M: one host thread enqueues all instances round-robin")
     ap.add_argument("--expm", default="lanczos", choices=["lanczos", "taylor"])
@@ -335,6 +377,7 @@ def main():
         run_group(group, seeds_g, args.warmup)
         for s in group:
             s.read(_lib.F_E_MAX)  # the read-back of the objective record, once untimed (also waits for the warm-up)
+        d0 = group[0].read(_lib.F_DUAL_INFO)
         barrier()
         t0 = time.perf_counter()
         run_group(group, seeds_g, args.steps)
@@ -347,11 +390,13 @@ def main():
         barrier()
         t1 = time.perf_counter()
         el, tail = t1 - t0, t1 - tA
+        d1 = group[0].read(_lib.F_DUAL_INFO)  # steps of the region whose exponential was ONE first-order product (/ in one fp16 half)
+        first = (int(d1[2] - d0[2]), int(d1[3] - d0[3]))
         if dist is not None:  # the slowest rank's clock, after the region
             tt = torch.tensor([el, tail], device=coll_dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el, tail = float(tt[0].item()), float(tt[1].item())
-        return el, tail, table
+        return el, tail, table, first
 
     def run_group(group, seeds_g, n):
         if group is solvers:
@@ -366,81 +411,108 @@ def main():
     for _ in range(3):
         gather([[i, Zi, 0.0, 0.0, 0, 0.0] for i, Zi in zip(mine, Zs)])
         barrier()
-    reps = max(1, args.repeats)
+    reps = max(1, args.repeats if args.repeats is not None else (7 if args.full else 1))
     regions = [timed_region(solvers, seeds) for _ in range(reps)]
     order = sorted(range(reps), key=lambda r: regions[r][0])
-    elapsed, tail_s, table = regions[order[reps // 2]]  # the median region
+    elapsed, tail_s, table, (first_iters, first16_iters) = regions[order[reps // 2]]  # the median region
     el_all = [r[0] for r in regions]
     if os.environ.get('BENCH_DEBUG'):
         print('[bench] regions (us): ' + ' '.join('%.0f(tail %.0f)' % (r[0] * 1e6, r[1] * 1e6) for r in regions), file=sys.stderr)
     info = solver.read(_lib.F_EXPM_INFO)
     m_used = int(info[1])
 
-    # ---- roofline pass: the same number of steps again with HIP events around every kernel class (first instance)
-    solver.reset(nit)
-    solver.iterate(args.warmup, None, seeds[0])
-    solver.set_profile(True)
-    solver.iterate(args.steps, None, seeds[0])
-    kt = solver.kernel_times()
-    solver.set_profile(False)
-    spmm_sync_us, spmm_sync_n = kt["spmm"]
-    # the same brackets around the shipped path (chunks without plan readback: softmax inside the violation pass, lagged plans,
-    # sketch riding in the LOSS launch, the exponential as one first-order product): what a step of the timed region consists of
-    solver.reset(nit)
-    solver.iterate(args.warmup, None, seeds[0])
-    solver.set_profile(2)
-    first0 = float(solver.read(_lib.F_DUAL_INFO)[2])
-    first16_0 = float(solver.read(_lib.F_DUAL_INFO)[3])
-    solver.iterate(args.steps, None, seeds[0])
-    kt2 = solver.kernel_times()
-    solver.set_profile(False)
-    first_iters = int(float(solver.read(_lib.F_DUAL_INFO)[2]) - first0)  # steps of this pass whose exponential was ONE first-order product
-    first16_iters = int(float(solver.read(_lib.F_DUAL_INFO)[3]) - first16_0)  # ... with the matrix in one fp16 half
-    # the roofline figure is the SpMM of the path the timed region runs (launches of the shipped path, HIP events on the solver's stream)
-    spmm_us, spmm_n = kt2["spmm"] if kt2["spmm"][1] else kt["spmm"]
-    K, D, nnzL, C = solver.K, solver.D, solver.nnzL, solver.C
-    b_spmm = nnzL * (w + 4) + (K + 1) * 4 + 2 * K * D * w
-    # launches that do work: a chunk enqueued without plan readback may launch a spare Lanczos stage that the device-side estimate
-    # skips (it returns at once, ~2 us); the synchronous pass counts exact launches for the same steps.  The skipped launches' time
-    # stays in the numerator: the figure is the SpMM time of the shipped path per working launch.
-    spmm_work = min(spmm_n, spmm_sync_n) if spmm_sync_n else spmm_n
-    spmm_avg_us = spmm_us / max(spmm_work, 1)
-    achieved = b_spmm / (spmm_avg_us * 1e-6) / 1e9 if spmm_work else 0.0
-    traffic = None  # HBM-side bytes per launch from the committed rocprofv3 PMC passes of this same command (profiles/)
-    for fn in sorted(os.listdir(os.path.join(ROOT, "profiles"))) if os.path.isdir(os.path.join(ROOT, "profiles")) else []:
-        if fn.endswith(".json") and "pmc_traffic" in fn:
-            try:
-                rec = json.load(open(os.path.join(ROOT, "profiles", fn)))
-                if rec.get("workload") == args.workload and dtype_name == "f32" and args.expm == "lanczos":
-                    traffic = rec.get("traffic_bytes_per_launch_first_order") if first_iters else None
-                    if first16_iters * 2 >= args.steps and rec.get("traffic_bytes_per_launch_first_order_one_half"):
-                        traffic = rec["traffic_bytes_per_launch_first_order_one_half"]
-                    if traffic is None:
-                        traffic = rec["traffic_bytes_per_launch"]
-                    traffic_src = "profiles/" + fn
-            except Exception:
-                pass
-    kinfo = solver.spmm_kernel_info()
-    # the same kernel on the same matrix, 30 launches inside ONE pair of events: the bracket of the per-launch measurement above
-    # (event markers + the dispatch after a host synchronisation, ~5 us) amortised; this is the figure rocprofv3's mean agrees with
-    b2b_us = None
-    try:
-        os.environ["MMW_BENCH_LANCZOS"] = "1"
-        b2b_us = solver.bench_spmm({0: 0, 1: 1, 2: 1, 3: 2}[int(solver.read(_lib.F_SPMM_KIND)[0])], 30)  # generic / LDS-staged / matrix cores
-    except Exception:
-        b2b_us = None
-    finally:
-        os.environ.pop("MMW_BENCH_LANCZOS", None)
-    b2b_first_us = None  # ... and the first-order product (fp16 operands, its whole epilogue) the same way, when the timed region ran on it
-    if first_iters and int(solver.read(_lib.F_SPMM_KIND)[0]) == 3:
-        try:
-            os.environ["MMW_BENCH_FIRST"] = "1"
-            b2b_first_us = solver.bench_spmm(2, 30)
-        except Exception:
-            b2b_first_us = None
-        finally:
-            os.environ.pop("MMW_BENCH_FIRST", None)
+    # ---- what the last timed step computed, read back before anything else runs on the handles
+    if args.dump_outputs and rank == 0:
+        npdt = np.float32 if dtype_name == "f32" else np.float64
+        arrays = {}
+        for i, s in zip(mine, solvers):
+            for name, a in solver_outputs(s, npdt).items():
+                arrays[name if len(solvers) == 1 else "i%d_%s" % (i, name)] = a
+        dump_outputs(args.dump_outputs, arrays)
     spmm_kind = int(solver.read(_lib.F_SPMM_KIND)[0])
+    K, D, nnzL, C = solver.K, solver.D, solver.nnzL, solver.C
+
+    if args.full:
+        # ---- roofline pass: the same number of steps again with HIP events around every kernel class (first instance)
+        solver.reset(nit)
+        solver.iterate(args.warmup, None, seeds[0])
+        solver.set_profile(True)
+        solver.iterate(args.steps, None, seeds[0])
+        kt = solver.kernel_times()
+        solver.set_profile(False)
+        spmm_sync_us, spmm_sync_n = kt["spmm"]
+        # the same brackets around the shipped path (chunks without plan readback: softmax inside the violation pass, lagged plans,
+        # sketch riding in the LOSS launch, the exponential as one first-order product): what a step of the timed region consists of
+        solver.reset(nit)
+        solver.iterate(args.warmup, None, seeds[0])
+        solver.set_profile(2)
+        first0 = float(solver.read(_lib.F_DUAL_INFO)[2])
+        first16_0 = float(solver.read(_lib.F_DUAL_INFO)[3])
+        solver.iterate(args.steps, None, seeds[0])
+        kt2 = solver.kernel_times()
+        solver.set_profile(False)
+        first_iters = int(float(solver.read(_lib.F_DUAL_INFO)[2]) - first0)  # steps of this pass whose exponential was ONE first-order product
+        first16_iters = int(float(solver.read(_lib.F_DUAL_INFO)[3]) - first16_0)  # ... with the matrix in one fp16 half
+        # the roofline figure is the SpMM of the path the timed region runs (launches of the shipped path, HIP events on the solver's stream)
+        spmm_us, spmm_n = kt2["spmm"] if kt2["spmm"][1] else kt["spmm"]
+        b_spmm = nnzL * (w + 4) + (K + 1) * 4 + 2 * K * D * w
+        # launches that do work: a chunk enqueued without plan readback may launch a spare Lanczos stage that the device-side estimate
+        # skips (it returns at once, ~2 us); the synchronous pass counts exact launches for the same steps.  The skipped launches' time
+        # stays in the numerator: the figure is the SpMM time of the shipped path per working launch.
+        spmm_work = min(spmm_n, spmm_sync_n) if spmm_sync_n else spmm_n
+        spmm_avg_us = spmm_us / max(spmm_work, 1)
+        achieved = b_spmm / (spmm_avg_us * 1e-6) / 1e9 if spmm_work else 0.0
+        traffic = None  # HBM-side bytes per launch from the committed rocprofv3 PMC passes of this same command (profiles/)
+        for fn in sorted(os.listdir(os.path.join(ROOT, "profiles"))) if os.path.isdir(os.path.join(ROOT, "profiles")) else []:
+            if fn.endswith(".json") and "pmc_traffic" in fn:
+                try:
+                    rec = json.load(open(os.path.join(ROOT, "profiles", fn)))
+                    if rec.get("workload") == args.workload and dtype_name == "f32" and args.expm == "lanczos":
+                        traffic = rec.get("traffic_bytes_per_launch_first_order") if first_iters else None
+                        if first16_iters * 2 >= args.steps and rec.get("traffic_bytes_per_launch_first_order_one_half"):
+                            traffic = rec["traffic_bytes_per_launch_first_order_one_half"]
+                        if traffic is None:
+                            traffic = rec["traffic_bytes_per_launch"]
+                        traffic_src = "profiles/" + fn
+                except Exception:
+                    pass
+        kinfo = solver.spmm_kernel_info()
+        # the same kernel on the same matrix, 30 launches inside ONE pair of events: the bracket of the per-launch measurement above
+        # (event markers + the dispatch after a host synchronisation, ~5 us) amortised; this is the figure rocprofv3's mean agrees with
+        b2b_us = None
+        try:
+            os.environ["MMW_BENCH_LANCZOS"] = "1"
+            b2b_us = solver.bench_spmm({0: 0, 1: 1, 2: 1, 3: 2}[int(solver.read(_lib.F_SPMM_KIND)[0])], 30)  # generic / LDS-staged / matrix cores
+        except Exception:
+            b2b_us = None
+        finally:
+            os.environ.pop("MMW_BENCH_LANCZOS", None)
+        b2b_first_us = None  # ... and the first-order product (fp16 operands, its whole epilogue) the same way, when the timed region ran on it
+        if first_iters and int(solver.read(_lib.F_SPMM_KIND)[0]) == 3:
+            try:
+                os.environ["MMW_BENCH_FIRST"] = "1"
+                b2b_first_us = solver.bench_spmm(2, 30)
+            except Exception:
+                b2b_first_us = None
+            finally:
+                os.environ.pop("MMW_BENCH_FIRST", None)
+        roofline = {"bound": "hbm", "kernel": kinfo["name"] + " of the %s step" % args.expm +
+                    ("; first-order epilogue (y = u + (L/2 - mu I)u, the whole exponential) in %d of %d steps" % (first_iters, args.steps) if first_iters else ""),
+                    "limiter": kinfo["limiter"],
+                    "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "traffic_source": traffic_src if traffic is not None else None,
+                    "bytes_per_launch": int(b_spmm), "avg_launch_us": round(spmm_avg_us, 2),
+                    "timing": ("HIP start/stop events carried by each launch (hipExtLaunchKernelGGL)" if kinfo["name"].startswith("k_spmm_mfma") and not os.environ.get("MMW_KT_MARKERS")
+                               else "HIP event markers around each launch"),
+                    "avg_launch_us_back_to_back": None if b2b_us is None else round(b2b_us, 2),  # the Lanczos-epilogue launch (two bf16 planes)
+                    "avg_launch_us_back_to_back_first_order": None if b2b_first_us is None else round(b2b_first_us, 2),
+                    "frac_back_to_back": None if not (b2b_first_us or b2b_us) else round(b_spmm / ((b2b_first_us or b2b_us) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                    "avg_launch_us_synchronous": round(spmm_sync_us / max(spmm_sync_n, 1), 2), "launches": int(spmm_work),
+                    "launches_enqueued": int(spmm_n), "launches_per_step": round(spmm_work / max(args.steps, 1), 2)}
+        phases_sync = {k: round(v[0] / max(args.steps, 1), 2) for k, v in kt.items() if v[1]}
+        phases = {k: round(v[0] / max(args.steps, 1), 2) for k, v in kt2.items() if v[1]}
+
     if dtype_name == "f64":
         operand_precision = "fp64 values, operands and accumulation"
     elif spmm_kind == 3:
@@ -452,22 +524,6 @@ def main():
                              "`value_fp32_operands` is the same run with strictly-fp32 operands (MMW_NO_MFMA=1)")
     else:
         operand_precision = "fp32 values, operands and accumulation (no matrix-core product on this pattern)"
-    roofline = {"bound": "hbm", "kernel": kinfo["name"] + " of the %s step" % args.expm +
-                ("; first-order epilogue (y = u + (L/2 - mu I)u, the whole exponential) in %d of %d steps" % (first_iters, args.steps) if first_iters else ""),
-                "limiter": kinfo["limiter"],
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "traffic_source": traffic_src if traffic is not None else None,
-                "bytes_per_launch": int(b_spmm), "avg_launch_us": round(spmm_avg_us, 2),
-                "timing": ("HIP start/stop events carried by each launch (hipExtLaunchKernelGGL)" if kinfo["name"].startswith("k_spmm_mfma") and not os.environ.get("MMW_KT_MARKERS")
-                           else "HIP event markers around each launch"),
-                "avg_launch_us_back_to_back": None if b2b_us is None else round(b2b_us, 2),  # the Lanczos-epilogue launch (two bf16 planes)
-                "avg_launch_us_back_to_back_first_order": None if b2b_first_us is None else round(b2b_first_us, 2),
-                "frac_back_to_back": None if not (b2b_first_us or b2b_us) else round(b_spmm / ((b2b_first_us or b2b_us) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                "avg_launch_us_synchronous": round(spmm_sync_us / max(spmm_sync_n, 1), 2), "launches": int(spmm_work),
-                "launches_enqueued": int(spmm_n), "launches_per_step": round(spmm_work / max(args.steps, 1), 2)}
-    phases_sync = {k: round(v[0] / max(args.steps, 1), 2) for k, v in kt.items() if v[1]}
-    phases = {k: round(v[0] / max(args.steps, 1), 2) for k, v in kt2.items() if v[1]}
 
     out = {
         "metric": "mmw_iterations_per_sec", "value": round(n_inst * args.steps / elapsed, 2), "unit": "it/s",
@@ -484,15 +540,16 @@ def main():
                    "instances": n_inst, "instances_per_gpu": M,
                    "parallelism": "instance-sharded x%d" % world + (", %d resident per GPU" % M if M > 1 else "")},
         "instances_per_s": round(n_inst / elapsed, 3),  # solves of `steps` iterations per second, whole job
-        "roofline": roofline,
-        "device_us_per_step": phases,
-        "device_us_per_step_synchronous": phases_sync,  # the profiling mode the roofline figure comes from: every class in launches of its own
         "objectives": {"max_violation_per_instance": [round(float(x), 6) for x in table[:, 3]]},
     }
+    if args.full:
+        out["roofline"] = roofline
+        out["device_us_per_step"] = phases
+        out["device_us_per_step_synchronous"] = phases_sync  # the profiling mode the roofline figure comes from: every class in launches of its own
 
     # ---- wall-clock to a converged colouring: the whole binary search on the same instance (rank 0, N = 1 only)
     # ---- the same timed regions with strictly-fp32 operands (no 16-bit split anywhere: MMW_NO_MFMA=1 is read at handle creation)
-    if rank == 0 and world == 1 and M == 1 and dtype_name == "f32" and spmm_kind == 3 and not args.no_fp32_operands:
+    if args.full and rank == 0 and world == 1 and M == 1 and dtype_name == "f32" and spmm_kind == 3 and not args.no_fp32_operands:
         os.environ["MMW_NO_MFMA"] = "1"
         try:
             s32 = _lib.Solver(Z, state, nit, args.eta, dtype=dtype, device=local_rank)
@@ -515,7 +572,7 @@ def main():
                                 "spmm_roofline_frac": round(b_spmm / (us32 * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if us32 > 0 else None}
         s32.close()
 
-    if rank == 0 and world == 1 and M == 1 and not args.no_coloring:
+    if args.full and rank == 0 and world == 1 and M == 1 and not args.no_coloring:
         for s in solvers[1:]:
             s.close()
         # reference semantics first (cold probes): THE colouring figure; the warm-started search is an opt-in variant, labelled as such
@@ -527,7 +584,7 @@ def main():
                                                         device_state=geometry0 is not None)
 
     # ---- CPU baseline: the oracle on this host, bounded sample of the same instance (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and args.cpu_iters != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_iters != 0:
         from oracle import mmw_oracle as orc
         rng = np.random.RandomState(0)
         pat = orc.Pattern(Z, state)  # one-off state processing, outside the timed sample like on the GPU side

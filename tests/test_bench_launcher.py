@@ -51,7 +51,7 @@ def _run_bench(args, timeout=900):
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_on_one_device_from_plain_python():
     d = _run_bench(["--gpus", "2", "--backend", "gloo", "--single-device", "--workload", "er-5pct-2k", "--steps", "8", "--warmup", "2",
-                    "--cpu-iters", "0"])
+                    "--cpu-iters", "0", "--full"])
     assert d["n_gpus"] == 2 and d["config"]["instances"] == 2 and d["scaling"] == "weak"
     assert len(d["objectives"]["max_violation_per_instance"]) == 2 and d["value"] > 0
     assert "roofline" in d and "coloring" not in d
@@ -71,7 +71,7 @@ def test_bench_instances_per_gpu_config3_shape():
 def test_bench_line_carries_the_round3_fields_and_the_device_state_path():
     """One short run with the instance generated on the GPU and handed over there (--state device): the line still carries every
     contract field, the spread of the timed regions, the operand disclosure and the three colouring records."""
-    d = _run_bench(["--steps", "8", "--warmup", "4", "--cpu-iters", "2", "--repeats", "3", "--state", "device", "--no-fp32-operands"])
+    d = _run_bench(["--steps", "8", "--warmup", "4", "--cpu-iters", "2", "--repeats", "3", "--state", "device", "--no-fp32-operands", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "value_min", "value_max", "timed_regions", "region_tail_ms"):
         assert k in d, k

@@ -3,16 +3,17 @@
 # separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE do not fit one pass), corrected as MI355X_MICROARCH.md prescribes.
 #   bash tools/pmc_traffic.sh r01_f      -> gpurun_out/<tag>_pmc_traffic_journal-1pct.json (copy it to profiles/)
 TAG=${1:-rXX}
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_traffic
 rm -rf $OUT; mkdir -p $OUT
 # shipped path first (optimistic chunks: the exponential as one first-order product, k_spmm_mfma<4, ...>: every launch of it does work)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/S_$c -- python3 $GRAFT_REPO_ROOT/bench.py --steps 150 --warmup 10 --cpu-iters 0 --no-coloring --no-fp32-operands > $OUT/S_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/S_$c -- python3 $BENCH --full --steps 150 --warmup 10 --cpu-iters 0 --no-coloring --no-fp32-operands > $OUT/S_$c.log 2>&1
 done
 export MMW_SYNC_PLAN=1   # exact launches only: no early-exited stages in the per-kernel means (Lanczos epilogue, k_spmm_mfma<1, ...>)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -- python3 $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --cpu-iters 0 --no-coloring --no-fp32-operands > $OUT/$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -- python3 $BENCH --full --steps 50 --warmup 5 --cpu-iters 0 --no-coloring --no-fp32-operands > $OUT/$c.log 2>&1
 done
 python3 - <<PY
 import csv, glob, json, collections
@@ -35,7 +36,7 @@ shipped = {k: {c: {"launches": v[0], "mean_KB": round(v[1] / v[0], 1)} for c, v 
            if any(t in k for t in ("k_spmm_mfma<4", "k_spmm_mfma<(int)4", "k_spmm_mfma<5", "k_spmm_mfma<(int)5", "k_sddmm_mfma", "k_loss", "k_dual_h", "k_dual_scal"))}
 key = [k for k in allk if "k_spmm_mfma<1" in k or "k_spmm_mfma<(int)1" in k] or [k for k in allk if "k_spmm_blk2<float, 1>" in k or "k_spmm_blk2<float, (int)1>" in k]
 rec = {"workload": "journal-1pct",
-       "command": "MMW_SYNC_PLAN=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py --steps 50 --warmup 5 --cpu-iters 0 --no-coloring",
+       "command": "MMW_SYNC_PLAN=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py --full --steps 50 --warmup 5 --cpu-iters 0 --no-coloring",
        "correction": "MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE reads 1/2 of a wide (16 B/lane) coalesced read stream -> x2; WRITE_SIZE exact; unit KB -> x1024",
        "note": "exact launches (plan read back every iteration); the whole working set (~110 MB) is resident in the 256 MiB Infinity Cache, whose hits these fabric-side counters include",
        "all_kernels_KB": allk}
