@@ -1118,12 +1118,14 @@ template <typename T> struct Solver final : mmw_solver {
                 plan_seen = true;
                 note_plan();
                 m_guess = next_launch_order();
+                say_replay(0, "cautious attempt accepted");
                 return MMW_OK;
             }
             ++replays;
             say_replay(viol, "cautious attempt discarded");
             MMW_TRY(restore_pending());
         }
+        say_replay(0, "replayed synchronously");
         return iterate_impl(pend_n, nullptr, pend_seed, false);
     }
     int iterate(int32_t n, const double* randv, uint64_t seed) override {

@@ -31,18 +31,36 @@ def snapshot(s):
     return d
 
 
+def run_calls(s, calls, seed):
+    """The handle runs one `mmw_iterate(n, NULL, seed)` per entry of `calls` (each chunked by the library); a snapshot after each."""
+    snaps = []
+    for n in calls:
+        s.iterate(n, None, seed)
+        snaps.append(snapshot(s))
+    return snaps
+
+
+def oracle_for(sketch, state, Z, nit, eta, seed, calls):
+    """The oracle on the sketches `sketch(seed, i)` regenerates, its trace kept at the end of every call of `calls`."""
+    o = orc.MMWOracle(nit=nit, eta=eta)
+    o.run(Z, state, lambda i, K, D: sketch(seed, i), keep_trace=set(int(e) - 1 for e in np.cumsum(calls)), factor=False)
+    return o
+
+
+def compare_calls(snaps, o, nit, bars=(1e-5, 1e-4)):
+    """compare() at the end of every call; the last call ends the run (the averages)."""
+    for j, got in enumerate(snaps):
+        compare(got, o, j, j == len(snaps) - 1, nit, bars)
+
+
 def follow(state, Z, nit, n1, eta, seed, dtype=_lib.F32):
     """Device run in two calls (each chunked by the library), then the oracle on the regenerated sketches."""
     s = _lib.Solver(Z, state, nit, eta, dtype=dtype)
     s.set_expm(_lib.EXPM_LANCZOS, 12, 1e-6 if dtype == _lib.F32 else 1e-12)  # bench.py's settings (fp32) / tight for the fp64 bars
-    s.iterate(n1, None, seed)
-    mid = snapshot(s)
-    s.iterate(nit - n1, None, seed)
-    end = snapshot(s)
+    mid, end = run_calls(s, [n1, nit - n1], seed)
     info = s.read(_lib.F_DUAL_INFO)
     replays = s.read(_lib.F_BLOCKING)[3]
-    o = orc.MMWOracle(nit=nit, eta=eta)
-    o.run(Z, state, lambda i, K, D: s.sketch(seed, i), keep_trace={n1 - 1, nit - 1}, factor=False)
+    o = oracle_for(s.sketch, state, Z, nit, eta, seed, [n1, nit - n1])
     s.close()
     return mid, end, o, info, replays
 
