@@ -1,4 +1,4 @@
-"""Overlay of `sim_src.alg`: only `mmw` is replaced; the rest resolves from the reference tree."""
+"""Overlay of `sim_src.alg`: `mmw` and `gm` are replaced; the rest resolves from the reference tree."""
 import pkgutil
 
 __path__ = pkgutil.extend_path(__path__, __name__)

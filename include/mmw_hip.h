@@ -245,6 +245,43 @@ int mmw_env_evaluate(mmw_env* e, const double* z_vec, int32_t Z, double packet_b
 int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, int32_t rank_radio, double eta, int32_t nit);
 int mmw_env_bounds(mmw_env* e, int32_t out[2]);
 
+/*
+ * The greedy baselines of sim_src/alg/gm.py on a light handle (csrc/kernels_gm.h): no MMW pattern, no blocking.
+ *
+ * mmw_gm_create: the per-call preparation of MAX_GAIN.run / MAX_ASSO.run / MAX_RAND.run (gm.py:11-18, 74-80, 136-142), once per state:
+ * the rows of S_gain with the diagonal zeroed (setdiag(0), explicit zeros dropped: they add nothing and fail nothing), the rows of
+ * Q_asso, h_max, and whether Q is a union of cliques with weights >= 1 (env.py:182-189), in which case the association check is one
+ * owner per access point and slot.  S and Q as canonical int32 CSR (sorted, no duplicates), Q without diagonal.
+ * device == -1: the same procedures as plain host C++ (no HIP call).
+ * mmw_gm_sizes: out = {K, clique groups (-1: Q is not a union of cliques, the general check runs), nnz of the S rows, nnz(Q)}.
+ */
+typedef struct mmw_gm mmw_gm;
+int mmw_gm_create(mmw_gm** out, int device, int32_t K, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
+                  const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max);
+int mmw_gm_destroy(mmw_gm* g);
+int mmw_gm_sizes(mmw_gm* g, int64_t out[4]);
+/*
+ * mmw_gm_pass: one slot of MAX_GAIN / MAX_ASSO (the body of `for z in range(Z)`, gm.py:25-56 / 86-113) for the visiting order
+ * order[0..n) the caller formed (kindx[np.argsort(-key[not_assigned])], :31-32 / :88-89; distinct users, all unassigned): `nattempt`
+ * attempts on sums set to zero once per call and carried from attempt to attempt (:26-27), the first longest list wins (:53-54).
+ * list_out[0..*nlist) receives it in acceptance order (caller-sized n).
+ */
+int mmw_gm_pass(mmw_gm* g, const int32_t* order, int32_t n, int32_t nattempt, int32_t* list_out, int32_t* nlist);
+/*
+ * mmw_gm_run: the whole slot loop of MAX_GAIN / MAX_ASSO (gm.py:24-58 / 85-115) in one device call, with the visiting order
+ * argsort(-key, kind="stable") ranked on the device (ties to the lower user index; the order restricted to the unassigned users is
+ * then the same for every slot).  Z: slot bound (K for not_Z_bound, :22-23).  z_out[K]: slot or -1 for a user left unassigned (the
+ * caller draws those, :60-64); *zz_out: ZZ, the slots entered (a slot that accepts nobody ends the loop early: every later slot
+ * would accept nobody either, ZZ = Z); *rem_out: users left over.
+ */
+int mmw_gm_run(mmw_gm* g, const double* key, int32_t Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out, int32_t* rem_out);
+/*
+ * mmw_gm_assign: MAX_RAND's user-major greedy (gm.py:152-193, the same procedure as sdp_solver.rounding_one_attempt) for the user
+ * order order[K] (`rank`, :150) and the per-user slot preference pref[K*Z] (row k = sorted_indices[:, k], :149), on the rounding's
+ * greedy kernels.  z_out[K]: slot or -1 (the caller draws those, :197-198); *rem_out: users left over.
+ */
+int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pref, int32_t* z_out, int32_t* rem_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,8 @@ I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X
 EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "mmw_destroy", "mmw_sizes", "mmw_set_expm",
            "mmw_set_timing", "mmw_set_profile", "mmw_bench_spmm", "mmw_reset", "mmw_set_slots", "mmw_set_slots_warm", "mmw_set_eta", "mmw_iterate", "mmw_sync", "mmw_sketch", "mmw_read_f64", "mmw_read_i32", "mmw_gap",
            "mmw_factor", "mmw_expm_apply", "mmw_sym_eig", "mmw_round", "mmw_env_create", "mmw_env_destroy", "mmw_env_sizes", "mmw_env_state",
-           "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds"]
+           "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds", "mmw_gm_create", "mmw_gm_destroy", "mmw_gm_sizes", "mmw_gm_pass",
+           "mmw_gm_run", "mmw_gm_assign"]
 
 
 class MMWError(RuntimeError):
@@ -80,6 +81,12 @@ def lib():
     L.mmw_env_evaluate.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_double, C.c_double, C.c_double, p_f64, p_f64]
     L.mmw_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.mmw_env_bounds.argtypes = [C.c_void_p, p_i32]
+    L.mmw_gm_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64]
+    L.mmw_gm_destroy.argtypes = [C.c_void_p]
+    L.mmw_gm_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.mmw_gm_pass.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int32, p_i32, p_i32]
+    L.mmw_gm_run.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_int32, p_i32, p_i32, p_i32]
+    L.mmw_gm_assign.argtypes = [C.c_void_p, C.c_int32, p_i32, p_i32, p_i32, p_i32]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -455,6 +462,65 @@ class DeviceState:
 
     def __len__(self):
         return 3
+
+
+class GreedyHandle:
+    """Owning wrapper of one `mmw_gm*`: the state of the greedy baselines of gm.py (mmw_gm_create), device = -1 for host C++."""
+
+    def __init__(self, state, device=0):
+        S, Q, h = state
+        self.K = int(S.shape[0])
+        if S.shape != (self.K, self.K) or Q.shape != (self.K, self.K) or len(h) != self.K:
+            raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
+        sp, si, sx = canonical_csr(S)
+        qp, qi, qx = canonical_csr(Q)
+        hm = _f64(h)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        check(lib().mmw_gm_create(C.byref(self._h), self.device, self.K, _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(hm)))
+        sz = (C.c_int64 * 4)()
+        check(lib().mmw_gm_sizes(self._h, sz))
+        self.groups = int(sz[1])  # -1: Q is not a union of cliques (general association check)
+
+    def pass_(self, order, nattempt=1):
+        """One slot for the visiting order `order` (unassigned users): the accepted users, in acceptance order."""
+        o = _i32(order)
+        out = np.empty(max(o.size, 1), dtype=np.int32)
+        n = C.c_int32(0)
+        check(lib().mmw_gm_pass(self._h, _pi(o), int(o.size), int(nattempt), _pi(out), C.byref(n)))
+        return out[:n.value]
+
+    def run(self, key, Z, nattempt=1):
+        """All slots under the stable order of -key: (slot int32[K] with -1 = unassigned, ZZ, remainder)."""
+        k = _f64(key)
+        if k.shape != (self.K,):
+            raise MMWError("key must hold one value per user")
+        z = np.empty(self.K, dtype=np.int32)
+        zz, rem = C.c_int32(0), C.c_int32(0)
+        check(lib().mmw_gm_run(self._h, _pd(k), int(Z), int(nattempt), _pi(z), C.byref(zz), C.byref(rem)))
+        return z, zz.value, rem.value
+
+    def assign(self, order, pref):
+        """User-major greedy: order[K], pref (K, Z) slot preference per user; returns (slot int32[K] with -1, remainder)."""
+        o = _i32(order)
+        p = _i32(pref)
+        if o.shape != (self.K,) or p.ndim != 2 or p.shape[0] != self.K:
+            raise MMWError("assign: order must be (K,) and pref (K, Z)")
+        z = np.empty(self.K, dtype=np.int32)
+        rem = C.c_int32(0)
+        check(lib().mmw_gm_assign(self._h, int(p.shape[1]), _pi(o), _pi(p), _pi(z), C.byref(rem)))
+        return z, rem.value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().mmw_gm_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sym_eig(G, rel_tol=1e-13, max_sweeps=30, device=0):
