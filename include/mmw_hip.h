@@ -282,6 +282,57 @@ int mmw_gm_run(mmw_gm* g, const double* key, int32_t Z, int32_t nattempt, int32_
  */
 int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pref, int32_t* z_out, int32_t* rem_out);
 
+/*
+ * Batched solver: B small independent fp64 instances, ONE workgroup per instance and `n` MMW iterations per launch
+ * (csrc/kernels_batch.h).  For the sweeps of the reference (many seeds x cell sizes, K = 75 ... 675 users per instance), where a
+ * handle's iteration is a chain of ~20 launches of a few us each.  Nothing waits across workgroups and every reduction runs in a
+ * fixed order inside the instance's workgroup: an instance's results are bitwise independent of its batch neighbours and of how
+ * its iterations are split into calls.  Limits (refused with MMW_ERR_ARG and a message; such instances stay on handles):
+ * K <= 4096, D = Z * rank_radio <= 512, nnzL <= 2^22, 96 MiB of device memory per instance.
+ *
+ * mmw_batch_create: mmw_create's state processing (csrc/pattern.h) per instance -- K[b], Z[b], nit[b] and the CSR arrays of
+ * instance b behind the b-th pointer of each array -- then all of them packed into one device arena at the initial point.
+ * device == -1 builds the host side only (mmw_batch_read_i32 and the host fields S_SUM / NORM_H / ST_DATA answer).
+ * mmw_batch_sizes: out as mmw_sizes for instance `inst` (Dpad = D: the batch keeps K x D blocks unpadded).
+ */
+typedef struct mmw_batch mmw_batch;
+int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, const int32_t* Z, int32_t rank_radio, double eta,
+                     const int32_t* nit, const int32_t* const* S_indptr, const int32_t* const* S_indices, const double* const* S_data,
+                     const int32_t* const* Q_indptr, const int32_t* const* Q_indices, const double* const* Q_data, const double* const* h_max);
+int mmw_batch_destroy(mmw_batch* b);
+int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]);
+/* per-instance slot counts for the next probes (norm_H and D rebuilt, every instance reset to the initial point with `nit`);
+ * Z[b] <= 0 takes instance b out of the runs until a later call gives it a slot count */
+int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit);
+int mmw_batch_reset(mmw_batch* b, int32_t nit);
+/* one step size per instance (eta[B]) for the iterations that follow */
+int mmw_batch_set_eta(mmw_batch* b, const double* eta);
+/* Taylor degree cap per substep (<= 16) and target relative accuracy of exp(L/2)R, per column (default 16, 1e-9) */
+int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol);
+/*
+ * mmw_batch_iterate: every instance runs min(n, nit - iterations done) iterations of mmw.py:75-200 in one launch; returns when done.
+ * randv: NULL -> Philox sketches on the device, instance b keyed by seeds[b] with the counter layout of mmw_iterate(..., NULL, seed)
+ * (a block is bitwise mmw_sketch's); otherwise the row-normalised K x D blocks of every instance that runs, instance after instance,
+ * iteration-major within an instance (parity mode).
+ */
+int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64_t* seeds);
+/* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
+ * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
+int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);
+int mmw_batch_read_i32(mmw_batch* b, int32_t inst, int which, int32_t* out, int64_t n);
+/* the block the device generator draws for instance `inst` in `iteration` of a run with `seed` (mmw_sketch's semantics) */
+int mmw_batch_sketch(mmw_batch* b, int32_t inst, uint64_t seed, int32_t iteration, double* out, int64_t n);
+/*
+ * mmw_batch_export: device-to-device copy of the instance's iterate (L, X, Xbar sum, Y, Ybar sum, e_accu, e_this, iteration count,
+ * nit) into an fp64 handle that mmw_create made from the same (state, Z): the handle is reset first (plans, chains, timers), its
+ * derived copies of L are rebuilt, and it then behaves as if it had run those iterations itself -- mmw_factor, mmw_round and mmw_gap
+ * run on it unchanged, and further mmw_iterate calls continue the run.  The batch's MMW_F_XAVG / MMW_F_YAVG hold X_0 + ... + X_{i-1}
+ * after i iterations; a handle's hold X_0 + ... + X_i while iterations remain (mmw_gap reads i + 1 terms), so before the last
+ * iteration the export adds the current X and Y to the sums it hands over.  Refuses fp32 handles and a handle whose K / Z / pattern
+ * differ.
+ */
+int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h);
+
 #ifdef __cplusplus
 }
 #endif

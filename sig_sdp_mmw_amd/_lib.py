@@ -25,7 +25,9 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_set_timing", "mmw_set_profile", "mmw_bench_spmm", "mmw_reset", "mmw_set_slots", "mmw_set_slots_warm", "mmw_set_eta", "mmw_iterate", "mmw_sync", "mmw_sketch", "mmw_read_f64", "mmw_read_i32", "mmw_gap",
            "mmw_factor", "mmw_expm_apply", "mmw_sym_eig", "mmw_round", "mmw_env_create", "mmw_env_destroy", "mmw_env_sizes", "mmw_env_state",
            "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds", "mmw_gm_create", "mmw_gm_destroy", "mmw_gm_sizes", "mmw_gm_pass",
-           "mmw_gm_run", "mmw_gm_assign"]
+           "mmw_gm_run", "mmw_gm_assign", "mmw_batch_create", "mmw_batch_destroy", "mmw_batch_sizes", "mmw_batch_set_slots",
+           "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
+           "mmw_batch_sketch", "mmw_batch_export"]
 
 
 class MMWError(RuntimeError):
@@ -87,6 +89,21 @@ def lib():
     L.mmw_gm_pass.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int32, p_i32, p_i32]
     L.mmw_gm_run.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_int32, p_i32, p_i32, p_i32]
     L.mmw_gm_assign.argtypes = [C.c_void_p, C.c_int32, p_i32, p_i32, p_i32, p_i32]
+    pp_i32 = C.POINTER(p_i32)
+    pp_f64 = C.POINTER(p_f64)
+    L.mmw_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, p_i32, p_i32, C.c_int32, C.c_double, p_i32,
+                                   pp_i32, pp_i32, pp_f64, pp_i32, pp_i32, pp_f64, pp_f64]
+    L.mmw_batch_destroy.argtypes = [C.c_void_p]
+    L.mmw_batch_sizes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+    L.mmw_batch_set_slots.argtypes = [C.c_void_p, p_i32, C.c_int32]
+    L.mmw_batch_reset.argtypes = [C.c_void_p, C.c_int32]
+    L.mmw_batch_set_eta.argtypes = [C.c_void_p, p_f64]
+    L.mmw_batch_set_expm.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    L.mmw_batch_iterate.argtypes = [C.c_void_p, C.c_int32, p_f64, C.POINTER(C.c_uint64)]
+    L.mmw_batch_read_f64.argtypes = [C.c_void_p, C.c_int32, C.c_int, p_f64, C.c_int64]
+    L.mmw_batch_read_i32.argtypes = [C.c_void_p, C.c_int32, C.c_int, p_i32, C.c_int64]
+    L.mmw_batch_sketch.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
+    L.mmw_batch_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -339,6 +356,157 @@ class Solver:
         rem = np.empty(nb, dtype=np.int32)
         check(lib().mmw_round(self._h, int(Z), int(Dp), None if on_device else _pd(gX), int(nb), _pd(randv), _pi(z), _pi(rem)))
         return z, rem
+
+
+class BatchSolver:
+    """Owning wrapper of one `mmw_batch*`: B small fp64 instances, one workgroup each, `n` iterations per launch
+    (csrc/kernels_batch.h).  Mirrors `Solver` with an instance index on every per-instance call.  `nit` is one count for all
+    instances or one per instance; Zs one slot count per instance."""
+
+    def __init__(self, Zs, states, nit, eta, rank_radio=2, device=0):
+        self.B = B = len(states)
+        if B < 1 or len(Zs) != B:
+            raise MMWError("BatchSolver: one slot count per state, at least one state")
+        nits = np.broadcast_to(np.asarray(nit, dtype=np.int32), (B,))
+        self._keep = []
+        arrays = {k: [] for k in ("sp", "si", "sx", "qp", "qi", "qx", "h")}
+        Ks = []
+        for S, Q, h in states:
+            K = int(S.shape[0])
+            if S.shape != (K, K) or Q.shape != (K, K) or len(h) != K:
+                raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
+            Ks.append(K)
+            sp, si, sx = canonical_csr(S)
+            qp, qi, qx = canonical_csr(Q)
+            for k, a in zip(("sp", "si", "sx", "qp", "qi", "qx", "h"), (sp, si, sx, qp, qi, qx, _f64(h))):
+                arrays[k].append(a)
+        self._keep.append(arrays)
+
+        def ptrs(name, ctype):
+            arr = (C.POINTER(ctype) * B)(*[a.ctypes.data_as(C.POINTER(ctype)) for a in arrays[name]])
+            self._keep.append(arr)
+            return arr
+        Karr, Zarr, narr = _i32(Ks), _i32(Zs), _i32(nits)
+        self._h = C.c_void_p()
+        check(lib().mmw_batch_create(C.byref(self._h), int(device), B, _pi(Karr), _pi(Zarr), int(rank_radio), float(eta), _pi(narr),
+                                     ptrs("sp", C.c_int32), ptrs("si", C.c_int32), ptrs("sx", C.c_double),
+                                     ptrs("qp", C.c_int32), ptrs("qi", C.c_int32), ptrs("qx", C.c_double), ptrs("h", C.c_double)))
+        self._keep = None
+        self.device = int(device)
+        self.nits = [int(x) for x in nits]
+        self.active = [True] * B
+        self._load_sizes()
+
+    def _load_sizes(self):
+        self.sizes = []
+        for b in range(self.B):
+            sz = (C.c_int64 * 10)()
+            check(lib().mmw_batch_sizes(self._h, b, sz))
+            self.sizes.append(dict(zip(("K", "Z", "D", "Dpad", "nnzL", "nnzST", "E_gain", "E_asso", "C", "iter"), [int(x) for x in sz])))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().mmw_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def iterations_done(self, inst):
+        sz = (C.c_int64 * 10)()
+        check(lib().mmw_batch_sizes(self._h, int(inst), sz))
+        return int(sz[9])
+
+    def set_expm(self, max_order=16, tol=1e-9):
+        check(lib().mmw_batch_set_expm(self._h, int(max_order), float(tol)))
+
+    def set_eta(self, eta):
+        """One step size for every instance, or one per instance."""
+        e = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (self.B,)))
+        check(lib().mmw_batch_set_eta(self._h, _pd(e)))
+
+    def reset(self, nit):
+        check(lib().mmw_batch_reset(self._h, int(nit)))
+        self.nits = [int(nit)] * self.B
+        self._load_sizes()
+
+    def set_slots(self, Zs, nit):
+        """Per-instance slot counts (0: the instance sits out until a later call gives it one); every instance restarts."""
+        z = _i32(Zs)
+        if z.size != self.B:
+            raise MMWError("set_slots: one slot count per instance")
+        check(lib().mmw_batch_set_slots(self._h, _pi(z), int(nit)))
+        self.nits = [int(nit)] * self.B
+        self.active = [int(x) > 0 for x in z]
+        self._load_sizes()
+
+    def iterate(self, n, randv=None, seeds=None):
+        """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the
+        n_b = min(n, nit - done) iterations it runs (instances that run nothing: None or an empty array)."""
+        n = int(n)
+        if randv is None:
+            if seeds is None:
+                raise MMWError("iterate: give sketches or one seed per instance")
+            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
+            check(lib().mmw_batch_iterate(self._h, n, None, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        else:
+            if len(randv) != self.B:
+                raise MMWError("iterate: one block list per instance")
+            parts = []
+            for b, r in enumerate(randv):
+                sz = self.sizes[b]
+                nb = max(0, min(n, self.nits[b] - sz["iter"])) if self.active[b] else 0
+                a = np.zeros(0) if r is None or nb == 0 else _f64(r).ravel()
+                if a.size != nb * sz["K"] * sz["D"]:
+                    raise MMWError("iterate: instance %d runs %d iterations and needs %d sketch values, got %d"
+                                   % (b, nb, nb * sz["K"] * sz["D"], a.size))
+                parts.append(a)
+            flat = _f64(np.concatenate(parts)) if parts else np.zeros(0)
+            check(lib().mmw_batch_iterate(self._h, n, _pd(flat), None))
+        self._load_sizes()
+
+    def sketch(self, inst, seed, iteration):
+        sz = self.sizes[inst]
+        out = np.empty((sz["K"], sz["D"]), dtype=np.float64)
+        check(lib().mmw_batch_sketch(self._h, int(inst), C.c_uint64(int(seed)), int(iteration), _pd(out), int(out.size)))
+        return out
+
+    _LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", F_XAVG: "nnzL", F_YAVG: "C",
+            F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST"}
+
+    def read(self, inst, which, n=None):
+        sz = self.sizes[inst]
+        if n is None:
+            if which in (F_XHALF, F_SKETCH):
+                n = sz["K"] * sz["D"]
+            elif which == F_EXPM_INFO:
+                n = 4
+            else:
+                n = sz[self._LEN[which]]
+        out = np.empty(int(n), dtype=np.float64)
+        check(lib().mmw_batch_read_f64(self._h, int(inst), int(which), _pd(out), int(n)))
+        if which in (F_XHALF, F_SKETCH):
+            out = out.reshape(sz["K"], sz["D"])
+        return out
+
+    _ILEN = {I_L_INDPTR: lambda s: s["K"] + 1, I_L_INDICES: lambda s: s["nnzL"], I_ST_INDPTR: lambda s: s["K"] + 1,
+             I_ST_INDICES: lambda s: s["nnzST"], I_GAIN_X: lambda s: s["E_gain"], I_GAIN_Y: lambda s: s["E_gain"],
+             I_ASSO_X: lambda s: s["E_asso"], I_ASSO_Y: lambda s: s["E_asso"], I_DIAG_POS: lambda s: s["K"],
+             I_ASSO_POS: lambda s: s["E_asso"]}
+
+    def read_i32(self, inst, which):
+        n = self._ILEN[which](self.sizes[inst])
+        out = np.empty(int(n), dtype=np.int32)
+        check(lib().mmw_batch_read_i32(self._h, int(inst), int(which), _pi(out), int(n)))
+        return out
+
+    def export(self, inst, solver):
+        """The instance's iterate into `solver` (an fp64 `Solver` of the same state and Z), which then factors / rounds it."""
+        check(lib().mmw_batch_export(self._h, int(inst), solver._h))
+        solver._timed = 0
 
 
 class DeviceFactor(np.lib.mixins.NDArrayOperatorsMixin):

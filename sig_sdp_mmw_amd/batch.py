@@ -1,0 +1,158 @@
+"""Many small MMW solves at once: the batched solver (one workgroup per instance, csrc/kernels_batch.h) behind the reference's
+sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_search_relaxation` per instance).
+
+    ok_xhalf = run_with_state_many(it, Zs, states, nit=150, eta=0.04, seeds=seeds)   # [(True, X_half), ...]
+    results  = search_many(states, nit=150, eta=0.04, seed=0)                          # [{"Z", "z_vec", "remainder", "probes"}, ...]
+
+The iterations of every instance run in one launch per call; X_half comes from the tested per-handle epilogue: the instance's
+iterate is exported into an fp64 handle of the same state (mmw_batch_export) and `mmw_factor` / `mmw_round` run there.
+
+`search_many` runs the bisection of binary_search_relaxation.py:44-72 for all instances in lockstep: each instance keeps its own
+bounds, all current probes run in one `mmw_batch_iterate`, and an instance whose search has ended sits out.  Sketches are the
+device's Philox blocks keyed by a per-(instance, probe) seed, and the rounding's projections come from a generator keyed the same
+way, so `single(state, index)` -- the reference's `run_with_state` / `rounding` protocol backed by a batch of one -- driven by
+`binary_search_relaxation` makes the same probes and ends at the same Z (instances are bitwise independent of their batch).
+"""
+import math
+
+import numpy as np
+
+from . import _lib
+from .binary_search import binary_search_relaxation
+
+
+def probe_seed(seed, index, probe):
+    """The device sketch seed of probe `probe` of instance `index` (what search_many and single agree on)."""
+    return ((int(seed) & 0xFFFFFF) << 40) | ((int(index) & 0xFFFFF) << 20) | (int(probe) & 0xFFFFF)
+
+
+def _rank(K, Z, rank_radio):
+    return int(min(K - 1, (Z - 1) * rank_radio))
+
+
+class _Handles:
+    """One fp64 handle per state, rebound to each probe's slot count (the export target)."""
+
+    def __init__(self, states, nit, eta, rank_radio, device):
+        self.states, self.nit, self.eta, self.rank_radio, self.device = states, nit, eta, rank_radio, device
+        self.h = [None] * len(states)
+
+    def get(self, i, Z):
+        h = self.h[i]
+        if h is None:
+            h = self.h[i] = _lib.Solver(Z, self.states[i], self.nit, self.eta, rank_radio=self.rank_radio, dtype=_lib.F64, device=self.device)
+        elif h.Z != Z:
+            h.set_slots(Z, self.nit)
+        return h
+
+    def close(self):
+        for h in self.h:
+            if h is not None:
+                h.close()
+        self.h = [None] * len(self.states)
+
+
+def _factor(batch, i, handle, Z, rank_radio, seed):
+    batch.export(i, handle)
+    return handle.factor(_rank(handle.K, Z, rank_radio), seed=seed)
+
+
+def _round(handle, Z, X_half, state, seed, nattempt):
+    """sdp_solver.rounding (sdp_solver.py:18-25): up to `nattempt` attempts, the first with remainder 0 wins; projections and the
+    random slots of users left over (:104-105) from a generator keyed by `seed`."""
+    rng = np.random.default_rng(seed)
+    Dp = X_half.shape[1]
+    r = rng.standard_normal((nattempt, Z, Dp))
+    r = r / np.linalg.norm(r, axis=2, keepdims=True)
+    z, rem = handle.round(Z, X_half, r)
+    a = int(np.argmax(rem == 0)) if np.any(rem == 0) else nattempt - 1
+    z_vec = z[a].astype(np.float64)
+    un = z[a] < 0
+    if np.any(un):
+        z_vec[un] = rng.integers(0, Z, size=int(un.sum()))
+    return z_vec, Z, int(rem[a])
+
+
+def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0):
+    """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
+    X_half per instance through export + mmw_factor on one reused fp64 handle per state.  Returns [(True, X_half), ...]."""
+    del bs_iteration  # the log index of the reference's signature; nothing here depends on it
+    seeds = np.arange(len(states), dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
+    b = _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device)
+    hs = _Handles(states, nit, eta, rank_radio, device)
+    try:
+        b.iterate(nit, None, seeds)
+        return [(True, _factor(b, i, hs.get(i, int(Z)), int(Z), rank_radio, factor_seed)) for i, Z in enumerate(Zs)]
+    finally:
+        hs.close()
+        b.close()
+
+
+def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0):
+    """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
+    Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}."""
+    B = len(states)
+    bs = binary_search_relaxation()
+    bounds = [bs.set_bounds(st) for st in states]
+    left = [lb for lb, _ in bounds]
+    right = [ub for _, ub in bounds]
+    done = [False] * B
+    probes = [[] for _ in range(B)]
+    out = [None] * B
+    mids = [max(2, math.floor(float(l + r) / 2.)) for l, r in zip(left, right)]
+    b = _lib.BatchSolver(mids, states, nit, eta, rank_radio=rank_radio, device=device)
+    hs = _Handles(states, nit, eta, rank_radio, device)
+    try:
+        while not all(done):
+            mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
+            b.set_slots(mids, nit)
+            seeds = np.array([probe_seed(seed, i, len(probes[i])) for i in range(B)], dtype=np.uint64)
+            b.iterate(nit, None, seeds)
+            for i in range(B):
+                if done[i]:
+                    continue
+                Z = mids[i]
+                h = hs.get(i, Z)
+                Xh = _factor(b, i, h, Z, rank_radio, 0)
+                z_vec, Z, rem = _round(h, Z, Xh, states[i], probe_seed(seed, i, len(probes[i])), nattempt)
+                probes[i].append(Z)
+                left[i], right[i], fin = binary_search_relaxation._step(left[i], right[i], Z, rem)
+                if fin:
+                    done[i] = True
+                    out[i] = {"Z": Z, "z_vec": z_vec, "remainder": rem, "probes": probes[i], "bounds": bounds[i]}
+        return out
+    finally:
+        hs.close()
+        b.close()
+
+
+class single:
+    """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
+    one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
+
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0):
+        self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
+        self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
+        self.probes = []
+        self._b = None
+        self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
+
+    def run_with_state(self, bs_iteration, Z, state):
+        Z = int(Z)
+        if self._b is None:
+            self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
+        self._b.set_slots([Z], self.nit)
+        self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])
+        self._h = self._hs.get(0, Z)
+        return True, _factor(self._b, 0, self._h, Z, self.rank_radio, 0)
+
+    def rounding(self, Z, gX, state):
+        z_vec, Z, rem = _round(self._h, int(Z), gX, state, probe_seed(self.seed, self.index, len(self.probes)), self.nattempt)
+        self.probes.append(int(Z))
+        return z_vec, Z, rem
+
+    def close(self):
+        self._hs.close()
+        if self._b is not None:
+            self._b.close()
+            self._b = None

@@ -2246,3 +2246,454 @@ int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pre
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Batched solver: many small fp64 instances, one workgroup each (csrc/kernels_batch.h).  Every instance's pattern is built by the
+// host code mmw_create uses (build_pattern / update_slots), then all of them are packed into one int32 and one fp64 arena.
+// ------------------------------------------------------------------------------------------------------------------------------
+#include "kernels_batch.h"
+
+struct mmw_batch {
+    int device = 0;
+    bool host_only = false;
+    hipStream_t st = nullptr;
+    int B = 0, rank_radio = 2, max_order = MAX_ORDER;
+    double tol = 1e-9;
+    std::vector<double> eta;  // per instance
+    std::vector<HostPattern> H;
+    std::vector<int> nit, iter;
+    std::vector<char> active;
+    std::vector<BatchDesc> desc;  // offsets and sizes; nrun / iter0 / seed / o_randv are set per call
+    DevBuf<int> ia;
+    DevBuf<double> fa, rbuf, skbuf;
+    DevBuf<BatchDesc> d_desc;
+
+    ~mmw_batch() {
+        if (host_only || !st) return;
+        (void)hipSetDevice(device);
+        (void)hipStreamDestroy(st);
+    }
+
+    static std::string check_limits(const HostPattern& P, int D) {
+        if (P.K > BATCH_MAX_K) return "K = " + std::to_string(P.K) + " exceeds the batch limit " + std::to_string(BATCH_MAX_K);
+        if (D > BATCH_MAX_D) return "D = " + std::to_string(D) + " exceeds the batch limit " + std::to_string(BATCH_MAX_D);
+        if (P.nnzL() > BATCH_MAX_NNZ) return "nnzL = " + std::to_string(P.nnzL()) + " exceeds the batch limit " + std::to_string(BATCH_MAX_NNZ);
+        const int64_t bytes = fp64_words(P, D) * 8 + int_words(P) * 4;
+        if (bytes > BATCH_MAX_BYTES) return "instance needs " + std::to_string(bytes) + " bytes, over the batch limit " + std::to_string(BATCH_MAX_BYTES);
+        return "";
+    }
+    static int64_t int_words(const HostPattern& P) { return (int64_t)P.K + 1 + 3 * P.nnzL() + P.K + P.E_asso(); }
+    static int64_t fp64_words(const HostPattern& P, int D) {
+        const int64_t K = P.K, nnz = P.nnzL(), C = P.C();
+        return 5 * nnz + 6 * K + 4 * C + 4 * K * D + 4 + 64;
+    }
+
+    // offsets of every instance; the int32 arena never changes, the fp64 one follows the slot counts
+    int layout() {
+        desc.assign(B, BatchDesc{});
+        int64_t oi = 0, of = 0;
+        auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };  // 256-byte aligned instance arrays
+        for (int b = 0; b < B; ++b) {
+            const HostPattern& P = H[b];
+            BatchDesc& d = desc[b];
+            const int64_t K = P.K, nnz = P.nnzL(), C = P.C();
+            d.K = P.K; d.Z = P.Z; d.D = P.Z * rank_radio; d.E_asso = (int)P.E_asso(); d.C = (int)C; d.nnzL = (int)nnz;
+            d.max_order = max_order; d.eta = eta[b]; d.tol = tol; d.o_randv = -1;
+            const std::string err = check_limits(P, d.D);
+            if (!err.empty()) return fail(MMW_ERR_ARG, "mmw_batch: instance " + std::to_string(b) + ": " + err + " (run it on a handle)");
+            d.o_indptr = oi; oi += K + 1;
+            d.o_col = oi; oi += nnz;
+            d.o_lrow = oi; oi += nnz;
+            d.o_pid = oi; oi += nnz;
+            d.o_diag = oi; oi += K;
+            d.o_apos = oi; oi += P.E_asso();
+            oi = a32(oi);
+            const int64_t KD = K * d.D;
+            d.o_sab = of; of += 2 * nnz;  // sab, then sba
+            d.o_hmax = of; of += K;
+            d.o_ssum = of; of += K;
+            d.o_invn = of; of += K;
+            d.o_cH = of; of += K;
+            d.o_lval = of = a32(of); of += nnz;
+            d.o_xval = of = a32(of); of += nnz;
+            d.o_xavg = of = a32(of); of += nnz;
+            d.o_Y = of = a32(of); of += C;
+            d.o_yavg = of = a32(of); of += C;
+            d.o_eaccu = of = a32(of); of += C;
+            d.o_ethis = of = a32(of); of += C;
+            d.o_wH = of = a32(of); of += K;
+            d.o_rsum = of = a32(of); of += K;
+            d.o_Xh = of = a32(of); of += KD;
+            d.o_R = of = a32(of); of += KD;
+            d.o_W1 = of = a32(of); of += KD;
+            d.o_W2 = of = a32(of); of += KD;
+            d.o_info = of = a32(of); of += 4;
+            of = a32(of);
+        }
+        if (host_only) return MMW_OK;
+        std::vector<int> hi((size_t)oi, 0);
+        std::vector<double> hf((size_t)of, 0.0);
+        for (int b = 0; b < B; ++b) {
+            const HostPattern& P = H[b];
+            const BatchDesc& d = desc[b];
+            const int K = P.K;
+            const int64_t nnz = P.nnzL();
+            std::copy(P.l_indptr.begin(), P.l_indptr.end(), hi.begin() + d.o_indptr);
+            std::copy(P.l_indices.begin(), P.l_indices.end(), hi.begin() + d.o_col);
+            for (int k = 0; k < K; ++k)
+                for (int e = P.l_indptr[k]; e < P.l_indptr[k + 1]; ++e) hi[d.o_lrow + e] = k;
+            std::copy(P.pid.begin(), P.pid.end(), hi.begin() + d.o_pid);
+            std::copy(P.diag_pos.begin(), P.diag_pos.end(), hi.begin() + d.o_diag);
+            std::copy(P.asso_pos.begin(), P.asso_pos.end(), hi.begin() + d.o_apos);
+            std::copy(P.sab.begin(), P.sab.end(), hf.begin() + d.o_sab);
+            std::copy(P.sba.begin(), P.sba.end(), hf.begin() + d.o_sab + nnz);
+            std::copy(P.h_max.begin(), P.h_max.end(), hf.begin() + d.o_hmax);
+            std::copy(P.S_sum.begin(), P.S_sum.end(), hf.begin() + d.o_ssum);
+            for (int k = 0; k < K; ++k) hf[d.o_invn + k] = 1.0 / P.norm_H[k];
+            std::copy(P.cH.begin(), P.cH.end(), hf.begin() + d.o_cH);
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(ia.upload(hi, st));
+        MMW_TRY(fa.upload(hf, st));
+        MMW_TRY(d_desc.alloc((size_t)B));
+        return MMW_OK;
+    }
+
+    // the reference's initial point (mmw.py:62-73): Y = 1/C, X = I, L = 0, sums zero
+    int reset(int32_t nit_) {
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (nit_ < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
+        MMW_HIP(hipSetDevice(device));
+        for (int b = 0; b < B; ++b) {
+            nit[b] = nit_;
+            MMW_TRY(reset_one(b));
+        }
+        return MMW_OK;
+    }
+    int reset_one(int b) {
+        iter[b] = 0;
+        const BatchDesc& d = desc[b];
+        std::vector<double> init((size_t)(d.o_info - d.o_lval), 0.0);  // the iterate (lval ... W2) in one copy
+        for (int k = 0; k < d.K; ++k) init[d.o_xval - d.o_lval + H[b].diag_pos[k]] = 1.0;
+        // the running sums start empty: iteration i adds X_i and Y_i when it starts, so after n iterations they hold X_0 + ... + X_{n-1}
+        for (int c = 0; c < d.C; ++c) init[d.o_Y - d.o_lval + c] = 1.0 / (double)d.C;
+        return copy_h2d(fa.p + d.o_lval, init.data(), init.size() * sizeof(double), st);
+    }
+
+    int iterate(int32_t n, const double* randv, const uint64_t* seeds) {
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (n < 1) return fail(MMW_ERR_ARG, "mmw_batch_iterate: n must be >= 1");
+        if (!randv && !seeds) return fail(MMW_ERR_ARG, "mmw_batch_iterate: give either the sketches or one seed per instance");
+        MMW_HIP(hipSetDevice(device));
+        std::vector<BatchDesc> dd = desc;
+        int64_t off = 0;
+        int runs = 0;
+        for (int b = 0; b < B; ++b) {
+            BatchDesc& d = dd[b];
+            d.nrun = active[b] ? std::min(n, nit[b] - iter[b]) : 0;
+            d.iter0 = iter[b];
+            d.eta = eta[b]; d.tol = tol; d.max_order = max_order;
+            d.seed = seeds ? seeds[b] : 0;
+            if (randv && d.nrun > 0) { d.o_randv = off; off += (int64_t)d.nrun * d.K * d.D; }
+            runs += d.nrun > 0;
+        }
+        if (!runs) return fail(MMW_ERR_STATE, "mmw_batch_iterate: every instance has run its announced iterations");
+        if (randv) MMW_TRY(rbuf.alloc((size_t)off));
+        if (randv) MMW_TRY(copy_h2d(rbuf.p, randv, (size_t)off * sizeof(double), st));
+        MMW_TRY(copy_h2d(d_desc.p, dd.data(), dd.size() * sizeof(BatchDesc), st));
+        hipLaunchKernelGGL(k_mmw_batch, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, randv ? rbuf.p : (const double*)nullptr);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b) iter[b] += dd[b].nrun;
+        return MMW_OK;
+    }
+
+    int set_slots(const int32_t* Z, int32_t nit_) {
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (nit_ < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
+        std::vector<HostPattern> keep = H;  // a refused slot count leaves the batch as it was
+        for (int b = 0; b < B; ++b) {
+            if (Z[b] <= 0) continue;
+            const std::string err = update_slots(H[b], Z[b]);
+            if (!err.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, "mmw_batch_set_slots: instance " + std::to_string(b) + ": " + err); }
+            const std::string lerr = check_limits(H[b], Z[b] * rank_radio);
+            if (!lerr.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, "mmw_batch_set_slots: instance " + std::to_string(b) + ": " + lerr + " (run it on a handle)"); }
+        }
+        MMW_TRY(layout());
+        for (int b = 0; b < B; ++b) {
+            active[b] = Z[b] > 0;
+            nit[b] = nit_;
+            MMW_TRY(reset_one(b));
+        }
+        return MMW_OK;
+    }
+
+    int check_inst(int b) const {
+        if (b < 0 || b >= B) return fail(MMW_ERR_ARG, "mmw_batch: instance index out of range");
+        return MMW_OK;
+    }
+    int read_dev(int64_t o, int64_t len, double* out, int64_t n) {
+        if (n != len) return fail(MMW_ERR_ARG, "mmw_batch_read_f64: wrong length " + std::to_string(n) + ", expected " + std::to_string(len));
+        MMW_HIP(hipSetDevice(device));
+        return copy_d2h(out, fa.p + o, (size_t)len * sizeof(double), st);
+    }
+    static int read_host(const std::vector<double>& v, double* out, int64_t n) {
+        if ((int64_t)v.size() != n) return fail(MMW_ERR_ARG, "mmw_batch_read_f64: wrong length");
+        if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(double));
+        return MMW_OK;
+    }
+    int read_f64(int b, int which, double* out, int64_t n) {
+        MMW_TRY(check_inst(b));
+        const HostPattern& P = H[b];
+        switch (which) {
+            case MMW_F_S_SUM: return read_host(P.S_sum, out, n);
+            case MMW_F_NORM_H: return read_host(P.norm_H, out, n);
+            case MMW_F_ST_DATA: return read_host(P.st_data, out, n);
+            default: break;
+        }
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        const BatchDesc& d = desc[b];
+        const int64_t KD = (int64_t)d.K * d.D;
+        switch (which) {
+            case MMW_F_Y: return read_dev(d.o_Y, d.C, out, n);
+            case MMW_F_E_ACCU: return read_dev(d.o_eaccu, d.C, out, n);
+            case MMW_F_E_THIS: return read_dev(d.o_ethis, d.C, out, n);
+            case MMW_F_LVAL: return read_dev(d.o_lval, d.nnzL, out, n);
+            case MMW_F_XVAL: return read_dev(d.o_xval, d.nnzL, out, n);
+            case MMW_F_XAVG: return read_dev(d.o_xavg, d.nnzL, out, n);
+            case MMW_F_YAVG: return read_dev(d.o_yavg, d.C, out, n);
+            case MMW_F_XHALF: return read_dev(d.o_Xh, KD, out, n);
+            case MMW_F_SKETCH:
+                if (iter[b] == 0) return fail(MMW_ERR_STATE, "mmw_batch_read_f64: no iteration has run on this instance");
+                return read_dev(d.o_R, KD, out, n);
+            case MMW_F_EXPM_INFO: return read_dev(d.o_info, 4, out, n);
+            default: return fail(MMW_ERR_ARG, "mmw_batch_read_f64: field not held by a batch");
+        }
+    }
+    static int read_i(const std::vector<int32_t>& v, int32_t* out, int64_t n) {
+        if ((int64_t)v.size() != n) return fail(MMW_ERR_ARG, "mmw_batch_read_i32: wrong length");
+        if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int32_t));
+        return MMW_OK;
+    }
+    int read_i32(int b, int which, int32_t* out, int64_t n) {
+        MMW_TRY(check_inst(b));
+        const HostPattern& P = H[b];
+        switch (which) {
+            case MMW_I_L_INDPTR: return read_i(P.l_indptr, out, n);
+            case MMW_I_L_INDICES: return read_i(P.l_indices, out, n);
+            case MMW_I_ST_INDPTR: return read_i(P.st_indptr, out, n);
+            case MMW_I_ST_INDICES: return read_i(P.st_indices, out, n);
+            case MMW_I_GAIN_X: return read_i(P.gain_x, out, n);
+            case MMW_I_GAIN_Y: return read_i(P.gain_y, out, n);
+            case MMW_I_ASSO_X: return read_i(P.asso_x, out, n);
+            case MMW_I_ASSO_Y: return read_i(P.asso_y, out, n);
+            case MMW_I_DIAG_POS: return read_i(P.diag_pos, out, n);
+            case MMW_I_ASSO_POS: return read_i(P.asso_pos, out, n);
+            default: return fail(MMW_ERR_ARG, "mmw_batch_read_i32: unknown field");
+        }
+    }
+    int sketch(int b, uint64_t seed, int32_t iteration, double* out, int64_t n) {
+        MMW_TRY(check_inst(b));
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (iteration < 0) return fail(MMW_ERR_ARG, "mmw_batch_sketch: iteration must be >= 0");
+        const BatchDesc& d = desc[b];
+        const int64_t KD = (int64_t)d.K * d.D;
+        if (n != KD) return fail(MMW_ERR_ARG, "mmw_batch_sketch: wrong length for a K x D block");
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(skbuf.alloc((size_t)KD));
+        hipLaunchKernelGGL(k_batch_sketch, dim3(1), dim3(BATCH_THREADS), 0, st, d.K, d.D, seed, (uint32_t)iteration, skbuf.p);
+        MMW_HIP(hipGetLastError());
+        return copy_d2h(out, skbuf.p, (size_t)KD * sizeof(double), st);
+    }
+};
+
+namespace {
+// mmw_batch_export: the instance's iterate into an fp64 handle of the same (state, Z), as if the handle had run those iterations.
+int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {
+    const BatchDesc& d = bt->desc[b];
+    const HostPattern& P = bt->H[b];
+    if (s->host_only || bt->host_only) return fail(MMW_ERR_STATE, "mmw_batch_export: host-only batch or handle");
+    if (s->device != bt->device) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle lives on another device");
+    if (s->K != d.K || s->Z != d.Z || s->D != d.D || s->H.nnzL() != (int64_t)d.nnzL || s->H.C() != (int64_t)d.C)
+        return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's K / Z / nnzL do not match the instance's");
+    if (s->H.l_indices != P.l_indices || s->H.l_indptr != P.l_indptr) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's pattern is not the instance's");
+    MMW_HIP(hipSetDevice(s->device));
+    MMW_TRY(s->settle());
+    MMW_HIP(hipStreamSynchronize(bt->st));
+    MMW_HIP(hipStreamSynchronize(s->st));
+    // the state a reset leaves (plans, lagged history, chains, timers), then the iterate on top
+    MMW_TRY(s->reset(std::max(1, bt->nit[b])));
+    const size_t nnz = (size_t)d.nnzL, C = (size_t)d.C;
+    const double* f = bt->fa.p;
+    MMW_HIP(hipMemcpyAsync(s->lval.p, f + d.o_lval, nnz * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->xval.p, f + d.o_xval, nnz * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->xavg.p, f + d.o_xavg, nnz * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->Y.p, f + d.o_Y, C * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->yavg.p, f + d.o_yavg, C * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->e_accu.p, f + d.o_eaccu, C * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    MMW_HIP(hipMemcpyAsync(s->e_this.p, f + d.o_ethis, C * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    // The batch adds X_i / Y_i to the running sums when iteration i starts; a handle adds them as soon as they are made while
+    // iterations remain (mmw_gap reads iter + 1 terms then).  Before the last iteration the handle's sums hold the current X / Y too.
+    if (bt->iter[b] < bt->nit[b]) {
+        const unsigned gx = (unsigned)std::min<size_t>((nnz + BLOCK - 1) / BLOCK, 4096), gy = (unsigned)std::min<size_t>((C + BLOCK - 1) / BLOCK, 4096);
+        hipLaunchKernelGGL((k_accumulate<double>), dim3(gx), dim3(BLOCK), 0, s->st, nnz, s->xval.p, s->xavg.p);
+        hipLaunchKernelGGL((k_accumulate<double>), dim3(gy), dim3(BLOCK), 0, s->st, C, s->Y.p, s->yavg.p);
+        MMW_HIP(hipGetLastError());
+    }
+    // derived copies: L in the LDS-staged SpMM's traversal order (when the handle's blocking is attached; a later attach gathers it
+    // from lval itself)
+    if (s->lval_blk.p && s->HB.nent > 0) {
+        hipLaunchKernelGGL((k_gather_blocked<double>), dim3(grid_elems((size_t)s->HB.nent)), dim3(BLOCK), 0, s->st, (size_t)s->HB.nent,
+                           s->b_bepos.p, s->lval.p, s->lval_blk.p);
+        MMW_HIP(hipGetLastError());
+    }
+    s->lblk_stale = false;
+    s->iter = bt->iter[b];
+    MMW_HIP(hipStreamSynchronize(s->st));
+    return MMW_OK;
+}
+}  // namespace
+
+namespace {
+// no C++ exception (std::bad_alloc from a host vector, ...) crosses the C boundary of the batch entries
+template <typename F> int batch_guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::exception& ex) {
+        return fail(MMW_ERR_ARG, std::string("mmw_batch: ") + ex.what());
+    } catch (...) {
+        return fail(MMW_ERR_ARG, "mmw_batch: unknown exception");
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, const int32_t* Z, int32_t rank_radio, double eta,
+                     const int32_t* nit, const int32_t* const* S_indptr, const int32_t* const* S_indices, const double* const* S_data,
+                     const int32_t* const* Q_indptr, const int32_t* const* Q_indices, const double* const* Q_data, const double* const* h_max) {
+    return batch_guarded([&]() -> int {
+        if (!out || !K || !Z || !nit || !S_indptr || !S_indices || !S_data || !Q_indptr || !Q_indices || !Q_data || !h_max)
+            return fail(MMW_ERR_ARG, "mmw_batch_create: null pointer");
+        *out = nullptr;
+        if (B < 1) return fail(MMW_ERR_ARG, "mmw_batch_create: B must be >= 1");
+        if (B > 65535) return fail(MMW_ERR_ARG, "mmw_batch_create: at most 65535 instances per batch");
+        if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
+        if (!(eta >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
+        auto bt = std::make_unique<mmw_batch>();
+        bt->device = device;
+        bt->host_only = device == -1;
+        bt->B = B;
+        bt->rank_radio = rank_radio;
+        bt->eta.assign(B, eta);
+        bt->H.resize(B);
+        bt->nit.assign(nit, nit + B);
+        bt->iter.assign(B, 0);
+        bt->active.assign(B, 1);
+        for (int b = 0; b < B; ++b) {
+            if (nit[b] < 1) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": nit must be >= 1");
+            if (!S_indptr[b] || !S_indices[b] || !S_data[b] || !Q_indptr[b] || !Q_indices[b] || !Q_data[b] || !h_max[b])
+                return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": null pointer");
+            if (K[b] > BATCH_MAX_K) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": K = " + std::to_string(K[b]) +
+                                                    " exceeds the batch limit " + std::to_string(BATCH_MAX_K) + " (run it on a handle)");
+            const std::string err = build_pattern(bt->H[b], K[b], Z[b], S_indptr[b], S_indices[b], S_data[b], Q_indptr[b], Q_indices[b],
+                                                  Q_data[b], h_max[b]);
+            if (!err.empty()) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": " + err);
+        }
+        if (!bt->host_only) {
+            int ndev = 0;
+            MMW_TRY(mmw_device_count(&ndev));
+            if (device < 0 || device >= ndev) return fail(MMW_ERR_HIP, "mmw_batch_create: no such HIP device " + std::to_string(device));
+            MMW_HIP(hipSetDevice(device));
+            MMW_HIP(hipStreamCreateWithFlags(&bt->st, hipStreamNonBlocking));
+        }
+        MMW_TRY(bt->layout());
+        if (!bt->host_only)
+            for (int b = 0; b < B; ++b) MMW_TRY(bt->reset_one(b));
+        *out = bt.release();
+        return MMW_OK;
+    });
+}
+int mmw_batch_destroy(mmw_batch* b) {
+    return batch_guarded([&]() -> int {
+        delete b;
+        return MMW_OK;
+    });
+}
+int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]) {
+    return batch_guarded([&]() -> int {
+        if (!b || !out) return fail(MMW_ERR_ARG, "null pointer");
+        MMW_TRY(b->check_inst(inst));
+        const HostPattern& P = b->H[inst];
+        const BatchDesc& d = b->desc[inst];
+        const int64_t v[10] = {P.K, P.Z, d.D, d.D, P.nnzL(), P.nnzST(), P.E_gain(), P.E_asso(), P.C(), b->iter[inst]};
+        for (int i = 0; i < 10; ++i) out[i] = v[i];
+        return MMW_OK;
+    });
+}
+int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit) {
+    return batch_guarded([&]() -> int {
+        if (!b || !Z) return fail(MMW_ERR_ARG, "null pointer");
+        return b->set_slots(Z, nit);
+    });
+}
+int mmw_batch_reset(mmw_batch* b, int32_t nit) {
+    return batch_guarded([&]() -> int {
+        if (!b) return fail(MMW_ERR_ARG, "null batch handle");
+        return b->reset(nit);
+    });
+}
+int mmw_batch_set_eta(mmw_batch* b, const double* eta) {
+    return batch_guarded([&]() -> int {
+        if (!b || !eta) return fail(MMW_ERR_ARG, "null pointer");
+        for (int i = 0; i < b->B; ++i)
+            if (!(eta[i] >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
+        b->eta.assign(eta, eta + b->B);
+        return MMW_OK;
+    });
+}
+int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) {
+    return batch_guarded([&]() -> int {
+        if (!b) return fail(MMW_ERR_ARG, "null batch handle");
+        if (max_order < 1 || max_order > MAX_ORDER) return fail(MMW_ERR_ARG, "max_order must be in [1, 16]");
+        if (!(tol > 0.0)) return fail(MMW_ERR_ARG, "tol must be positive");
+        b->max_order = max_order;
+        b->tol = tol;
+        return MMW_OK;
+    });
+}
+int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64_t* seeds) {
+    return batch_guarded([&]() -> int {
+        if (!b) return fail(MMW_ERR_ARG, "null batch handle");
+        return b->iterate(n, randv, seeds);
+    });
+}
+int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n) {
+    return batch_guarded([&]() -> int {
+        if (!b || (!out && n)) return fail(MMW_ERR_ARG, "null pointer");
+        return b->read_f64(inst, which, out, n);
+    });
+}
+int mmw_batch_read_i32(mmw_batch* b, int32_t inst, int which, int32_t* out, int64_t n) {
+    return batch_guarded([&]() -> int {
+        if (!b || (!out && n)) return fail(MMW_ERR_ARG, "null pointer");
+        return b->read_i32(inst, which, out, n);
+    });
+}
+int mmw_batch_sketch(mmw_batch* b, int32_t inst, uint64_t seed, int32_t iteration, double* out, int64_t n) {
+    return batch_guarded([&]() -> int {
+        if (!b || !out) return fail(MMW_ERR_ARG, "null pointer");
+        return b->sketch(inst, seed, iteration, out, n);
+    });
+}
+int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h) {
+    return batch_guarded([&]() -> int {
+        if (!b || !h) return fail(MMW_ERR_ARG, "null pointer");
+        MMW_TRY(b->check_inst(inst));
+        auto* s = dynamic_cast<Solver<double>*>(h);
+        if (!s) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle is not an fp64 handle");
+        return batch_export_into(b, inst, s);
+    });
+}
+
+}  // extern "C"
