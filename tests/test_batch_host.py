@@ -67,6 +67,40 @@ def test_oversize_instances_are_refused_with_a_message():
     assert b"mmw_batch_create" in L.mmw_last_error()
 
 
+BATCH_MAX_BYTES = 96 << 20  # kernels_batch.h
+
+
+def batch_instance_bytes(p, D):
+    """Arena bytes of one instance as mmw_batch::fp64_words / int_words count them (csrc/mmw_api.hip), from the oracle's pattern."""
+    K, nnz, C, EA = p.K, p.nnzL, p.C, p.E_asso
+    return (5 * nnz + 6 * K + 4 * C + 4 * K * D + 4 + 64) * 8 + (K + 1 + 3 * nnz + K + EA) * 4
+
+
+def test_arena_bytes_limit_refuses_just_over_and_accepts_just_under():
+    """K = 4 096 (the K limit) and D = 512 (the D limit): an ER density of 0.0187 puts the instance 6 152 bytes over 96 MiB, and the
+    same graph at Z = 255 (D = 510) 255 992 bytes under it.  The nnzL <= 2^22 limit cannot fire first at K <= 4 096: 2^22 pattern
+    entries alone take 52 bytes each in the arena (5 fp64 and 3 int32 words), 218 MB, far over 96 MiB, so every instance that reaches
+    it has already been refused by the byte count."""
+    from oracle import mmw_oracle as orc
+    from sig_sdp_mmw_amd.graphs import er_contention_graph
+    assert 52 * (1 << 22) > BATCH_MAX_BYTES
+    state = er_contention_graph(4096, 0.0187, 1)
+    p = orc.Pattern(256, state)
+    over, under = batch_instance_bytes(p, 512), batch_instance_bytes(p, 510)
+    # conditions on the inputs: just over at D = 512, just under at D = 510, both far below the nnzL limit
+    assert 0 < over - BATCH_MAX_BYTES < 1 << 20 and 0 < BATCH_MAX_BYTES - under < 1 << 20, (over, under)
+    assert p.nnzL < 1 << 22
+    with pytest.raises(_lib.MMWError, match="instance 0: instance needs %d bytes, over the batch limit %d" % (over, BATCH_MAX_BYTES)):
+        _lib.BatchSolver([256], [state], 5, 0.05, device=-1)
+    # a second instance that is fine does not hide the first's refusal, and the index names the one that is over
+    small = er_contention_graph(60, 0.1, 1)
+    with pytest.raises(_lib.MMWError, match="instance 1: instance needs %d bytes" % over):
+        _lib.BatchSolver([4, 256], [small, state], 5, 0.05, device=-1)
+    b = _lib.BatchSolver([255], [state], 5, 0.05, device=-1)
+    assert (b.sizes[0]["K"], b.sizes[0]["D"], b.sizes[0]["nnzL"], b.sizes[0]["C"]) == (4096, 510, p.nnzL, p.C)
+    b.close()
+
+
 def test_host_only_batch_refuses_set_slots_and_bad_expm_settings():
     gs, states = golden_batch()
     b = _lib.BatchSolver([int(g["Z"]) for g in gs], states, 3, 0.05, device=-1)
