@@ -316,6 +316,25 @@ int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol);
  * iteration-major within an instance (parity mode).
  */
 int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64_t* seeds);
+/*
+ * The duality gap inside the batch: the LOG_GAP branch mmw.py:79-117 as a phase of the instance's own workgroup, so a whole
+ * convergence sweep (every instance, every iteration, every gap row) stays ONE launch per mmw_batch_iterate.
+ *
+ * mmw_batch_set_gap: from the next mmw_batch_iterate on, every iteration i of every active instance logs one row when it starts,
+ * from the i + 1 terms X_0 .. X_i / Y_0 .. Y_i of the running sums (mmw.py:77-81): {e_max = the largest constraint violation at
+ * Xbar, K * theta with theta = lambda_min(L(Ybar)) by plain Lanczos, e_max - K * theta, steps} -- LOGGED_NP_DATA["gap"][:, 3:6] of
+ * the reference and the Lanczos steps taken.  The recurrence stops at |beta_m s_m| <= 1e-11 * scale (mmw_gap's fp64 criterion), on
+ * an invariant subspace, or at m = min(K, m_cap); `steps` is NEGATIVE when m_cap was reached without meeting the criterion (theta
+ * is then a Ritz value, an upper bound of lambda_min).  m_cap <= 0 takes the default 600, m_cap > 1024 is refused.  The phase only
+ * reads the iterate: with the gap on every other field is bitwise what it is with the gap off, and a row is bitwise independent of
+ * the batch neighbours and of how the iterations are split into calls.  The log and the phase's work space (nnzL + 5 K doubles
+ * per instance) live in a buffer of their own, allocated when the gap is first enabled.  Rows of iterations that ran while the gap
+ * was off are NaN; mmw_batch_reset / mmw_batch_set_slots clear the log and keep the setting.  MMW_ERR_STATE on a host-only batch.
+ * mmw_batch_read_gap: the rows of instance `inst`, 4 doubles per iteration done (n must be 4 x that count); MMW_ERR_STATE if the
+ * gap was never enabled.
+ */
+int mmw_batch_set_gap(mmw_batch* b, int enabled, int32_t m_cap);
+int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n);
 /* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
  * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);

@@ -27,7 +27,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds", "mmw_gm_create", "mmw_gm_destroy", "mmw_gm_sizes", "mmw_gm_pass",
            "mmw_gm_run", "mmw_gm_assign", "mmw_batch_create", "mmw_batch_destroy", "mmw_batch_sizes", "mmw_batch_set_slots",
            "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
-           "mmw_batch_sketch", "mmw_batch_export"]
+           "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap"]
 
 
 class MMWError(RuntimeError):
@@ -104,6 +104,8 @@ def lib():
     L.mmw_batch_read_i32.argtypes = [C.c_void_p, C.c_int32, C.c_int, p_i32, C.c_int64]
     L.mmw_batch_sketch.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
     L.mmw_batch_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.mmw_batch_set_gap.argtypes = [C.c_void_p, C.c_int, C.c_int32]
+    L.mmw_batch_read_gap.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_int64]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -502,6 +504,20 @@ class BatchSolver:
         out = np.empty(int(n), dtype=np.int32)
         check(lib().mmw_batch_read_i32(self._h, int(inst), int(which), _pi(out), int(n)))
         return out
+
+    def set_gap(self, on=True, m_cap=0):
+        """Log the duality gap (mmw.py:79-117) of every iteration that follows, inside the batch launch; m_cap <= 0: 600 steps."""
+        check(lib().mmw_batch_set_gap(self._h, 1 if on else 0, int(m_cap)))
+
+    def gap_log(self, inst):
+        """(rows[iterations, 3], steps[iterations]): per iteration done {e_max, K lambda_min, their difference} -- the columns 3:6 of
+        the reference's LOGGED_NP_DATA["gap"] -- and the Lanczos steps taken (negative: the cap was reached first).  Rows of
+        iterations that ran with the gap off are NaN (steps 0)."""
+        n = self.iterations_done(inst)
+        out = np.empty((n, 4), dtype=np.float64)
+        check(lib().mmw_batch_read_gap(self._h, int(inst), _pd(out), int(out.size)))
+        st = out[:, 3]
+        return out[:, :3].copy(), np.where(np.isnan(st), 0, st).astype(np.int64)
 
     def export(self, inst, solver):
         """The instance's iterate into `solver` (an fp64 `Solver` of the same state and Z), which then factors / rounds it."""

@@ -4,6 +4,8 @@ sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_searc
     ok_xhalf = run_with_state_many(it, Zs, states, nit=150, eta=0.04, seeds=seeds)   # [(True, X_half), ...]
     results  = search_many(states, nit=150, eta=0.04, seed=0)                          # [{"Z", "z_vec", "remainder", "probes"}, ...]
 
+    curves   = convergence_many(Zs, states, nit=625, eta=0.04)                         # [{"gap": [nit, 3], "lanczos_steps": [nit]}, ...]
+
 The iterations of every instance run in one launch per call; X_half comes from the tested per-handle epilogue: the instance's
 iterate is exported into an fp64 handle of the same state (mmw_batch_export) and `mmw_factor` / `mmw_round` run there.
 
@@ -85,6 +87,29 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
         return [(True, _factor(b, i, hs.get(i, int(Z)), int(Z), rank_radio, factor_seed)) for i, Z in enumerate(Zs)]
     finally:
         hs.close()
+        b.close()
+
+
+def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0):
+    """The reference's convergence sweeps (sim_convergence_rho.py, sim_all_mmw.py: LOG_GAP = True, one run per instance) as one
+    batch: `nit` and `eta` are one value for all or one per instance, the gap is logged inside the launch (mmw.py:79-117) and all
+    iterations of all instances run in ONE `iterate`.  Returns per instance {"gap": [nit, 3], "lanczos_steps": [nit]}; the three
+    columns are LOGGED_NP_DATA["gap"][:, 3:6] of the reference."""
+    B = len(states)
+    nits = [int(x) for x in np.broadcast_to(np.asarray(nit, dtype=np.int64), (B,))]
+    etas = np.broadcast_to(np.asarray(eta, dtype=np.float64), (B,))
+    seeds = np.arange(B, dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
+    b = _lib.BatchSolver(list(Zs), states, nits, float(etas[0]), rank_radio=rank_radio, device=device)
+    try:
+        b.set_eta(etas)
+        b.set_gap(True)
+        b.iterate(max(nits), None, seeds)
+        out = []
+        for i in range(B):
+            rows, steps = b.gap_log(i)
+            out.append({"gap": rows, "lanczos_steps": steps})
+        return out
+    finally:
         b.close()
 
 

@@ -15,6 +15,11 @@
 // row-sum bound of ||L/2 - mu I||_1, substeps doubled until the order fits max_order), planned in the workgroup every iteration,
 // with a per-column stop: column c stops adding terms once ||T_{j-1} e_c||_inf + ||T_j e_c||_inf <= tol ||F e_c||_inf.
 //
+// The duality gap (mmw.py:79-117, LOG_GAP) is a phase of the same workgroup: k_mmw_batch<true> logs one row per iteration (the
+// maximum violation at Xbar, K lambda_min(L(Ybar)) by Lanczos with the tridiagonal solved in the workgroup, their difference and the
+// Lanczos steps taken) into a work buffer of its own.  The phase reads the iterate and writes nothing of it; k_mmw_batch<false> is
+// the kernel without the phase.
+//
 // Limits (mmw_batch_create refuses larger instances; they stay on handles): K <= BATCH_MAX_K, D = Z * rank_radio <= BATCH_MAX_D
 // (the sketch's lane layout: 64 lanes x 4 groups x 2 columns), nnzL <= BATCH_MAX_NNZ, and BATCH_MAX_BYTES of arena per instance.
 #pragma once
@@ -89,8 +94,250 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_sketch(int K, int D, ui
     batch_sketch_rows(K, D, seed, iter, R);
 }
 
+// ---- the duality gap of one iteration (mmw.py:79-117), a phase of the instance's workgroup ----------------------------------------
+constexpr int GAP_MAX_M = 1024;     // Lanczos steps per row at most: the tridiagonal and its solve live in LDS
+constexpr int GAP_DEFAULT_M = 600;  // the handles' cap (solver_extras.h lambda_min)
+
+struct GapDesc {
+    int m_cap, pad0;
+    int64_t o_work;  // gap buffer: L(Ybar) on the pattern [nnzL], row sums [K], H weights [K], three Lanczos vectors [3K]
+    int64_t o_log;   // gap buffer: 4 doubles per iteration {e_max, K theta, e_max - K theta, steps}
+};
+
+// Row `gi` of the instance's gap log, from n = gi + 1 terms: xbar = (xavg + xval) / n and ybar = (yavg + Y) / n are the averages the
+// iteration forms right after (the same sums, bitwise).  e_max by the DUAL formulas, L(Ybar) by the LOSS formulas with coefficient
+// +1, lambda_min by plain Lanczos (no reorthogonalisation: the extreme Ritz value converges regardless) on a Philox start vector
+// keyed by the instance's sizes.  One row takes 8 lanes in the SpMV (cross-lane sum in a fixed order); alpha and beta are fixed-order
+// block sums.  theta_min(T_m) and the last component of its eigenvector are solved in the workgroup at m = 10, 20, ... with the
+// interval growing by a quarter: theta by multisection of the Sturm count (every thread one shift per round, the bracket's upper
+// end carried over from the last check: theta_min(T_m) does not increase with m), the eigenvector by three inverse iterations of
+// one lane on a factorisation kept in LDS (reciprocal pivots and multipliers: one fma per element and pass).  Stop: |beta_m s_m| <= 1e-11 scale (the handles' criterion and scale; beta_m <= 1e-11
+// scale, an invariant subspace, meets it at once), or m = min(K, m_cap): steps is negative when the cap cut a Krylov space short.
+__device__ __forceinline__ void batch_gap_row(const BatchDesc& d, const GapDesc& g, const int* __restrict__ ia, const double* fa,
+                                              double* __restrict__ ga, int gi, double* sh) {
+    __shared__ double t_a[GAP_MAX_M], t_b[GAP_MAX_M], t_c[GAP_MAX_M], t_d[GAP_MAX_M], t_s[GAP_MAX_M];
+    __shared__ double t_last;
+    const int tid = (int)threadIdx.x, NT = (int)blockDim.x;
+    const int K = d.K, Z = d.Z, C = d.C, nnz = d.nnzL, EA = d.E_asso, baseH = K + EA;
+    const int* __restrict__ indptr = ia + d.o_indptr;
+    const int* __restrict__ col = ia + d.o_col;
+    const int* __restrict__ lrow = ia + d.o_lrow;
+    const int* __restrict__ pid = ia + d.o_pid;
+    const int* __restrict__ diag = ia + d.o_diag;
+    const int* __restrict__ apos = ia + d.o_apos;
+    const double* sab = fa + d.o_sab;
+    const double* sba = sab + nnz;
+    const double* hmax = fa + d.o_hmax;
+    const double* ssum = fa + d.o_ssum;
+    const double* invn = fa + d.o_invn;
+    const double* cH = fa + d.o_cH;
+    const double* xval = fa + d.o_xval;
+    const double* xavg = fa + d.o_xavg;
+    const double* Y = fa + d.o_Y;
+    const double* yavg = fa + d.o_yavg;
+    double* gl = ga + g.o_work;
+    double* wrs = gl + nnz;
+    double* wwH = wrs + K;
+    double* vp = wwH + K;
+    double* vc = vp + K;
+    double* vw = vc + K;
+    const double nterm = (double)(gi + 1);
+    const double invK = 1.0 / (double)K, Zm1 = (double)(Z - 1);
+    const double denF = 1.0 / ((double)K * Zm1) + 0.5;
+    // ---- e_max = max e(Xbar) (mmw.py:81-96, the DUAL formulas of the loop body)
+    double best = -1e300;
+    for (int k = tid; k < K; k += NT) {
+        const int dp = diag[k];
+        double s = 0.0;
+        for (int e = indptr[k]; e < indptr[k + 1]; ++e)
+            if (e != dp) s += (xavg[e] + xval[e]) / nterm;
+        wrs[k] = s;
+        const double eD = ((xavg[dp] + xval[dp]) / nterm - 1.0) * (1.0 / (1.0 - invK));
+        best = eD > best ? eD : best;
+    }
+    for (int p = tid; p < EA; p += NT) {
+        const double eF = ((xavg[apos[p]] + xval[apos[p]]) / nterm + 1.0 / Zm1) / denF;
+        best = eF > best ? eF : best;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += NT) {
+        double s = 0.0;
+        for (int e = indptr[k]; e < indptr[k + 1]; ++e) {
+            const double w = sab[e];
+            if (w != 0.0) s += w * wrs[col[e]];
+        }
+        const double eH = (s * Zm1 / (double)Z - (hmax[k] - (1.0 / (double)Z) * ssum[k])) * invn[k];
+        best = eH > best ? eH : best;
+    }
+    const double emax = block_max(best, sh);
+    // ---- L(Ybar) on the pattern (mmw.py:98-115, the LOSS formulas with coefficient +1)
+    double sD = 0.0, sF = 0.0, sW = 0.0;
+    for (int c = tid; c < C; c += NT) {
+        const double y = (yavg[c] + Y[c]) / nterm;
+        if (c < K) sD += y;
+        else if (c < baseH) sF += y;
+        else {
+            const double w = y * invn[c - baseH];
+            wwH[c - baseH] = w;
+            sW += cH[c - baseH] * w;
+        }
+    }
+    sD = block_sum(sD, sh);
+    sF = block_sum(sF, sh);
+    sW = block_sum(sW, sh);  // (its barriers publish wwH)
+    const double dconst = -(sD * invK) / (1.0 - invK) + (sF / ((double)K * Zm1)) / denF - sW;
+    const double gscale = Zm1 / (double)(2 * Z);
+    for (int e = tid; e < nnz; e += NT) {
+        const int r = lrow[e], c = col[e], q = pid[e];
+        double v;
+        if (c == r) v = ((yavg[r] + Y[r]) / nterm) / (1.0 - invK) + dconst;
+        else if (q >= 0) v = (((yavg[K + q] + Y[K + q]) / nterm) * 0.5) / denF;
+        else v = (sab[e] * wwH[c] + sba[e] * wwH[r]) * gscale;
+        gl[e] = v;
+    }
+    // ---- lambda_min(L(Ybar)): 8 lanes per row, lane 0 of a group owns the row's vector entries
+    const int g8 = tid >> 3, l8 = tid & 7, NG8 = NT >> 3;
+    double ss = 0.0;
+    if (l8 == 0)
+        for (int r = g8; r < K; r += NG8) {
+            uint32_t w[4];
+            philox4x32_10((uint32_t)r, 0u, 0u, 0x4c5a4750u, (uint32_t)K, (uint32_t)nnz, w);
+            double n0, n1;
+            box_muller(w, n0, n1);
+            vc[r] = n0;
+            ss += n0 * n0;
+        }
+    ss = block_sum(ss, sh);
+    const double inrm = 1.0 / sqrt(ss);
+    if (l8 == 0)
+        for (int r = g8; r < K; r += NG8) vc[r] *= inrm;
+    __syncthreads();  // gl and the start vector
+    const int mmax = K < g.m_cap ? K : g.m_cap;
+    double beta_prev = 0.0, theta = 0.0, hprev = 1e300;
+    double lo_full = 1e300, hi_full = -1e300, sc_full = 0.0, amin = 1e300;
+    int steps = 0, next = mmax < 10 ? mmax : 10;
+    for (int j = 1; j <= mmax; ++j) {
+        double al = 0.0;
+        for (int r = g8; r < K; r += NG8) {
+            double acc = 0.0;
+            for (int e = indptr[r] + l8; e < indptr[r + 1]; e += 8) acc += gl[e] * vc[col[e]];
+            acc = group_sum(acc, 8);
+            if (l8 == 0) {
+                vw[r] = acc;
+                al += vc[r] * acc;
+            }
+        }
+        al = block_sum(al, sh);
+        double bb = 0.0;
+        if (l8 == 0)
+            for (int r = g8; r < K; r += NG8) {
+                double t = vw[r] - al * vc[r];
+                if (j > 1) t -= beta_prev * vp[r];
+                vw[r] = t;
+                bb += t * t;
+            }
+        bb = block_sum(bb, sh);
+        const double be = sqrt(bb);
+        if (tid == 0) { t_a[j - 1] = al; t_b[j - 1] = be; }
+        // Gershgorin bounds and the scale of T_j (its last row has beta_{j-1} only)
+        const double lo = fmin(lo_full, al - beta_prev), hi = fmax(hi_full, al + beta_prev);
+        const double scale = fmax(fmax(sc_full, fabs(al)), 1e-300);
+        amin = fmin(amin, al);
+        lo_full = fmin(lo_full, al - beta_prev - be);
+        hi_full = fmax(hi_full, al + beta_prev + be);
+        sc_full = fmax(sc_full, fabs(al) + be);
+        if (be <= 1e-11 * scale || j == next || j == mmax) {
+            __syncthreads();  // t_a, t_b
+            // theta_min(T_j) in [lo, min(min_i alpha_i, the last check's upper end)]
+            double l = lo, h = fmin(amin, hprev);
+            for (int rd = 0; rd < 16 && h - l > 4e-16 * fmax(fabs(l), fabs(h)); ++rd) {
+                const double w = h - l;
+                const double x = l + w * ((double)(tid + 1) / (double)(NT + 1));
+                double q = t_a[0] - x;
+                bool below = q < 0.0;  // an eigenvalue of T_j below x (Sturm sequence)
+                for (int i = 1; i < j && !below; ++i) {
+                    const double den = fabs(q) < 1e-300 ? (q < 0.0 ? -1e-300 : 1e-300) : q;
+                    q = t_a[i] - x - t_b[i - 1] * t_b[i - 1] / den;
+                    below = q < 0.0;
+                }
+                const int fi = (int)(-block_max(below ? -(double)tid : -(double)NT, sh));  // the first such shift
+                const double nl = fi > 0 ? l + w * ((double)fi / (double)(NT + 1)) : l;
+                if (fi < NT) h = l + w * ((double)(fi + 1) / (double)(NT + 1));
+                l = nl;
+            }
+            theta = 0.5 * (l + h);
+            hprev = h;
+            if (tid == 0) {  // inverse iteration on (T_j - (theta - shift) I), positive definite
+                const double shf = theta - 1e-10 * fmax(1.0, fabs(hi - lo));
+                // pivots once (the shift is the same for the three solves): t_d = 1 / pivot, t_c = beta / pivot
+                double piv = t_a[0] - shf;
+                if (fabs(piv) < 1e-300) piv = 1e-300;
+                double pinv = 1.0 / piv;
+                t_d[0] = pinv;
+#pragma unroll 4
+                for (int i = 1; i < j; ++i) {
+                    const double bi = t_b[i - 1], c = bi * pinv;
+                    t_c[i - 1] = c;
+                    piv = t_a[i] - shf - bi * c;
+                    if (fabs(piv) < 1e-300) piv = 1e-300;
+                    pinv = 1.0 / piv;
+                    t_d[i] = pinv;
+                }
+                // three solves from s = 1, unnormalised in between (growth <= 1e10 per solve); each pass is one fma per element
+                for (int i = 0; i < j; ++i) t_s[i] = 1.0;
+                double nn = 0.0, sn = 0.0;
+                for (int rep = 0; rep < 3; ++rep) {
+                    double sp = t_s[0];
+#pragma unroll 8
+                    for (int i = 1; i < j; ++i) {
+                        sp = t_s[i] - t_c[i - 1] * sp;
+                        t_s[i] = sp;
+                    }
+                    sn = sp * t_d[j - 1];
+                    t_s[j - 1] = sn;
+                    nn = sn * sn;
+#pragma unroll 8
+                    for (int i = j - 2; i >= 0; --i) {
+                        sn = t_s[i] * t_d[i] - t_c[i] * sn;
+                        t_s[i] = sn;
+                        nn += sn * sn;
+                    }
+                }
+                t_last = t_s[j - 1] / sqrt(nn);
+            }
+            __syncthreads();
+            const bool conv = fabs(be * t_last) <= 1e-11 * scale;
+            if (conv || j == mmax) {
+                steps = conv || j >= K ? j : -j;
+                break;
+            }
+            next = j + (j / 4 > 10 ? j / 4 : 10);
+            next = next < mmax ? next : mmax;
+        }
+        const double ib = 1.0 / be;
+        if (l8 == 0)
+            for (int r = g8; r < K; r += NG8) vw[r] *= ib;
+        double* const t = vp;
+        vp = vc;
+        vc = vw;
+        vw = t;
+        beta_prev = be;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double* row = ga + g.o_log + (size_t)4 * gi;
+        const double kt = (double)K * theta;
+        row[0] = emax;
+        row[1] = kt;
+        row[2] = emax - kt;
+        row[3] = (double)steps;
+    }
+}
+
+template <bool GAP>
 __global__ __launch_bounds__(BATCH_THREADS) void k_mmw_batch(const BatchDesc* __restrict__ descs, const int* __restrict__ ia,
-                                                             double* __restrict__ fa, const double* __restrict__ randv) {
+                                                             double* __restrict__ fa, const double* __restrict__ randv,
+                                                             const GapDesc* __restrict__ gdescs, double* __restrict__ ga) {
     const BatchDesc d = descs[blockIdx.x];
     if (d.nrun <= 0) return;
     __shared__ double sh[BATCH_WAVES];
@@ -129,8 +376,14 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_mmw_batch(const BatchDesc* __
     const int NG = NT / D, tc = tid % D, tg = tid / D;
     const bool tlive = tg < NG;
     const size_t KD = (size_t)K * D;
+    GapDesc g{};
+    if constexpr (GAP) g = gdescs[blockIdx.x];
 
     for (int it = 0; it < d.nrun; ++it) {
+        if constexpr (GAP) {
+            // ---- LOG_GAP (mmw.py:79-117) on the sums this iteration is about to form; reads the iterate only
+            batch_gap_row(d, g, ia, fa, ga, d.iter0 + it, sh);
+        }
         // ---- averaging (mmw.py:77-78) and DUAL step 1: off-diagonal row sums of X, eD, eF (mmw.py:124-131)
         for (int e = tid; e < nnz; e += NT) xavg[e] += xval[e];
         for (int c = tid; c < C; c += NT) yavg[c] += Y[c];

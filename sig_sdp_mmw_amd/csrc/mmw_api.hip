@@ -2251,6 +2251,8 @@ int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pre
 // Batched solver: many small fp64 instances, one workgroup each (csrc/kernels_batch.h).  Every instance's pattern is built by the
 // host code mmw_create uses (build_pattern / update_slots), then all of them are packed into one int32 and one fp64 arena.
 // ------------------------------------------------------------------------------------------------------------------------------
+#include <limits>
+
 #include "kernels_batch.h"
 
 struct mmw_batch {
@@ -2267,6 +2269,12 @@ struct mmw_batch {
     DevBuf<int> ia;
     DevBuf<double> fa, rbuf, skbuf;
     DevBuf<BatchDesc> d_desc;
+    // the duality-gap log (mmw_batch_set_gap): a buffer of its own, made when the gap is first enabled, so the arenas do not move
+    bool gap_ever = false, gap_on = false;
+    int gap_mcap = GAP_DEFAULT_M;
+    std::vector<GapDesc> gdesc;
+    DevBuf<double> ga;
+    DevBuf<GapDesc> d_gdesc;
 
     ~mmw_batch() {
         if (host_only || !st) return;
@@ -2359,6 +2367,43 @@ struct mmw_batch {
         return MMW_OK;
     }
 
+    // offsets of every instance's gap work space (nnzL + 5 K doubles, all instances first) and log (4 doubles per announced
+    // iteration, all logs after the work spaces); every log row NaN
+    int gap_layout() {
+        gdesc.assign(B, GapDesc{});
+        int64_t og = 0;
+        auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };
+        for (int b = 0; b < B; ++b) { gdesc[b].o_work = og; og = a32(og + (int64_t)desc[b].nnzL + 5 * (int64_t)desc[b].K); }
+        const int64_t log0 = og;
+        for (int b = 0; b < B; ++b) { gdesc[b].o_log = og; og = a32(og + 4 * (int64_t)nit[b]); }
+        const std::vector<double> init((size_t)(og - log0), std::numeric_limits<double>::quiet_NaN());
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(ga.alloc((size_t)og));
+        MMW_TRY(copy_h2d(ga.p + log0, init.data(), init.size() * sizeof(double), st));
+        MMW_TRY(d_gdesc.alloc((size_t)B));
+        return MMW_OK;
+    }
+    int set_gap(int enabled, int32_t m_cap) {
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (m_cap > GAP_MAX_M) return fail(MMW_ERR_ARG, "mmw_batch_set_gap: m_cap must be at most " + std::to_string(GAP_MAX_M));
+        if (enabled && !gap_ever) {
+            MMW_TRY(gap_layout());
+            gap_ever = true;
+        }
+        gap_on = enabled != 0;
+        gap_mcap = m_cap <= 0 ? GAP_DEFAULT_M : m_cap;
+        return MMW_OK;
+    }
+    int read_gap(int b, double* out, int64_t n) {
+        MMW_TRY(check_inst(b));
+        if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
+        if (!gap_ever) return fail(MMW_ERR_STATE, "mmw_batch_read_gap: the gap was never enabled on this batch (mmw_batch_set_gap)");
+        if (n != 4 * (int64_t)iter[b]) return fail(MMW_ERR_ARG, "mmw_batch_read_gap: wrong length " + std::to_string(n) + ", expected 4 x " + std::to_string(iter[b]) + " iterations done");
+        if (n == 0) return MMW_OK;
+        MMW_HIP(hipSetDevice(device));
+        return copy_d2h(out, ga.p + gdesc[b].o_log, (size_t)n * sizeof(double), st);
+    }
+
     // the reference's initial point (mmw.py:62-73): Y = 1/C, X = I, L = 0, sums zero
     int reset(int32_t nit_) {
         if (host_only) return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)");
@@ -2368,6 +2413,7 @@ struct mmw_batch {
             nit[b] = nit_;
             MMW_TRY(reset_one(b));
         }
+        if (gap_ever) MMW_TRY(gap_layout());  // an empty log for the new run
         return MMW_OK;
     }
     int reset_one(int b) {
@@ -2401,7 +2447,14 @@ struct mmw_batch {
         if (randv) MMW_TRY(rbuf.alloc((size_t)off));
         if (randv) MMW_TRY(copy_h2d(rbuf.p, randv, (size_t)off * sizeof(double), st));
         MMW_TRY(copy_h2d(d_desc.p, dd.data(), dd.size() * sizeof(BatchDesc), st));
-        hipLaunchKernelGGL(k_mmw_batch, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, randv ? rbuf.p : (const double*)nullptr);
+        const double* rv = randv ? rbuf.p : (const double*)nullptr;
+        if (gap_on) {
+            for (int b = 0; b < B; ++b) gdesc[b].m_cap = gap_mcap;
+            MMW_TRY(copy_h2d(d_gdesc.p, gdesc.data(), gdesc.size() * sizeof(GapDesc), st));
+            hipLaunchKernelGGL(k_mmw_batch<true>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, rv, d_gdesc.p, ga.p);
+        } else {
+            hipLaunchKernelGGL(k_mmw_batch<false>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, rv, (const GapDesc*)nullptr, (double*)nullptr);
+        }
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(st));
         for (int b = 0; b < B; ++b) iter[b] += dd[b].nrun;
@@ -2425,6 +2478,7 @@ struct mmw_batch {
             nit[b] = nit_;
             MMW_TRY(reset_one(b));
         }
+        if (gap_ever) MMW_TRY(gap_layout());
         return MMW_OK;
     }
 
@@ -2660,6 +2714,18 @@ int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) {
         b->max_order = max_order;
         b->tol = tol;
         return MMW_OK;
+    });
+}
+int mmw_batch_set_gap(mmw_batch* b, int enabled, int32_t m_cap) {
+    return batch_guarded([&]() -> int {
+        if (!b) return fail(MMW_ERR_ARG, "null batch handle");
+        return b->set_gap(enabled, m_cap);
+    });
+}
+int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n) {
+    return batch_guarded([&]() -> int {
+        if (!b || (!out && n)) return fail(MMW_ERR_ARG, "null pointer");
+        return b->read_gap(inst, out, n);
     });
 }
 int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64_t* seeds) {
