@@ -181,8 +181,8 @@ inline void build_blocking(HostBlocking& B, int K, const std::vector<int32_t>& i
     // union that brings the fewest new columns (ties: lowest RCM rank).  On a geometric graph this makes compact
     // two-dimensional patches instead of slices of the one-dimensional RCM order: ~25 % smaller unions for the same rows,
     // i.e. fewer bytes gathered into LDS per nonzero (the gathers run at the CU's L2 rate).
-    // MMW_BLK_GROW=0 keeps consecutive RCM rows.
-    const bool grow = B.grow && !(getenv("MMW_BLK_GROW") && atoi(getenv("MMW_BLK_GROW")) == 0);
+    // (B.grow == false, a handle made from the generator: consecutive rows of the order it brings.)
+    const bool grow = B.grow;
     B.order.assign(K, -1);  // filled block by block: position -> original row
     std::vector<char> assigned(K, 0);
     std::vector<int32_t> in_union(K, 0), in_stamp(K, -1);  // neighbours of v inside the current union (valid for stamp == blk)
@@ -192,15 +192,13 @@ inline void build_blocking(HostBlocking& B, int K, const std::vector<int32_t>& i
     B.un_cols.clear();
     std::vector<int32_t> stamp(K, -1), loc(K, 0), cur;
     int blk = 0, p = 0;
-    const int row_cap = getenv("MMW_BLK_ROWS") ? atoi(getenv("MMW_BLK_ROWS")) : BLK_ROWS;
-    const int row_quant = getenv("MMW_BLK_QUANT") ? atoi(getenv("MMW_BLK_QUANT")) : 1;
     while (p < K) {
         cur.clear();
         int rows = 0, entries = 0;
         const int p_start = p;
         while (assigned[rcm[seed_pos]]) ++seed_pos;
         int r = rcm[seed_pos];
-        while (p < K && rows < row_cap) {
+        while (p < K && rows < BLK_ROWS) {
             int fresh = 0;
             for (int e = indptr[r]; e < indptr[r + 1]; ++e)
                 if (stamp[indices[e]] != blk) ++fresh;
@@ -242,22 +240,6 @@ inline void build_blocking(HostBlocking& B, int K, const std::vector<int32_t>& i
             }
             if (best < 0) break;  // the union holds no unassigned row (a finished component): next block, next seed
             r = best;
-        }
-        if (row_quant > 1 && rows > row_quant && rows % row_quant && p < K) {  // trim to a multiple of the wave count
-            const int keep = rows / row_quant * row_quant;
-            for (int q = p_start + keep; q < p; ++q) assigned[B.order[q]] = 0;
-            p = p_start + keep;
-            seed_pos = 0;
-            cur.clear();
-            ++blk;  // fresh stamp generation for the rebuilt union
-            for (int q = p_start; q < p; ++q) {
-                const int r = B.order[q];
-                for (int e = indptr[r]; e < indptr[r + 1]; ++e)
-                    if (stamp[indices[e]] != blk) {
-                        stamp[indices[e]] = blk;
-                        cur.push_back(indices[e]);
-                    }
-            }
         }
         std::sort(cur.begin(), cur.end(), [&](int a, int b) { return rank[a] < rank[b]; });
         // exact staged entry count under the parity arrangement; shed rows until both kernels' budgets hold
@@ -475,7 +457,8 @@ inline void build_sd_tables(HostBlocking& B, int K, const std::vector<int32_t>& 
 // Row blocks for the matrix-core SpMM (kernels_mfma.h): grown like the blocks above (seed = next unassigned row of the RCM
 // order, then always the unassigned union member that brings the fewest new columns), bounded only by the union size and
 // `max_rows` (32 or 64).  Fills m_order / m_rowptr / m_desc {q0, rows, 0, 0, 0, union size, 0, 0} / m_unfixed, kbase and fpos.
-inline void build_mfma_blocking(HostBlocking& B, int K, const std::vector<int32_t>& indptr, const std::vector<int32_t>& indices, int max_rows) {
+inline void build_mfma_blocking(HostBlocking& B, int K, const std::vector<int32_t>& indptr, const std::vector<int32_t>& indices, int max_rows,
+                                int union_cap_want /* Switches::mf_union_cap; 0: MF_UNION */) {
     const int64_t nnz = indptr[K];
     B.fits_mfma = false;
     if (B.rcm_cache.size() != (size_t)K) return;
@@ -484,8 +467,7 @@ inline void build_mfma_blocking(HostBlocking& B, int K, const std::vector<int32_
     const std::vector<int32_t>& rcm = B.rcm_cache;
     std::vector<int32_t> rank(K);
     for (int p = 0; p < K; ++p) rank[rcm[p]] = p;
-    static const int cap_env = getenv("MMW_MF_UNION_CAP") ? atoi(getenv("MMW_MF_UNION_CAP")) : 0;
-    const int union_cap = cap_env > 0 ? std::min(cap_env, MF_UNION) : MF_UNION;
+    const int union_cap = union_cap_want > 0 ? std::min(union_cap_want, MF_UNION) : MF_UNION;
     B.m_order.assign(K, -1);
     B.m_rowptr.assign(1, 0);
     std::vector<int32_t> un_ptr(1, 0), un_cols;

@@ -38,10 +38,9 @@ inline int make_layout(int D, int vec, BlockLayout& lay, std::string& err) {
 
 // The generic SpMM's small-K form (k_spmm_slice): bytes of a staged row slice (0: not applicable) and the row ranges of its grid --
 // the partial slabs a Lanczos launch really fills
-template <typename T> inline int slice_bytes(int K, const BlockLayout& lay) {
-    static const bool off = getenv("MMW_NO_SLICE_SPMM") != nullptr;
+template <typename T> inline int slice_bytes(const Switches& sw, int K, const BlockLayout& lay) {
     const int row_bytes = lay.Dpad * (int)sizeof(T);
-    if (off || K < 256) return 0;
+    if (sw.no_slice_spmm || K < 256) return 0;
     if ((size_t)K * 64 <= (size_t)SLICE_LDS_MAX && row_bytes % 64 == 0) return 64;
     if ((size_t)K * 32 <= (size_t)SLICE_LDS_MAX && row_bytes % 32 == 0) return 32;
     return 0;
@@ -52,16 +51,16 @@ template <typename T> inline int slice_ranges(int K, const BlockLayout& lay, int
     return std::max(1, std::min((K + 15) / 16, device_cus() / std::max(1, nslices)));
 }
 // slabs of partial sums a Lanczos launch of the generic path fills (the rest of the caller's `nblk` slabs it clears)
-template <typename T> inline int generic_slabs(int K, const BlockLayout& lay, int nblk) {
-    const int sb = slice_bytes<T>(K, lay);
+template <typename T> inline int generic_slabs(const Switches& sw, int K, const BlockLayout& lay, int nblk) {
+    const int sb = slice_bytes<T>(sw, K, lay);
     return sb ? std::min(nblk, slice_ranges<T>(K, lay, sb)) : nblk;
 }
 // one launch of the CSR SpMM (any fused epilogue) for a block with layout `lay`
 template <typename T, int MODE>
-inline int spmm_launch(hipStream_t st, int K, const BlockLayout& lay, int nblk, const int* indptr, const int* col, const T* val,
+inline int spmm_launch(hipStream_t st, const Switches& sw, int K, const BlockLayout& lay, int nblk, const int* indptr, const int* col, const T* val,
                        const T* in, T* out, T* F, const T* X2, double c1, double c2, double c3, double* partial,
                        const ExpmPlan* plan = nullptr, int step = 0, double* partial_o2 = nullptr, int nslabs_fold = -1) {
-    if (const int sb = slice_bytes<T>(K, lay)) {  // small K without locality: the block's column slices staged in LDS (k_spmm_slice)
+    if (const int sb = slice_bytes<T>(sw, K, lay)) {  // small K without locality: the block's column slices staged in LDS (k_spmm_slice)
         const int nslices = lay.Dpad * (int)sizeof(T) / sb;
         int nranges = slice_ranges<T>(K, lay, sb);
         if (MODE == SPMM_LANCZOS) nranges = std::min(nranges, nblk);
@@ -95,28 +94,14 @@ inline int spmm_launch(hipStream_t st, int K, const BlockLayout& lay, int nblk, 
 // nb * ntiles / (2.5 * slots) tiles.  Short workgroups re-stage the block's entries once per tile group (fabric traffic
 // 79 MB vs 41 MB algorithmic at the bench config, all of it Infinity-Cache hits) but two co-resident workgroups in
 // different phases interleave better than two long ones in lockstep: whole blocks first and only the last partial
-// round cut into pieces (MMW_SCHED=2) moves 40 % fewer bytes and measures 5 % slower.
+// round cut into pieces moved 40 % fewer bytes and measured 5 % slower (that two-phase schedule was removed; the kernel's
+// whole-block phase stays empty: nfull = grid1 = 0).
 inline Blk2Sched blk2_schedule(int nb, int ntiles) {
     const int slots = 2 * device_cus();
     Blk2Sched s;
-    static const bool two_phase = getenv("MMW_SCHED") && atoi(getenv("MMW_SCHED")) == 2;
-    if (!two_phase) {
-        int tpw = (int)((double)nb * ntiles / (2.5 * slots) + 0.5);  // 2.5-4 rounds measure the same; fewer groups re-stage less
-        if (const char* e = getenv("MMW_TPW")) tpw = atoi(e);
-        tpw = tpw < 1 ? 1 : (tpw > ntiles ? ntiles : tpw);
-        s.nfull = 0; s.grid1 = 0; s.tpw_tail = tpw; s.groups_tail = (ntiles + tpw - 1) / tpw;
-        return s;
-    }
-    s.nfull = nb / slots * slots;
-    s.grid1 = (s.nfull + 7) / 8 * 8;
-    const int rem = nb - s.nfull;
-    s.tpw_tail = ntiles; s.groups_tail = 1;
-    double best = 1e300;
-    for (int g = 1; g <= ntiles && rem > 0; ++g) {  // rounds x (prologue + tiles), in units of one tile's time
-        const int tpw = (ntiles + g - 1) / g, groups = (ntiles + tpw - 1) / tpw;
-        const double cost = (double)((rem * groups + slots - 1) / slots) * (1.2 + tpw);
-        if (cost < best - 1e-9) { best = cost; s.tpw_tail = tpw; s.groups_tail = groups; }
-    }
+    int tpw = (int)((double)nb * ntiles / (2.5 * slots) + 0.5);  // 2.5-4 rounds measure the same; fewer groups re-stage less
+    tpw = tpw < 1 ? 1 : (tpw > ntiles ? ntiles : tpw);
+    s.nfull = 0; s.grid1 = 0; s.tpw_tail = tpw; s.groups_tail = (ntiles + tpw - 1) / tpw;
     return s;
 }
 
@@ -140,7 +125,6 @@ inline int spmm_blk_launch(hipStream_t st, const BlkDev& B, int Dpad, const T* v
     constexpr int CT = BLK_TILE_BYTES / (int)sizeof(T);
     const int ntiles = (Dpad + CT - 1) / CT;
     int tpw = (int)((double)B.nb * ntiles / (3.0 * 256.0) + 0.5);  // ~3 workgroups per CU over the launch
-    if (getenv("MMW_TPW")) tpw = atoi(getenv("MMW_TPW"));
     tpw = tpw < 1 ? 1 : (tpw > ntiles ? ntiles : tpw);
     const int total = B.nb * ((ntiles + tpw - 1) / tpw);
     const int per = (total + 7) / 8;
@@ -156,7 +140,7 @@ inline unsigned long long* g_mf_stamps = nullptr;  // diagnostic runs only: per-
 // and a group of GT column tiles; the group is as wide as still gives the chip ~1.5 workgroups per CU (narrower groups re-read
 // the block's A fragments once per group).
 template <int MODE>
-inline int spmm_mfma_launch(hipStream_t st, const MfmaDev& M, int mt, int Dpad, size_t plane_bytes, const char* planes, const float* in,
+inline int spmm_mfma_launch(hipStream_t st, const Switches& sw, const MfmaDev& M, int mt, int Dpad, size_t plane_bytes, const char* planes, const float* in,
                             float* out, double ascale, double shift, double* partial, double* partial_o2, const ExpmPlan* plan, int step, int* viol,
                             MfEpi epi = MfEpi{}, int* grid_out = nullptr /* workgroups launched (the first-order epilogue's trace slab) */,
                             hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr /* recorded by the launch itself (KernelTimers::begin_attached) */) {
@@ -179,8 +163,7 @@ inline int spmm_mfma_launch(hipStream_t st, const MfmaDev& M, int mt, int Dpad, 
         if (grid_out) *grid_out = grid_x * ((ntiles + gtw - 1) / gtw);                                                                 \
     } while (0)
     int gt = 12;  // column tiles per workgroup: 12, 8 or 4
-    static const int gt_env = getenv("MMW_MF_GT") ? atoi(getenv("MMW_MF_GT")) : 0;
-    if (gt_env) gt = gt_env;
+    if (sw.mf_gt) gt = sw.mf_gt;
     else {
         auto wgs = [&](int g) { return (long)M.nb * ((ntiles + g - 1) / g); };
         if (wgs(12) * 2 < 3L * cus) gt = 8;
@@ -188,7 +171,6 @@ inline int spmm_mfma_launch(hipStream_t st, const MfmaDev& M, int mt, int Dpad, 
     }
     if (ntiles <= 4) gt = 4;
     else if (ntiles <= 8 && gt > 8) gt = 8;
-    static const int cfg = getenv("MMW_MF_CFG") ? atoi(getenv("MMW_MF_CFG")) : 0;  // experiments
     // The fragment image pads a block's k-steps to a multiple of MF_KPAD = 4 (3.6 % more k-steps than a padding to 2) so that the first-order
     // product can take four k-steps per barrier: half the barriers, 32 KB of DMA in flight per workgroup.
     // (row tiles, column tiles per wave, waves, row-tile groups of waves, k-steps per chunk, chunks resident).  Measured at the
@@ -196,14 +178,12 @@ inline int spmm_mfma_launch(hipStream_t st, const MfmaDev& M, int mt, int Dpad, 
     // 2 chunks resident (three workgroups per CU) 22.6 us; 4 waves 26.0; 3 chunks resident 25.9; 1 k-step per barrier 33.4;
     // 8 / 12 column tiles per workgroup 36.7 / 48.0 (too few workgroups for 256 CUs).
     if (mt == 1) {
-        if (gt == 4) { if (cfg == 1) MMW_MF_LAUNCH(1, 1, 4, 1, 2, 3); else MMW_MF_LAUNCH(1, 1, 4, 1, 2, 2); }
+        if (gt == 4) MMW_MF_LAUNCH(1, 1, 4, 1, 2, 2);
         else if (gt == 8) MMW_MF_LAUNCH(1, 2, 4, 1, 2, 2);
         else MMW_MF_LAUNCH(1, 3, 4, 1, 1, 3);
     } else {
         if (gt == 4) {
-            if (cfg == 1) MMW_MF_LAUNCH(2, 1, 4, 1, 2, 2);
-            else if (cfg == 4) MMW_MF_LAUNCH(2, 1, 8, 2, 2, 3);
-            else if (mf_first(MODE) && cfg != 6) MMW_MF_LAUNCH(2, 1, 8, 2, 4, 2);  // fp16 operands: four k-steps per barrier fit (68 KB): 21.3 -> 20.2 us
+            if constexpr (mf_first(MODE)) MMW_MF_LAUNCH(2, 1, 8, 2, 4, 2);  // fp16 operands: four k-steps per barrier fit (68 KB): 21.3 -> 20.2 us
             else MMW_MF_LAUNCH(2, 1, 8, 2, 2, 2);
         }
         else if (gt == 8) MMW_MF_LAUNCH(2, 2, 8, 2, 2, 2);
@@ -215,6 +195,8 @@ inline int spmm_mfma_launch(hipStream_t st, const MfmaDev& M, int mt, int Dpad, 
 }
 
 template <typename T> struct ExpmEngine {
+    const Switches& sw;  // the owner's (a handle's, or the stand-alone call's)
+    explicit ExpmEngine(const Switches& s) : sw(s) {}
     hipStream_t st = nullptr;
     int K = 0;
     BlockLayout lay{};
@@ -263,8 +245,7 @@ template <typename T> struct ExpmEngine {
     bool start_colsq_ready = false;  // the producer of the start block already filled `partial` with its column sums of squares (npart_start slabs)
     int npart_start = 0;
     // the a-posteriori stop rides on the shifted Lanczos epilogue of the half-tile and of the generic SpMM (not the full-tile one)
-    bool apost_off = getenv("MMW_NO_APOST") != nullptr;  // read when the handle is created
-    bool apost() const { return (!use_blk || blk.half_tile) && method == MMW_EXPM_LANCZOS && !apost_off; }
+    bool apost() const { return (!use_blk || blk.half_tile) && method == MMW_EXPM_LANCZOS && !sw.no_apost; }
     int kbegin(int slot) { return kt ? kt->begin(slot) : MMW_OK; }
     int kend() { return kt ? kt->end() : MMW_OK; }
 
@@ -297,7 +278,7 @@ template <typename T> struct ExpmEngine {
         MMW_TRY(partial_sq.alloc((size_t)MAX_PART * lay.Dpad));
         MMW_TRY(partial_du.alloc((size_t)MAX_PART * lay.Dpad));
         MMW_TRY(partial_o2.alloc(slabs * lay.Dpad));
-        npart = generic_slabs<T>(K, lay, nblk);
+        npart = generic_slabs<T>(sw, K, lay, nblk);
         MMW_TRY(colsum.alloc(lay.Dpad));
         MMW_TRY(scal.alloc((size_t)4 * (MAX_ORDER + 2) * lay.Dpad));
         MMW_TRY(row_part.alloc((size_t)3 * ROW_GRID_MAX));
@@ -391,7 +372,7 @@ template <typename T> struct ExpmEngine {
                 MMW_TRY(check_slabs(mf.nb));
                 hipEvent_t ea = nullptr, eb = nullptr;
                 if (kt) MMW_TRY(kt->begin_attached(KT_SPMM, &ea, &eb));
-                MMW_TRY((spmm_mfma_launch<MODE>(st, mf, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_in), in, out, ascale,
+                MMW_TRY((spmm_mfma_launch<MODE>(st, sw, mf, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_in), in, out, ascale,
                                                 shift, partial.p, apost() ? partial_o2.p : nullptr, plan, step, viol_d.p, MfEpi{}, nullptr, ea, eb)));
                 return kend();
             }
@@ -405,7 +386,7 @@ template <typename T> struct ExpmEngine {
             MMW_TRY((spmm_blk_launch<T, MODE>(st, blk, lay.Dpad, val_blk, in, out, F, nullptr, ascale, shift, inv_k, partial.p, plan, step,
                                               apost() ? partial_o2.p : nullptr)));
         else
-            MMW_TRY((spmm_launch<T, MODE>(st, K, lay, nblk, indptr, col, val, in, out, F, nullptr, ascale, shift, inv_k, partial.p, plan, step,
+            MMW_TRY((spmm_launch<T, MODE>(st, sw, K, lay, nblk, indptr, col, val, in, out, F, nullptr, ascale, shift, inv_k, partial.p, plan, step,
                                           apost() ? partial_o2.p : nullptr, npart)));
         return kend();
     }
@@ -458,7 +439,7 @@ template <typename T> struct ExpmEngine {
         MMW_HIP(hipStreamSynchronize(st));
         last = *plan_h;
         last_mfma_ok = last.mfma_ok != 0;
-        if (getenv("MMW_VERBOSE")) {
+        if (live_switch(LIVE_VERBOSE)) {
             union { unsigned u; float f; } c1, c2;
             c1.u = last.conv[1]; c2.u = last.conv[2];
             fprintf(stderr, "[plan] rho %.3e absn %.3e mfma_ok %d tol %.1e m %d (a-priori %d) apost %d m_eff %d est[1] %.3e est[2] %.3e viol %d\n", last.rho,
@@ -498,10 +479,10 @@ template <typename T> struct ExpmEngine {
             if (afrag16) {
                 MfmaDev m16 = mf;
                 m16.afrag = reinterpret_cast<const unsigned*>(afrag16);
-                MMW_TRY((spmm_mfma_launch<SPMM_FIRST16>(st, m16, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(0)), U.p, out,
+                MMW_TRY((spmm_mfma_launch<SPMM_FIRST16>(st, sw, m16, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(0)), U.p, out,
                                                         ascale / (double)MF_F16_SCALE, 0.0, partial.p, partial_o2.p, plan_d.p, 1, viol_d.p, E, ntr, ea, eb)));
             } else
-                MMW_TRY((spmm_mfma_launch<SPMM_FIRST>(st, mf, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(0)), U.p, out,
+                MMW_TRY((spmm_mfma_launch<SPMM_FIRST>(st, sw, mf, mf_mt, lay.Dpad, bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(0)), U.p, out,
                                                       ascale / (double)MF_F16_SCALE, 0.0, partial.p, partial_o2.p, plan_d.p, 1, viol_d.p, E, ntr, ea, eb)));
             MMW_TRY(kend());
             planes_ready[0] = false;

@@ -71,12 +71,13 @@ inline double tridiag_min_eig(const std::vector<double>& a, const std::vector<do
 }
 
 template <typename T> struct DenseWork {
+    const Switches& sw;
+    explicit DenseWork(const Switches& s) : sw(s) {}
     hipStream_t st = nullptr;
-    DevBuf<double> G, Q, Q2, G2, Q3, Gpart, cs, diag, dscale, off, scale;
+    DevBuf<double> G, Q, Q2, Gpart, cs, diag, dscale, off, scale;
     DevBuf<int> perm, flag;
     DevBuf<double> dfac;  // the current panel's factored diagonal block (k_chol_panel -> k_chol_update)
     DevBuf<double> dinv;  // the inverses of all diagonal blocks of the last factor (k_chol_panel -> k_trsm_blocked)
-    const bool chol_lds = getenv("MMW_CHOL_LDS") != nullptr;  // the panel's diagonal block factored through LDS (for comparison)
     int bcap = 0;
     int sweeps_total = 0, calls_total = 0;
     int ensure(int b, int nslice) {
@@ -88,33 +89,20 @@ template <typename T> struct DenseWork {
         MMW_TRY(scale.alloc(bcap)); MMW_TRY(perm.alloc(bcap));
         return MMW_OK;
     }
-    static void gram_geometry(int K, int b, int& nslice, int& rps) {
-        const int tiles = ((b + 63) / 64) * ((b + 15) / 16);
-        nslice = std::max(1, std::min(16, (1024 + tiles - 1) / tiles));
-        rps = (K + nslice - 1) / nslice;
-        rps = (rps + 3) / 4 * 4;
-        nslice = (K + rps - 1) / rps;
-    }
     // G = V^T W  (b x b)
     int gram(int K, int b, int ld, const T* V, const T* W, bool sym) {
         int nslice, rps;
         MMW_TRY(ensure(b, 16));
-        static const bool old_gram = getenv("MMW_GRAM_WAVES") != nullptr;  // (the one-wave-per-tile kernel, for comparison)
-        if (old_gram) {
-            gram_geometry(K, b, nslice, rps);
-            hipLaunchKernelGGL((k_gram<T>), dim3((b + 63) / 64, (b + 15) / 16, nslice), dim3(WAVE), 0, st, K, b, ld, V, W, rps, Gpart.p);
-        } else {
-            const int tiles = ((b + 63) / 64) * ((b + 63) / 64);
-            nslice = std::max(1, std::min(16, (768 + tiles - 1) / tiles));
-            rps = ((K + nslice - 1) / nslice + GR_ROWS - 1) / GR_ROWS * GR_ROWS;
-            nslice = (K + rps - 1) / rps;
-            hipLaunchKernelGGL((k_gram_tiles<T>), dim3((b + 63) / 64, (b + 63) / 64, nslice), dim3(BLOCK), 0, st, K, b, ld, V, W, rps, Gpart.p);
-        }
+        const int tiles = ((b + 63) / 64) * ((b + 63) / 64);
+        nslice = std::max(1, std::min(16, (768 + tiles - 1) / tiles));
+        rps = ((K + nslice - 1) / nslice + GR_ROWS - 1) / GR_ROWS * GR_ROWS;
+        nslice = (K + rps - 1) / rps;
+        hipLaunchKernelGGL((k_gram_tiles<T>), dim3((b + 63) / 64, (b + 63) / 64, nslice), dim3(BLOCK), 0, st, K, b, ld, V, W, rps, Gpart.p);
         hipLaunchKernelGGL(k_gram_reduce, dim3(grid_elems((size_t)b * b)), dim3(BLOCK), 0, st, b, nslice, Gpart.p, G.p, sym ? 1 : 0);
         MMW_HIP(hipGetLastError());
         return MMW_OK;
     }
-    // Jacobi of G (b x b) -> eigenvalues in `diag`, eigenvectors in Q (one launch per round, ping-pong buffers)
+    // Jacobi of G (b x b) -> eigenvalues in `diag`, eigenvectors in Q
     DevBuf<double> bjH[2], bjQ[2], bjR;
     int reserve_jacobi(int b) {
         int M = (b + BJ_NB - 1) / BJ_NB;
@@ -130,7 +118,7 @@ template <typename T> struct DenseWork {
         return MMW_OK;
     }
     // block Jacobi (kernels_dense.h, k_bj_solve / k_bj_apply): two launches per block round, M - 1 block rounds per sweep
-    int jacobi_blocked(int b, double rel_tol, int max_sweeps, int* sweeps_done) {
+    int jacobi(int b, double rel_tol, int max_sweeps, int* sweeps_done = nullptr) {
         int M = (b + BJ_NB - 1) / BJ_NB;
         M = std::max(2, M + (M & 1));
         const int P = BJ_NB * M;
@@ -141,7 +129,7 @@ template <typename T> struct DenseWork {
         }
         if (bjR.n < (size_t)(M / 2) * BJ_N2 * BJ_N2) MMW_TRY(bjR.alloc((size_t)(M / 2) * BJ_N2 * BJ_N2));
         MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_bj_apply), BJ_APPLY_LDS));
-        static const bool all_full = getenv("MMW_BJ_FULL") != nullptr;  // every meeting solves the whole 64 x 64 problem
+        const bool all_full = sw.bj_full;  // every meeting solves the whole 64 x 64 problem
         hipLaunchKernelGGL(k_bj_pad, dim3(grid_elems(pp)), dim3(BLOCK), 0, st, b, P, G.p, bjH[0].p, bjQ[0].p);
         int cur = 0, sw = 0;
         double h_off[2] = {0, 0};
@@ -166,49 +154,6 @@ template <typename T> struct DenseWork {
         MMW_HIP(hipGetLastError());
         return MMW_OK;
     }
-    int jacobi(int b, double rel_tol, int max_sweeps, int* sweeps_done = nullptr) {
-        static const bool blocked = getenv("MMW_JACOBI_ROUNDS") == nullptr;
-        if (blocked) return jacobi_blocked(b, rel_tol, max_sweeps, sweeps_done);
-        const int n = (b % 2 == 0) ? b : b + 1;
-        if (b <= JAC_LDS_MAX) {  // small: the whole eigensolve in one launch, matrices in LDS
-            const size_t sh = ((size_t)2 * b * b + n + 2) * sizeof(double);
-            MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_jacobi_lds), (int)(((size_t)2 * JAC_LDS_MAX * JAC_LDS_MAX + JAC_LDS_MAX + 4) * sizeof(double))));
-            hipLaunchKernelGGL(k_jacobi_lds, dim3(1), dim3(1024), sh, st, b, G.p, diag.p, Q.p, rel_tol, max_sweeps, (int*)nullptr);
-            MMW_HIP(hipGetLastError());
-            calls_total += 1;
-            if (sweeps_done) *sweeps_done = 0;
-            return MMW_OK;
-        }
-        if (G2.n < (size_t)b * b) { MMW_TRY(G2.alloc((size_t)bcap * bcap)); MMW_TRY(Q3.alloc((size_t)bcap * bcap)); }
-        hipLaunchKernelGGL(k_set_eye, dim3(grid_elems((size_t)b * b)), dim3(BLOCK), 0, st, b, Q.p);
-        const int half = n / 2;
-        const int ga = grid_elems((size_t)std::max(half * half, b * half));
-        double h_off[2] = {0, 0};
-        double* Hc = G.p;
-        double* Hn = G2.p;
-        double* Qc = Q.p;
-        double* Qn = Q3.p;
-        int sw = 0;
-        for (; sw < max_sweeps; ++sw) {
-            hipLaunchKernelGGL(k_offdiag, dim3(1), dim3(1024), 0, st, b, Hc, off.p);
-            MMW_HIP(hipMemcpyAsync(h_off, off.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-            MMW_HIP(hipStreamSynchronize(st));
-            if (!(std::sqrt(h_off[0]) > rel_tol * h_off[1] * std::sqrt((double)b)) || b < 2) break;
-            for (int r = 0; r < n - 1; ++r) {
-                hipLaunchKernelGGL(k_jacobi_round, dim3(ga), dim3(BLOCK), 0, st, b, n, r, Hc, Hn, Qc, Qn);
-                std::swap(Hc, Hn);
-                std::swap(Qc, Qn);
-            }
-            MMW_HIP(hipGetLastError());
-        }
-        if (sweeps_done) *sweeps_done = sw;
-        sweeps_total += sw;
-        calls_total += 1;
-        hipLaunchKernelGGL(k_get_diag, dim3(grid_elems(b)), dim3(BLOCK), 0, st, b, Hc, diag.p);
-        if (Qc != Q.p) MMW_HIP(hipMemcpyAsync(Q.p, Qc, (size_t)b * b * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MMW_HIP(hipGetLastError());
-        return MMW_OK;
-    }
     // Cholesky of the unit-diagonal Gram matrix D G D in place (G <- L); *ok = false when it is not numerically SPD
     int chol_factor(int b, bool* ok) {
         if (flag.n < 1) MMW_TRY(flag.alloc(1));
@@ -220,7 +165,7 @@ template <typename T> struct DenseWork {
         MMW_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
         for (int j0 = 0; j0 < b; j0 += CH_NB) {
             const int below = b - std::min(b, j0 + CH_NB);
-            hipLaunchKernelGGL(k_chol_panel, dim3(std::max(1, (below + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, b, j0, G.p, flag.p, dfac.p, chol_lds ? 1 : 0, dinv.p);
+            hipLaunchKernelGGL(k_chol_panel, dim3(std::max(1, (below + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, b, j0, G.p, flag.p, dfac.p, sw.chol_lds ? 1 : 0, dinv.p);
             if (below > 0) {
                 const int mt = (below + CH_NB - 1) / CH_NB;
                 hipLaunchKernelGGL(k_chol_update, dim3(mt, mt), dim3(BLOCK), 0, st, b, j0, G.p, (const int*)flag.p, (const double*)dfac.p);
@@ -242,6 +187,8 @@ template <typename T> struct DenseWork {
 };
 
 template <typename T> struct Factorizer {
+    const Switches& sw;
+    explicit Factorizer(const Switches& s) : sw(s), dw(s) {}
     hipStream_t st = nullptr;
     KernelTimers* kt = nullptr;
     int K = 0;
@@ -286,7 +233,7 @@ template <typename T> struct Factorizer {
     int spmm(const BlockLayout& lay, int nblk, const int* indptr, const int* col, const T* val, const T* in, T* outp, T* Fp, const T* X2p,
              double c1, double c2, double c3) {
         if (have_blk) return spmm_blk_launch<T, MODE>(st, blk, lay.Dpad, val_blk.p, in, outp, Fp, X2p, c1, c2, c3, nullptr);
-        return spmm_launch<T, MODE>(st, K, lay, nblk, indptr, col, val, in, outp, Fp, X2p, c1, c2, c3, nullptr);
+        return spmm_launch<T, MODE>(st, sw, K, lay, nblk, indptr, col, val, in, outp, Fp, X2p, c1, c2, c3, nullptr);
     }
 
     // the matrix-core form of the two products above (fp32 only): `in` is read through its planes, the result is written with its own
@@ -305,7 +252,7 @@ template <typename T> struct Factorizer {
         if constexpr (sizeof(T) == 4) {
             MfEpi e;
             e.F = Fp; e.X2 = X2p; e.c3 = (float)c3; e.out_planes = planes_of(outp);
-            return spmm_mfma_launch<MODE>(st, mf, mf_mt, ld, mf_bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(in)), in, outp, c1, c2,
+            return spmm_mfma_launch<MODE>(st, sw, mf, mf_mt, ld, mf_bs * sizeof(unsigned short), reinterpret_cast<const char*>(planes_of(in)), in, outp, c1, c2,
                                           nullptr, nullptr, nullptr, 0, nullptr, e);
         }
         return fail(MMW_ERR_STATE, "matrix-core products are fp32 only");
@@ -316,10 +263,9 @@ template <typename T> struct Factorizer {
     int orthonormalise(int b, int ld, DevBuf<T>& A, DevBuf<T>& B, double eps) {
         // tolerated deviation from the identity for the one-term form of the second pass: its result is off by 3/8 ||E||^2
         const double ns_max = sizeof(T) == 4 ? 1.6e-3 : 5e-7;
-        static const bool ns_on = getenv("MMW_FACTOR_NO_NS") == nullptr;
         for (int pass = 0; pass < 2; ++pass) {
             MMW_TRY(dw.gram(K, b, ld, A.p, A.p, true));
-            if (pass == 1 && ns_on) {
+            if (pass == 1 && !sw.factor_no_ns) {
                 // After the first pass G = I + E with a small E: V (I - E/2) is orthonormal to 3/8 ||E||^2 -- one small kernel and a
                 // tall GEMM instead of a Cholesky factorisation (b / 32 dependent panel steps) and a row substitution.
                 double dev2 = 0.0;
@@ -346,13 +292,8 @@ template <typename T> struct Factorizer {
                 MMW_HIP(hipMemsetAsync(B.p, 0, (size_t)K * ld * sizeof(T), st));
                 MMW_TRY(dw.gemm(K, b, b, ld, A.p, dw.Q2.p, b, B.p));
             } else {  // V <- (V D) L^{-T} by forward substitution on the rows
-                static const bool trsm_rows = getenv("MMW_TRSM_ROWS") != nullptr;  // one wavefront per row (for comparison)
-                if (trsm_rows)
-                    hipLaunchKernelGGL((k_trsm_rows<T>), dim3(grid_rows(K)), dim3(BLOCK), (size_t)WAVES_PER_BLOCK * b * sizeof(double), st, K, b, ld,
-                                       A.p, dw.G.p, dw.dscale.p, B.p);
-                else
-                    hipLaunchKernelGGL((k_trsm_blocked<T>), dim3((K + 63) / 64), dim3(BLOCK), 0, st, K, b, ld, (const T*)A.p, (const double*)dw.G.p,
-                                       (const double*)dw.dscale.p, (const double*)dw.dinv.p, B.p);
+                hipLaunchKernelGGL((k_trsm_blocked<T>), dim3((K + 63) / 64), dim3(BLOCK), 0, st, K, b, ld, (const T*)A.p, (const double*)dw.G.p,
+                                   (const double*)dw.dscale.p, (const double*)dw.dinv.p, B.p);
                 MMW_HIP(hipGetLastError());
             }
             std::swap(A.p, B.p);
@@ -397,6 +338,7 @@ template <typename T> struct Factorizer {
     // factor of A = ascale * (values `val` on the pattern).  out: K*rank float64 (host), or nullptr
     int run(const int* indptr, const int* col, const T* val, double ascale, int rank, uint64_t seed, double* out) {
         if (rank < 1 || rank >= K + 1) return fail(MMW_ERR_ARG, "mmw_factor: rank must be in [1, K]");
+        const bool verbose = live_switch(LIVE_FACTOR_VERBOSE);
         auto vnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double v_t0 = vnow();
         const bool f32 = sizeof(T) == 4;
@@ -410,7 +352,7 @@ template <typename T> struct Factorizer {
         const int nblk = grid_slabs(K);
         // matrix-core filter passes: every block carries its bf16 hi / lo planes right behind its fp32 values
         bool mf_use = false;
-        if constexpr (sizeof(T) == 4) mf_use = have_mf && have_blk && b < K && ld % 32 == 0 && !getenv("MMW_FACTOR_NO_MFMA");
+        if constexpr (sizeof(T) == 4) mf_use = have_mf && have_blk && b < K && ld % 32 == 0 && !sw.factor_no_mfma;
         const size_t bs_alloc = mf_use ? 2 * bs : bs;
         mf_bs = bs;
         if (V.n < bs_alloc) { MMW_TRY(V.alloc(bs_alloc)); MMW_TRY(W.alloc(bs_alloc)); MMW_TRY(Y1.alloc(bs_alloc)); MMW_TRY(Y2.alloc(bs_alloc)); }
@@ -418,35 +360,35 @@ template <typename T> struct Factorizer {
         if (colsum.n < (size_t)ld) MMW_TRY(colsum.alloc(ld));
         if (rho_part.n < (size_t)MAX_PART) MMW_TRY(rho_part.alloc(MAX_PART));
         MMW_TRY(dw.ensure(b, 16));
-        if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   allocations done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+        if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   allocations done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
         if (kt) MMW_TRY(kt->begin(KT_FACTOR));
         if (have_blk) {  // matrix values once into the blocked order (padding entries stay zero)
             if (val_blk.n < (size_t)nent) MMW_TRY(val_blk.alloc((size_t)nent));
             hipLaunchKernelGGL((k_gather_blocked<T>), dim3(grid_elems((size_t)nent)), dim3(BLOCK), 0, st, (size_t)nent, bepos, val, val_blk.p);
-            if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   gather blocked at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+            if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   gather blocked at %.1f ms\n", (vnow() - v_t0) * 1e3); }
         }
         if constexpr (sizeof(T) == 4) {
             if (mf_use) {
                 if (afrag.n < mf_image) MMW_TRY(afrag.alloc(mf_image));
                 MMW_HIP(hipMemsetAsync(afrag.p, 0, mf_image * sizeof(unsigned), st));
-                if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   memset image at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+                if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   memset image at %.1f ms\n", (vnow() - v_t0) * 1e3); }
                 hipLaunchKernelGGL((k_refrag<T>), dim3(grid_elems((size_t)mf_nnz)), dim3(BLOCK), 0, st, (size_t)mf_nnz, val, mf_fpos, afrag.p);
-                if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   refrag at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+                if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   refrag at %.1f ms\n", (vnow() - v_t0) * 1e3); }
                 mf.afrag = afrag.p;
             }
         }
-        if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   matrix copies done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+        if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   matrix copies done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
         // spectral scale: ||A||_1 >= |lambda|_max
         hipLaunchKernelGGL((k_rowabs<T>), dim3(nblk), dim3(BLOCK), 0, st, K, indptr, col, val, ascale, (const double*)nullptr, 0, rho_part.p);
         std::vector<double> hp(nblk);
         MMW_HIP(hipMemcpyAsync(hp.data(), rho_part.p, nblk * sizeof(double), hipMemcpyDeviceToHost, st));
         MMW_HIP(hipStreamSynchronize(st));
         const double rho = *std::max_element(hp.begin(), hp.end());
-        if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   norm bound done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+        if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   norm bound done at %.1f ms\n", (vnow() - v_t0) * 1e3); }
         // random start block (rows of unit norm; any full-rank start works)
         hipLaunchKernelGGL((k_sketch_rng<T>), dim3(nblk), dim3(BLOCK), 0, st, K, b, ld, seed ^ 0x9E3779B97F4A7C15ull, 0u, V.p, (double*)nullptr);
         MMW_TRY(orthonormalise(b, ld, V, W, 1e-14));
-        if (getenv("MMW_FACTOR_VERBOSE")) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   start block orthonormal at %.1f ms\n", (vnow() - v_t0) * 1e3); }
+        if (verbose) { (void)hipStreamSynchronize(st); fprintf(stderr, "[factor]   start block orthonormal at %.1f ms\n", (vnow() - v_t0) * 1e3); }
         std::vector<double> theta(b), res(b), hres((size_t)64 * b);
         std::vector<int> perm(b);
         std::vector<double> ones(b, 1.0);
@@ -468,7 +410,7 @@ template <typename T> struct Factorizer {
             // With 1 x tol -- every filter pass there is, since a pass runs only while the residual is above the tolerance -- the last
             // residuals end at 2.6e-6 instead of 5e-7: the split's own floor, an eighth of the tolerance, and the last pass of the small
             // ranks costs half.  A pass on the matrix cores that does not halve a residual below 100 x tol sends the rest to the fp32 kernel.)
-            static const double mf_floor = getenv("MMW_FACTOR_MF_FLOOR") ? atof(getenv("MMW_FACTOR_MF_FLOOR")) : 1.0;
+            constexpr double mf_floor = 1.0;
             const bool mf_stage = mf_use && !mf_stalled && (outer == 0 || last_resid > mf_floor * tol);
             const bool no_rr_next = rr_skip > 0 && b < K;
             // ---- Rayleigh-Ritz on span(V)
@@ -489,7 +431,7 @@ template <typename T> struct Factorizer {
             // Jacobi sweeps of b - 1 launches each).
             // (Seeding the block with the previous probe's Ritz vectors was tried: the averaged X of neighbouring slot counts
             // do not share their leading subspace -- first residual 0.2 either way -- so every call starts from a random block.)
-            skip_rr = outer == 0 && b > JAC_LDS_MAX && b < K && !getenv("MMW_FACTOR_FULL_RR");
+            skip_rr = outer == 0 && b > JAC_LDS_MAX && b < K && !sw.factor_full_rr;
             if (skip_rr) {
                 hipLaunchKernelGGL(k_set_eye, dim3(grid_elems((size_t)b * b)), dim3(BLOCK), 0, st, b, dw.Q.p);
                 hipLaunchKernelGGL(k_get_diag, dim3(grid_elems(b)), dim3(BLOCK), 0, st, b, dw.G.p, dw.diag.p);
@@ -497,11 +439,9 @@ template <typename T> struct Factorizer {
                 // The eigensolve only has to be as sharp as the subspace is: what it leaves off the diagonal mixes Ritz pairs whose residuals are
                 // still `last_resid`, so 1e-2 of that (never looser than 1e-4, never tighter than the final 1e-8 / 1e-13; the residuals that decide are true residuals of the rotated vectors) costs the residual
                 // estimate nothing and the block Jacobi a sweep or two per call (b = 444: a sweep is 13 block rounds of two launches).
-                static const bool jac_fixed = getenv("MMW_FACTOR_JACOBI_FIXED") != nullptr;
                 const double jac_fin = f32 ? 1e-8 : 1e-13;
-                static const double jac_rel = getenv("MMW_FACTOR_JACOBI_REL") ? atof(getenv("MMW_FACTOR_JACOBI_REL")) : 1e-2;
-                static const double jac_cap = getenv("MMW_FACTOR_JACOBI_CAP") ? atof(getenv("MMW_FACTOR_JACOBI_CAP")) : 1e-4;
-                const double jac_tol = (jac_fixed || outer == 0 || !(last_resid > 0.0)) ? jac_fin : std::max(jac_fin, std::min(jac_cap, jac_rel * last_resid));
+                constexpr double jac_rel = 1e-2, jac_cap = 1e-4;
+                const double jac_tol = (outer == 0 || !(last_resid > 0.0)) ? jac_fin : std::max(jac_fin, std::min(jac_cap, jac_rel * last_resid));
                 MMW_TRY(dw.jacobi(b, jac_tol, 30));
             }
             MMW_HIP(hipMemcpyAsync(theta.data(), dw.diag.p, b * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -534,12 +474,12 @@ template <typename T> struct Factorizer {
             const double scale_top = std::max(std::fabs(theta[0]), 1e-300);
             last_resid = worst / scale_top;
             if (mf_last_pass && prev_resid > 0.0 && last_resid < 100.0 * tol && last_resid > 0.5 * prev_resid) mf_stalled = true;
-            if (getenv("MMW_FACTOR_VERBOSE")) fprintf(stderr, "[factor]   outer %d degree %d resid %.2e at %.1f ms\n", outer, degree, last_resid, (vnow() - v_t0) * 1e3);
+            if (verbose) fprintf(stderr, "[factor]   outer %d degree %d resid %.2e at %.1f ms\n", outer, degree, last_resid, (vnow() - v_t0) * 1e3);
             if (!skip_rr && (b >= K || last_resid <= tol)) {
                 done = true;
                 break;
             }
-            if (!skip_rr && !getenv("MMW_FACTOR_FULL_RR")) rr_skip = last_resid > 1e3 * tol ? 2 : (last_resid > 30.0 * tol ? 1 : 0);
+            if (!skip_rr && !sw.factor_full_rr) rr_skip = last_resid > 1e3 * tol ? 2 : (last_resid > 30.0 * tol ? 1 : 0);
             }  // Rayleigh-Ritz
             // ---- Chebyshev filter on B = A^2 damping [0, cut], cut = smallest Ritz value of B in the block
             const double mu_top = theta[0] * theta[0];
@@ -595,8 +535,8 @@ template <typename T> struct Factorizer {
         }
         outer_done = outer;
         if (kt) MMW_TRY(kt->end());
-        if (getenv("MMW_FACTOR_VERBOSE")) fprintf(stderr, "[factor]   iteration done at %.1f ms\n", (vnow() - v_t0) * 1e3);
-        if (getenv("MMW_FACTOR_VERBOSE"))
+        if (verbose) fprintf(stderr, "[factor]   iteration done at %.1f ms\n", (vnow() - v_t0) * 1e3);
+        if (verbose)
             fprintf(stderr, "[factor] K=%d rank=%d b=%d outer=%d degree_last=%d resid=%.2e jacobi_sweeps=%d jacobi_calls=%d\n", K, rank, b, outer, degree,
                     last_resid, dw.sweeps_total, dw.calls_total);
         if (!done && last_resid > 100 * tol)
@@ -619,11 +559,11 @@ template <typename T> struct Factorizer {
         else MMW_HIP(hipStreamSynchronize(st));
         last_n = (size_t)K * rank;
         last_rank = rank;
-        if (getenv("MMW_FACTOR_VERBOSE")) fprintf(stderr, "[factor]   export + copy-out done at %.1f ms\n", (vnow() - v_t0) * 1e3);
+        if (verbose) fprintf(stderr, "[factor]   export + copy-out done at %.1f ms\n", (vnow() - v_t0) * 1e3);
 
         // restore the unit column scales used by k_select_cols
         if (out) memcpy(out, last_host.p, last_n * sizeof(double));
-        if (getenv("MMW_FACTOR_VERBOSE")) fprintf(stderr, "[factor]   host copy done at %.1f ms\n", (vnow() - v_t0) * 1e3);
+        if (verbose) fprintf(stderr, "[factor]   host copy done at %.1f ms\n", (vnow() - v_t0) * 1e3);
         return MMW_OK;
     }
 };

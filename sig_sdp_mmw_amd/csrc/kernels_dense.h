@@ -14,48 +14,12 @@ namespace mmw {
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 // ---- G_part[slice] (b x b) += V[rows of slice]^T W[rows of slice] ---------------------------------
-// grid = (ceil(b/64) j-tiles, ceil(b/16) i-tiles, nslice); one wavefront per workgroup tile 16(i) x 64(j).
-// v_mfma_f64_16x16x4_f64: lane l feeds A[i = l&15][k = l>>4] = V[k][i] and B[k][j = l&15] = W[k][j]:
-// both are 16 consecutive elements of a block row -> coalesced straight from global memory.
-template <typename T>
-__global__ __launch_bounds__(WAVE) void k_gram(int K, int b, int ld, const T* __restrict__ V, const T* __restrict__ W,
-                                               int rows_per_slice, double* __restrict__ Gpart) {
-    const int lane = threadIdx.x;
-    const int j0 = blockIdx.x * 64, i0 = blockIdx.y * 16, sl = blockIdx.z;
-    const int r_beg = sl * rows_per_slice;
-    const int r_end = min(K, r_beg + rows_per_slice);
-    const int li = lane & 15, lk = lane >> 4;
-    d4 acc[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[n] = (d4){0.0, 0.0, 0.0, 0.0};
-    const bool iok = i0 + li < b;
-    bool jok[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) jok[n] = j0 + n * 16 + li < b;
-    for (int r = r_beg; r < r_end; r += 4) {
-        const int row = r + lk;
-        const bool rok = row < r_end;
-        const double a = (rok && iok) ? (double)V[(size_t)row * ld + i0 + li] : 0.0;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const double bb = (rok && jok[n]) ? (double)W[(size_t)row * ld + j0 + n * 16 + li] : 0.0;
-            acc[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bb, acc[n], 0, 0, 0);
-        }
-    }
-    double* G = Gpart + (size_t)sl * b * b;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + lk + 4 * q, j = j0 + n * 16 + li;
-            if (i < b && j < b) G[(size_t)i * b + j] = acc[n][q];
-        }
-}
-// The same product from LDS tiles: a workgroup of four waves owns a 64 x 64 tile of G for one slice of rows and walks the rows 16 at a
+// v_mfma_f64_16x16x4_f64: lane l feeds A[i = l&15][k = l>>4] = V[k][i] and B[k][j = l&15] = W[k][j].
+// From LDS tiles: a workgroup of four waves owns a 64 x 64 tile of G for one slice of rows and walks the rows 16 at a
 // time -- every thread brings 16 bytes of V and of W per stage (a row's 64 columns are one 256-byte run), double-buffered, and wave w
-// multiplies its 16 columns of V with the tile's 64 columns of W exactly as k_gram does.  k_gram's one wave per 16 x 64 tile fetched
-// its operands in 64-byte runs, one row per lane group, W once per 16 rows of G: 627 MB of 64-byte requests per call at b = 444
-// (418 us, 9 TFLOP/s); here 250 MB in 256-byte runs.  Row stride 80 floats in LDS: the four k-rows of a fragment read fall on four
+// multiplies its 16 columns of V with the tile's 64 columns of W.  The first Gram kernel (k_gram, removed: one wave per 16 x 64 tile, operands
+// straight from global memory) fetched them in 64-byte runs, one row per lane group, W once per 16 rows of G: 627 MB of 64-byte requests per
+// call at b = 444 (418 us, 9 TFLOP/s); here 250 MB in 256-byte runs.  Row stride 80 floats in LDS: the four k-rows of a fragment read fall on four
 // different 16-bank groups.
 constexpr int GR_ROWS = 16, GR_LD = 80;
 template <typename T>
@@ -184,157 +148,14 @@ __device__ __forceinline__ void jacobi_pair(int n, int r, int i, int& p, int& q)
         q = t;
     }
 }
-// rotation (c, s) that annihilates H[p][q]
-__device__ __forceinline__ void jacobi_cs(const double* __restrict__ H, int b, int p, int q, double& c, double& s) {
-    c = 1.0;
-    s = 0.0;
-    if (q < b) {
-        const double apq = H[(size_t)p * b + q];
-        if (apq != 0.0) {
-            const double app = H[(size_t)p * b + p], aqq = H[(size_t)q * b + q];
-            const double tau = (aqq - app) / (2.0 * apq);
-            const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            c = 1.0 / sqrt(1.0 + t * t);
-            s = t * c;
-        }
-    }
-}
-// one Jacobi round in ONE launch, ping-pong buffers: Hout = J^T Hin J on 2x2 blocks (pair i, pair j), Qout = Qin J.
-// Every thread rebuilds the two rotations it needs from the untouched input matrix, so there is no
-// separate parameter pass and no race.
-__global__ __launch_bounds__(BLOCK) void k_jacobi_round(int b, int n, int r, const double* __restrict__ Hin, double* __restrict__ Hout,
-                                                        const double* __restrict__ Qin, double* __restrict__ Qout) {
-    const int half = n / 2;
-    const int total = half * half;
-    for (int o = blockIdx.x * BLOCK + threadIdx.x; o < total; o += gridDim.x * BLOCK) {
-        const int i = o / half, j = o % half;
-        int pi, qi, pj, qj;
-        jacobi_pair(n, r, i, pi, qi);
-        jacobi_pair(n, r, j, pj, qj);
-        double ci, si, cj, sj;
-        jacobi_cs(Hin, b, pi, qi, ci, si);
-        jacobi_cs(Hin, b, pj, qj, cj, sj);
-        const bool qi_ok = qi < b, qj_ok = qj < b;
-        double h00 = Hin[(size_t)pi * b + pj];
-        double h01 = qj_ok ? Hin[(size_t)pi * b + qj] : 0.0;
-        double h10 = qi_ok ? Hin[(size_t)qi * b + pj] : 0.0;
-        double h11 = (qi_ok && qj_ok) ? Hin[(size_t)qi * b + qj] : 0.0;
-        const double t00 = ci * h00 - si * h10, t01 = ci * h01 - si * h11;
-        const double t10 = si * h00 + ci * h10, t11 = si * h01 + ci * h11;
-        h00 = t00 * cj - t01 * sj;
-        h01 = t00 * sj + t01 * cj;
-        h10 = t10 * cj - t11 * sj;
-        h11 = t10 * sj + t11 * cj;
-        Hout[(size_t)pi * b + pj] = h00;
-        if (qj_ok) Hout[(size_t)pi * b + qj] = h01;
-        if (qi_ok) Hout[(size_t)qi * b + pj] = h10;
-        if (qi_ok && qj_ok) Hout[(size_t)qi * b + qj] = h11;
-    }
-    const int totq = b * half;
-    for (int o = blockIdx.x * BLOCK + threadIdx.x; o < totq; o += gridDim.x * BLOCK) {
-        const int x = o / half, j = o % half;
-        int pj, qj;
-        jacobi_pair(n, r, j, pj, qj);
-        const double a = Qin[(size_t)x * b + pj];
-        if (qj >= b) {
-            Qout[(size_t)x * b + pj] = a;
-            continue;
-        }
-        double cj, sj;
-        jacobi_cs(Hin, b, pj, qj, cj, sj);
-        const double d = Qin[(size_t)x * b + qj];
-        Qout[(size_t)x * b + pj] = a * cj - d * sj;
-        Qout[(size_t)x * b + qj] = a * sj + d * cj;
-    }
-}
-// ---- whole Jacobi eigensolve of a small matrix (b <= JAC_LDS_MAX) in ONE launch: H and Q live in LDS, rounds are
-// separated by workgroup barriers instead of kernel boundaries.  Same rotations and ordering as k_jacobi_round.
-constexpr int JAC_LDS_MAX = 96;
-__global__ __launch_bounds__(1024) void k_jacobi_lds(int b, const double* __restrict__ Hin, double* __restrict__ diag, double* __restrict__ Qout,
-                                                     double rel_tol, int max_sweeps, int* __restrict__ sweeps_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* H = reinterpret_cast<double*>(smem_raw);  // [b][b]
-    double* Q = H + (size_t)b * b;                    // [b][b]
-    double* cs = Q + (size_t)b * b;                   // [n]
-    __shared__ double red[32];
-    __shared__ int stop;
-    const int n = (b % 2 == 0) ? b : b + 1, half = n / 2;
-    for (int o = threadIdx.x; o < b * b; o += blockDim.x) {
-        H[o] = Hin[o];
-        Q[o] = (o / b == o % b) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    int sw = 0;
-    for (; sw < max_sweeps; ++sw) {
-        // off-diagonal norm and diagonal scale
-        double s = 0.0, d = 0.0;
-        for (int o = threadIdx.x; o < b * b; o += blockDim.x) {
-            const int i = o / b, j = o % b;
-            const double h = H[o];
-            if (i != j) s += h * h;
-            else d = fabs(h) > d ? fabs(h) : d;
-        }
-        s = wave_sum(s);
-        d = wave_max(d);
-        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; red[16 + (threadIdx.x >> 6)] = d; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double ts = 0.0, td = 0.0;
-            for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { ts += red[w]; td = red[16 + w] > td ? red[16 + w] : td; }
-            stop = !(sqrt(ts) > rel_tol * td * sqrt((double)b)) || b < 2;
-        }
-        __syncthreads();
-        if (stop) break;
-        for (int r = 0; r < n - 1; ++r) {
-            for (int i = threadIdx.x; i < half; i += blockDim.x) {
-                int p, q;
-                jacobi_pair(n, r, i, p, q);
-                double c, sn;
-                jacobi_cs(H, b, p, q, c, sn);
-                cs[2 * i] = c;
-                cs[2 * i + 1] = sn;
-            }
-            __syncthreads();
-            for (int o = threadIdx.x; o < half * half; o += blockDim.x) {
-                const int i = o / half, j = o % half;
-                int pi, qi, pj, qj;
-                jacobi_pair(n, r, i, pi, qi);
-                jacobi_pair(n, r, j, pj, qj);
-                const double ci = cs[2 * i], si = cs[2 * i + 1], cj = cs[2 * j], sj = cs[2 * j + 1];
-                const bool qi_ok = qi < b, qj_ok = qj < b;
-                double h00 = H[pi * b + pj];
-                double h01 = qj_ok ? H[pi * b + qj] : 0.0;
-                double h10 = qi_ok ? H[qi * b + pj] : 0.0;
-                double h11 = (qi_ok && qj_ok) ? H[qi * b + qj] : 0.0;
-                const double t00 = ci * h00 - si * h10, t01 = ci * h01 - si * h11;
-                const double t10 = si * h00 + ci * h10, t11 = si * h01 + ci * h11;
-                H[pi * b + pj] = t00 * cj - t01 * sj;
-                if (qj_ok) H[pi * b + qj] = t00 * sj + t01 * cj;
-                if (qi_ok) H[qi * b + pj] = t10 * cj - t11 * sj;
-                if (qi_ok && qj_ok) H[qi * b + qj] = t10 * sj + t11 * cj;
-            }
-            for (int o = threadIdx.x; o < b * half; o += blockDim.x) {
-                const int x = o / half, j = o % half;
-                int pj, qj;
-                jacobi_pair(n, r, j, pj, qj);
-                if (qj >= b) continue;
-                const double cj = cs[2 * j], sj = cs[2 * j + 1];
-                const double a = Q[x * b + pj], dd = Q[x * b + qj];
-                Q[x * b + pj] = a * cj - dd * sj;
-                Q[x * b + qj] = a * sj + dd * cj;
-            }
-            __syncthreads();
-        }
-    }
-    for (int o = threadIdx.x; o < b * b; o += blockDim.x) Qout[o] = Q[o];
-    for (int i = threadIdx.x; i < b; i += blockDim.x) diag[i] = H[i * b + i];
-    if (threadIdx.x == 0 && sweeps_out) *sweeps_out = sw;
-}
-// ---- block Jacobi: the eigensolve above one round per launch (b - 1 launches a sweep, each a few microseconds of work) is
+// (The element-wise solvers built on this order -- k_jacobi_round, one round per launch, and k_jacobi_lds, a whole small eigensolve in one
+// workgroup's LDS -- were measured against the block Jacobi below and removed.)
+constexpr int JAC_LDS_MAX = 96;  // the factor takes its first Rayleigh-Ritz step's eigensolve only up to this width (factor.h, skip_rr)
+// ---- block Jacobi: an eigensolve of one element round per launch (b - 1 launches a sweep, each a few microseconds of work) is
 // launch-bound.  Here the matrix is cut into 32-wide block columns (M of them, M even, zero-padded to P = 32 M); a block round
 // pairs them up disjointly (the same round-robin order, on blocks), and per round two launches do the work of ~63 element
-// rounds: k_bj_solve runs a cyclic Jacobi sweep on every pair's 64 x 64 diagonal problem in LDS (rotations as in
-// k_jacobi_lds) and leaves the accumulated 64 x 64 orthogonal factor R_a per pair; k_bj_apply forms H <- R^T H R and Q <- Q R
+// rounds: k_bj_solve runs a cyclic Jacobi sweep on every pair's 64 x 64 diagonal problem in LDS
+// and leaves the accumulated 64 x 64 orthogonal factor R_a per pair; k_bj_apply forms H <- R^T H R and Q <- Q R
 // from the untouched input (ping-pong buffers), one workgroup per pair of pairs / per 64 rows of Q.  M - 1 block rounds make a
 // block sweep: every element pair has then been rotated at least once.  Padding rows are zero, so no rotation touches them.
 constexpr int BJ_NB = 32, BJ_N2 = 64;
@@ -468,7 +289,7 @@ __global__ __launch_bounds__(BLOCK) void k_bj_apply(int M, int P, int r, const d
     }
     __syncthreads();
     // 64 x 64 x 64 products on the fp64 matrix cores: wave w owns output rows 16 w .. 16 w + 15, four 16 x 16 column tiles
-    // (operand / accumulator layout of v_mfma_f64_16x16x4_f64 as in k_gram)
+    // (operand / accumulator layout of v_mfma_f64_16x16x4_f64 as in k_gram_tiles)
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const int li = lane & 15, lk = lane >> 4;
     d4 acc[4];
@@ -715,9 +536,9 @@ __global__ __launch_bounds__(BLOCK) void k_chol_update(int b, int j0, double* __
 }
 // ---- Vout = (V diag(dscale)) L^{-T} in column blocks of 32 on the fp64 matrix cores: X_J = (V_J D_J - X_{<J} L[J, <J]^T) Linv_JJ^T with the
 // inverses of L's diagonal blocks from k_chol_panel.  A workgroup owns 64 rows and walks the blocks left to right (its rows depend on
-// nobody else's); the part of X already computed comes back from Vout (as stored, in T) through LDS tiles of 64 columns.  k_trsm_rows
-// below -- one wavefront per row, b dependent steps of a 64-lane sum, two broadcasts and a division -- took 0.13 ms at b = 105 and
-// 0.89 ms at b = 444.
+// nobody else's); the part of X already computed comes back from Vout (as stored, in T) through LDS tiles of 64 columns.  The row-wise
+// form it replaced (k_trsm_rows, removed: one wavefront per row, b dependent steps of a 64-lane sum, two broadcasts and a division) took
+// 0.13 ms at b = 105 and 0.89 ms at b = 444.
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_trsm_blocked(int K, int b, int ld, const T* __restrict__ V, const double* __restrict__ L,
                                                        const double* __restrict__ dscale, const double* __restrict__ Dinv, T* __restrict__ Vout) {
@@ -778,30 +599,6 @@ __global__ __launch_bounds__(BLOCK) void k_trsm_blocked(int K, int b, int ld, co
     for (int o = threadIdx.x; o < 64 * (ld - b); o += BLOCK) {  // padding columns
         const int rr = o / (ld - b), c = b + o % (ld - b);
         if (r0 + rr < K) Vout[(size_t)(r0 + rr) * ld + c] = T(0);
-    }
-}
-// ---- Vout[r,:] = (V[r,:] * dscale) L^{-T}: forward substitution per block row, one wavefront per row.
-// x_j = (v_j d_j - sum_{i<j} x_i L[j][i]) / L[j][j]; the running x lives in LDS, row j of L is read coalesced.
-// This is the orthonormalising right factor of Cholesky-QR applied without ever forming an inverse.
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void k_trsm_rows(int K, int b, int ld, const T* __restrict__ V, const double* __restrict__ L,
-                                                     const double* __restrict__ dscale, T* __restrict__ Vout) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* xs = reinterpret_cast<double*>(smem_raw);  // [WAVES_PER_BLOCK][b]
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    double* x = xs + (size_t)wib * b;
-    for (int row = blockIdx.x * WAVES_PER_BLOCK + wib; row < K; row += gridDim.x * WAVES_PER_BLOCK) {
-        for (int j = 0; j < b; ++j) {
-            double s = 0.0;
-            const double* Lj = L + (size_t)j * b;
-            for (int i = lane; i < j; i += WAVE) s += x[i] * Lj[i];
-            s = wave_sum(s);
-            if (lane == 0) x[j] = ((double)V[(size_t)row * ld + j] * dscale[j] - s) / Lj[j];
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): x[j] is in LDS before the next step reads it
-        }
-        for (int j = lane; j < b; j += WAVE) Vout[(size_t)row * ld + j] = (T)x[j];
-        for (int j = b + lane; j < ld; j += WAVE) Vout[(size_t)row * ld + j] = T(0);
     }
 }
 // off-diagonal Frobenius norm^2 and diagonal scale: out[0] = sum_{i != j} H_ij^2, out[1] = max |H_ii|

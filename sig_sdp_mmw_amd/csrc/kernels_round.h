@@ -130,13 +130,9 @@ __global__ __launch_bounds__(BLOCK) void k_slot_pref(int K, int Z, const double*
 // gain_sum[n][z] accumulates S[k'][n] over the members k' of slot z in assignment order, exactly like
 // the reference's dense row adds (sdp_solver.py:94) restricted to the nonzeros (user-major layout: the
 // Z sums of one user are contiguous).
-// The loop is sequential in the users, so its speed is the length of the dependent-load chain per user.
-// Everything that does not depend on earlier assignments (the user's id, neighbour lists, gains, thresholds,
-// preference row) is fetched one user ahead into a double-buffered LDS record; what remains on the chain is
-// slot[n] (LDS when K fits) -> gain_sum[n][slot[n]].
-struct GreedyLds {          // one prefetched user
-    int k, deg, qdeg, pad;
-};
+// The loop is sequential in the users, so its speed is the length of the dependent-load chain per user: slot[n] (LDS when K
+// fits) -> gain_sum[n][slot[n]].  (The first kernel, k_greedy, took one user per step with everything else fetched one user ahead
+// into a double-buffered LDS record: 3.5 us per user.  Measured against k_greedy_b below and removed.)
 // one header per processing position (shared by the attempts of a batch): everything needed to address user order[kk]'s
 // static data without a chain of dependent loads
 struct GreedyHdr {
@@ -155,157 +151,14 @@ __global__ __launch_bounds__(BLOCK) void k_greedy_headers(int K, const int* __re
         hdr[kk] = h;
     }
 }
-// workgroup barrier that orders LDS traffic only: global loads issued earlier (the prefetch of the next user) stay in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <bool SLOT_LDS>
-__global__ __launch_bounds__(BLOCK) void k_greedy(int K, int Z, int maxdeg, int maxq, const GreedyHdr* __restrict__ hdr,
-                                                  const int* __restrict__ pref_all, const int* __restrict__ so_indices,
-                                                  const double* __restrict__ so_data, const double* __restrict__ so_hmax,
-                                                  const int* __restrict__ q_indices, double* __restrict__ gain_all,
-                                                  int* __restrict__ slot_all, int* __restrict__ rem) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    // layout: [2] x { nid[maxdeg] int, nval[maxdeg] f64, nh[maxdeg] f64, qid[maxq] int, pref[Z] int }, bad[Z] int, slot[K] int (optional)
-    char* sp = smem_raw;
-    double* nval[2]; double* nh[2]; int* nid[2]; int* qid[2]; int* prf[2];
-    for (int s2 = 0; s2 < 2; ++s2) { nval[s2] = reinterpret_cast<double*>(sp); sp += (size_t)maxdeg * 8; nh[s2] = reinterpret_cast<double*>(sp); sp += (size_t)maxdeg * 8; }
-    for (int s2 = 0; s2 < 2; ++s2) { nid[s2] = reinterpret_cast<int*>(sp); sp += (size_t)maxdeg * 4; qid[s2] = reinterpret_cast<int*>(sp); sp += (size_t)maxq * 4;
-                                     prf[s2] = reinterpret_cast<int*>(sp); sp += (size_t)Z * 4; }
-    int* bad = reinterpret_cast<int*>(sp); sp += (size_t)Z * 4;
-    int* slot_l = reinterpret_cast<int*>(sp);
-    __shared__ GreedyLds rec[2];
-    __shared__ double hk[2];
-    __shared__ int best;
-    __shared__ int unassigned;
-    const int b = blockIdx.x;
-    const int* pref = pref_all + (size_t)b * K * Z;
-    double* gain = gain_all + (size_t)b * K * Z;   // [K][Z]
-    int* slot_g = slot_all + (size_t)b * K;
-    int* slot = SLOT_LDS ? slot_l : slot_g;
-    if (SLOT_LDS)
-        for (int i = threadIdx.x; i < K; i += BLOCK) slot_l[i] = -1;
-    if (threadIdx.x == 0) unassigned = 0;
-    // Software pipeline over the users, none of its loads depends on another load of the same step:
-    //   step kk   requests the header of user kk+2 (h2) and, with the header of user kk+1 that arrived during step kk-1 (h1),
-    //             that user's neighbour ids, gains, thresholds (so_hmax: h_max of the neighbour, per edge), access-point
-    //             peers and preference row; they are written to the other LDS record at the end of the step (commit).
-    // The barriers inside a step order LDS only (lds_barrier), so these requests stay in flight; the barrier that ends the
-    // step is a full one: it publishes the step's additions to gain[] (global) before the next user's sums are read.
-    constexpr int NE = 4;  // neighbour elements per thread: maxdeg <= NE * BLOCK
-    GreedyHdr h1 = hdr[0], h2 = hdr[K > 1 ? 1 : 0];
-    int r_n[NE], r_q[NE], r_p[NE];
-    double r_v[NE], r_h[NE];
-    auto issue = [&](const GreedyHdr& h) {
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int e = threadIdx.x + i * BLOCK;
-            r_n[i] = e < h.deg ? so_indices[h.sb + e] : 0;
-            r_v[i] = e < h.deg ? so_data[h.sb + e] : 0.0;
-            r_h[i] = e < h.deg ? so_hmax[h.sb + e] : 0.0;
-            r_q[i] = e < h.qdeg ? q_indices[h.qb + e] : 0;
-            r_p[i] = e < Z ? pref[(size_t)h.k * Z + e] : 0;
-        }
-    };
-    auto commit = [&](int s2, const GreedyHdr& h) {
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int e = threadIdx.x + i * BLOCK;
-            if (e < h.deg) { nid[s2][e] = r_n[i]; nval[s2][e] = r_v[i]; nh[s2][e] = r_h[i]; }
-            if (e < h.qdeg) qid[s2][e] = r_q[i];
-            if (e < Z) prf[s2][e] = r_p[i];
-        }
-        if (threadIdx.x == 0) {
-            rec[s2].k = h.k; rec[s2].deg = h.deg; rec[s2].qdeg = h.qdeg;
-            hk[s2] = h.hk;
-        }
-    };
-    issue(h1);
-    commit(0, h1);
-    h1 = h2;                                  // header of user 1
-    if (K > 2) h2 = hdr[2];
-    __syncthreads();
-    for (int kk = 0; kk < K; ++kk) {
-        const int cur = kk & 1;
-        const bool more = kk + 1 < K;
-        const GreedyHdr hn = h1;               // user kk+1 (arrived during the previous step)
-        const int k = rec[cur].k, deg = rec[cur].deg, qdeg = rec[cur].qdeg;
-        const double hmk = hk[cur];
-        // the sums on the chain, requested together: the user's own row and, through slot[], each neighbour's sum in its slot
-        double g_self[NE];
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int z = threadIdx.x + i * BLOCK;
-            g_self[i] = z < Z ? gain[(size_t)k * Z + z] : 0.0;
-        }
-        int zn_e[NE];
-        double g_ne[NE];
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int e = threadIdx.x + i * BLOCK;
-            zn_e[i] = -1;
-            g_ne[i] = 0.0;
-            if (e < deg) {
-                zn_e[i] = slot[nid[cur][e]];
-                if (zn_e[i] >= 0) g_ne[i] = gain[(size_t)nid[cur][e] * Z + zn_e[i]];
-            }
-        }
-        // the prefetch is requested AFTER the chain loads: loads return in order, so waiting for the chain loads leaves every
-        // younger request in flight
-        if (more) issue(hn);
-        h1 = h2;
-        if (kk + 3 < K) h2 = hdr[kk + 3];      // two steps ahead
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int z = threadIdx.x + i * BLOCK;
-            if (z < Z) bad[z] = g_self[i] > hmk ? 1 : 0;
-        }
-        if (threadIdx.x == 0) best = Z;
-        lds_barrier();
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int e = threadIdx.x + i * BLOCK;
-            if (e < deg && zn_e[i] >= 0 && g_ne[i] + nval[cur][e] > nh[cur][e]) bad[zn_e[i]] = 1;
-        }
-        for (int e = threadIdx.x; e < qdeg; e += BLOCK) {
-            const int zn = slot[qid[cur][e]];
-            if (zn >= 0) bad[zn] = 1;
-        }
-        lds_barrier();
-        for (int zz = threadIdx.x; zz < Z; zz += BLOCK)
-            if (!bad[prf[cur][zz]]) {
-                atomicMin(&best, zz);
-                break;  // this thread's later candidates are worse
-            }
-        lds_barrier();
-        const int zz = best;
-        if (zz < Z) {
-            const int z = prf[cur][zz];
-            // fire-and-forget f64 atomic adds: one add per address and step, the steps separated by the full barrier below,
-            // so the sums are formed in the reference's order (sdp_solver.py:94) without waiting for a load
-            for (int e = threadIdx.x; e < deg; e += BLOCK) unsafeAtomicAdd(&gain[(size_t)nid[cur][e] * Z + z], nval[cur][e]);
-            if (threadIdx.x == 0) {
-                slot[k] = z;
-                if (SLOT_LDS) slot_g[k] = z;
-            }
-        } else if (threadIdx.x == 0) {
-            unassigned++;
-        }
-        if (more) commit(cur ^ 1, hn);
-        __threadfence_block();
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) rem[b] = unassigned;
-}
-
-
 // ---- the same greedy pass, several users per step ------------------------------------------------------------------------
-// The loop above is sequential in the users because a user's decision reads what earlier users wrote: slot[] of its out- and
+// The pass is sequential in the users because a user's decision reads what earlier users wrote: slot[] of its out- and
 // access-point neighbours, its own row of gain sums and the sums of its neighbours.  Two users a, b touch disjoint state -- and
 // can be decided in the same step with the reference's result -- unless a is an out-neighbour of b or b of a, they share an access
 // point, or they have a common out-neighbour.  The visiting order is by descending ||gX_k||, unrelated to the geometry, so on an
-// interference graph consecutive users rarely interact (~4 % of pairs at the benchmark).  k_greedy_conflicts finds, for every
-// position of the order, the nearest earlier position within the window that it interacts with; k_greedy_b then takes, per step,
-// the longest run of positions free of such pairs (up to GB_WAVES), one wavefront per user: every check, the preference scan and
+// interference graph consecutive users rarely interact (~4 % of pairs at the benchmark).  k_greedy_b takes, per step, up to
+// GB_WAVES positions free of such pairs (the steps come from k_greedy_schedule below; taking the longest contiguous run of the
+// order instead, from interaction lags of a kernel k_greedy_conflicts, was measured and removed), one wavefront per user: every check, the preference scan and
 // the sum updates of a user are wave-level (no workgroup barrier inside a step), and one full barrier per step publishes the
 // step's slots and sums.  The sums are still formed one add per address and step, in assignment order (sdp_solver.py:94).
 constexpr int GB_WAVES = 8;
@@ -320,25 +173,6 @@ __device__ __forceinline__ bool sorted_contains(const int* __restrict__ a, int n
     }
     return lo < n && a[lo] == x;
 }
-// lag[i] = smallest d in [1, GB_WAVES) such that the users at positions i and i - d interact; 0 if none.  One thread per (i, d).
-__global__ __launch_bounds__(BLOCK) void k_greedy_conflicts(int K, const GreedyHdr* __restrict__ hdr, const int* __restrict__ so_indices,
-                                                            const int* __restrict__ q_indices, int* __restrict__ lag) {
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
-    const int i = t / (GB_WAVES - 1), d = t % (GB_WAVES - 1) + 1;
-    if (i >= K || i - d < 0) return;
-    const GreedyHdr a = hdr[i - d], b = hdr[i];
-    const int* na = so_indices + a.sb;
-    const int* nb = so_indices + b.sb;
-    bool hit = sorted_contains(na, a.deg, b.k) || sorted_contains(nb, b.deg, a.k) || sorted_contains(q_indices + b.qb, b.qdeg, a.k);
-    for (int x = 0, y = 0; !hit && x < a.deg && y < b.deg;) {  // common out-neighbour: merge of the two sorted lists
-        const int u = na[x], v = nb[y];
-        if (u == v) hit = true;
-        else if (u < v) ++x;
-        else ++y;
-    }
-    if (hit) atomicMin(&lag[i], d);
-}
-
 // SCHED: the steps come from k_greedy_schedule -- `hdr` then holds GB_WAVES headers per step in schedule order (k = -1: no user for
 // this wave), `nsteps_p` the number of steps, and `lag` is not read.
 template <bool SLOT_LDS, bool SCHED = false>
@@ -514,7 +348,7 @@ __global__ __launch_bounds__(GB_WAVES * 64) void k_greedy_b(int K, int Z, const 
 // ---- the steps of k_greedy_b out of order -------------------------------------------------------------------------------------------
 // Contiguous runs end at the first pair that interacts (~6 users per step at the benchmark, 1 670 steps for 10 003 users); the users
 // behind that pair mostly interact with nobody in flight.  Any order that keeps every interacting pair in sequence order gives the
-// sequential result exactly -- two users touch common state only if they interact (k_greedy_conflicts' test), so users that do not
+// sequential result exactly -- two users touch common state only if they interact (k_greedy_cmask's test), so users that do not
 // commute, and every address still receives its additions in sequence order.  k_greedy_cmask records, for every position, which of the
 // GS_W positions before it it interacts with; k_greedy_schedule (one wavefront, once per call, shared by the attempts: the schedule does
 // not depend on what the users decide) repeatedly takes the first GB_WAVES positions of a window of GS_W whose interacting predecessors

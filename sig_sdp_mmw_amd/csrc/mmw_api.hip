@@ -48,6 +48,8 @@ namespace {
 template <typename T> BlockingLimits blocking_limits() { return BlockingLimits{blk_max_entries<T>(), (int)sizeof(BlkMeta<T>)}; }
 
 template <typename T> struct Solver final : mmw_solver {
+    const Switches sw;  // read once by mmw_create / mmw_create_from_env (switches.h); everything below this handle gets a reference
+    explicit Solver(const Switches& s) : sw(s), eng(sw), extras(sw) {}
     int device = 0;
     bool host_only = false;
     hipStream_t st = nullptr;
@@ -65,10 +67,9 @@ template <typename T> struct Solver final : mmw_solver {
     DevBuf<double> max_part, sum_part, scal, tr_part, stage64, out64;
     DevBuf<T> wH;  // Y_H / norm_H
     DevBuf<T> yun;  // the fused DUAL pass's unnormalised exponentials (see iterate_impl)
-    const bool fuse_dual = getenv("MMW_NO_FUSED_DUAL") == nullptr;
     // how far e_accu's maximum may run ahead of the fused pass's shift before its exponentials are distrusted (exp overflows T
     // near 88 / 709); MMW_DUAL_GAP is for the tests, which force the replay with it
-    const double dual_gap = getenv("MMW_DUAL_GAP") ? atof(getenv("MMW_DUAL_GAP")) : (sizeof(T) == 4 ? 60.0 : 600.0);
+    const double dual_gap = std::isnan(sw.dual_gap) ? (sizeof(T) == 4 ? 60.0 : 600.0) : sw.dual_gap;
     static constexpr int LOSS_GRID_MAX = 4096;
     // locality blocking (blocking.h)
     HostBlocking HB;
@@ -85,7 +86,6 @@ template <typename T> struct Solver final : mmw_solver {
     int sketch_done_slabs = 0;
     DevBuf<T> lval_blk;
     bool lblk_stale = false;         // lval_blk lags lval (the matrix-core kernel ran the last products)
-    bool lagged_plan = getenv("MMW_NO_LAGGED_PLAN") == nullptr;
     bool lagged_missed = false;  // an extrapolated plan of this run did not cover its matrix: the run's matrix outgrows the extrapolation, exact plans until the next reset
     DevBuf<ExpmPlan> sn_plan;        // plan (with its history) at the start of the pending chunk
     DevBuf<int> b_kbase, b_fpos, b_mdesc, b_munfixed, b_morder;  // matrix-core SpMM: its row blocks, CSR entry -> fragment image position
@@ -102,11 +102,8 @@ template <typename T> struct Solver final : mmw_solver {
     DevBuf<long long> rsfx;  // [2K] 2^-40 fixed-point totals: [0, K) row sums of the off-diagonal X, left by the matrix-core SDDMM; [K, 2K) row norms of
                              // y = exp(L/2)R from the first-order product (kernels_mfma.h).  Zeroed by every LOSS pass.
     DevBuf<double> tr1_part; // trace shares of the first-order product's workgroups (zero where none works)
-    const bool first_enabled = getenv("MMW_NO_FIRST_ORDER") == nullptr;
-    const bool first_a16_enabled = getenv("MMW_NO_FIRST_A16") == nullptr;
-    const double fv_du_scale = getenv("MMW_FV_DU_SCALE") ? atof(getenv("MMW_FV_DU_SCALE")) : 1.0;  // tests: inflates the measured rounding of the fp16 plane (forced miss)
     // the rounding of the first-order product's fp16 plane: measured by the sketch kernel (default), or the format's worst case
-    const bool fv_measure = getenv("MMW_FV_WORSTCASE") == nullptr;
+    const bool fv_measure = !sw.fv_worstcase;
     double plane_rounding() const { return fv_measure ? F16_PLANE_EXPECT : 1.02 * F16_UNIT; }
     DevBuf<unsigned short> afrag16;  // the matrix as ONE fp16 half, for the first-order product while 2 * 2^-12 absn <= tol (holes zero; an image of its own)
     bool first_a16_guess = false;    // the chunk being enqueued takes that form
@@ -135,8 +132,7 @@ template <typename T> struct Solver final : mmw_solver {
     }
     long long n_first_iters = 0;
     bool rs_last = false;    // the last iteration enqueued left rsfx for the X the next one starts from
-    const bool rs_enabled = getenv("MMW_NO_SDDMM_ROWSUMS") == nullptr;
-    const bool fv_in_sddmm = !(getenv("MMW_FV_IN_SDDMM") && atoi(getenv("MMW_FV_IN_SDDMM")) == 0);  // where the first-order certificate's workgroups run
+    const bool rs_enabled = !sw.no_sddmm_rowsums;
     long long n_rs_iters = 0, n_fused_iters = 0;  // MMW_F_DUAL_INFO
     bool sddmm_mfma = false;
     size_t afrag_n = 0;
@@ -156,7 +152,6 @@ template <typename T> struct Solver final : mmw_solver {
     double emax_h = 0.0;
     int emax_enq_iter = -1, emax_iter = -1;  // iteration count the enqueued / fetched maximum violation belongs to
     bool exact_plans_only = false;  // a cautious second attempt at a discarded chunk is running (settle)
-    const bool cautious_replay = !(getenv("MMW_CAUTIOUS_REPLAY") && atoi(getenv("MMW_CAUTIOUS_REPLAY")) == 0);
     ExpmEngine<T> eng;
     Extras<T> extras;
     KernelTimers kt;
@@ -192,7 +187,6 @@ template <typename T> struct Solver final : mmw_solver {
     int init(int dev, int32_t K_, int32_t Z_, int32_t rr, double eta_, int32_t nit_, const int32_t* Sp, const int32_t* Si,
              const double* Sx, const int32_t* Qp, const int32_t* Qi, const double* Qx, const double* h) {
         device = dev;
-        const bool verbose = getenv("MMW_VERBOSE") != nullptr;
         auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_0 = tnow();
         // The first kernel launch of a process loads the library's code object (~0.15 s): start it on a helper thread now, under
@@ -212,11 +206,10 @@ template <typename T> struct Solver final : mmw_solver {
         {   // whether the matrix-core blocking is wanted depends on the block's padded width only
             BlockLayout lay0;
             std::string lerr;
-            blk_want_mf = sizeof(T) == 4 && !getenv("MMW_NO_MFMA") && make_layout(Z_ * rr, V16<T>::N, lay0, lerr) == MMW_OK &&
+            blk_want_mf = sizeof(T) == 4 && !sw.no_mfma && make_layout(Z_ * rr, V16<T>::N, lay0, lerr) == MMW_OK &&
                           (double)K_ * lay0.Dpad * 4.0 < 4.0e9;
         }
-        const char* blk_env = getenv("MMW_BLOCKING");
-        const bool start_blk = !host_only && !(blk_env && blk_env[0] == '0');
+        const bool start_blk = !host_only && !sw.no_blocking;
         double t_struct = 0.0;
         std::string err = build_pattern(H, K_, Z_, Sp, Si, Sx, Qp, Qi, Qx, h, [&]() {
             t_struct = tnow();
@@ -230,7 +223,7 @@ template <typename T> struct Solver final : mmw_solver {
         if (host_only) {  // device == -1: pattern inspection only (CPU tests of the host logic)
             std::string lerr;
             if (make_layout(D, V16<T>::N, eng.lay, lerr) != MMW_OK) return fail(MMW_ERR_ARG, lerr);
-            if (getenv("MMW_HOST_BLOCKING")) {  // developer aid: build the locality blocking on the host and print its statistics
+            if (live_switch(LIVE_HOST_BLOCKING)) {  // developer aid: build the locality blocking on the host and print its statistics
                 const double t0 = tnow();
                 build_blocking(HB, K, H.l_indptr, H.l_indices, blocking_limits<T>());
                 build_sd_tables(HB, K, H.l_indptr, H.l_indices);
@@ -239,15 +232,15 @@ template <typename T> struct Solver final : mmw_solver {
                         (double)HB.un_cols.size() / std::max(1, HB.nb()), HB.reuse, (long long)HB.nent, (long long)H.nnzL(),
                         100.0 * ((double)HB.nent / (double)H.nnzL() - 1.0), HB.sd2_rounds);
                 const double t1 = tnow();
-                build_mfma_blocking(HB, K, H.l_indptr, H.l_indices, getenv("MMW_MF_ROWS") ? atoi(getenv("MMW_MF_ROWS")) : 64);
+                build_mfma_blocking(HB, K, H.l_indptr, H.l_indices, sw.mf_rows, sw.mf_union_cap);
                 fprintf(stderr, "[mmw] matrix-core blocking %.1f ms: ok %d blocks %d rows/block %.1f reuse %.2f row tiles %d k-steps %d\n", (tnow() - t1) * 1e3,
                         (int)HB.fits_mfma, HB.nbm(), (double)K / std::max(1, HB.nbm()), HB.m_reuse, HB.mfma_mt, HB.kbase.empty() ? 0 : HB.kbase.back());
-                if (getenv("MMW_HOST_BLOCKING_HIST")) {  // k-steps of every block, in launch order
+                if (live_switch(LIVE_HOST_BLOCKING_HIST)) {  // k-steps of every block, in launch order
                     for (int b = 0; b < HB.nbm(); ++b) fprintf(stderr, "%d:%d ", HB.m_desc[(size_t)b * 8 + 1], HB.kbase[b + 1] - HB.kbase[b]);
                     fprintf(stderr, "\n");
                 }
             }
-            if (getenv("MMW_CHECK_BLOCKING")) {  // CPU tests: build the blocking and check its invariants
+            if (sw.check_blocking) {  // CPU tests: build the blocking and check its invariants
                 const BlockingLimits lim = blocking_limits<T>();
                 if (HB.order.empty()) build_blocking(HB, K, H.l_indptr, H.l_indices, lim);
                 build_sd_tables(HB, K, H.l_indptr, H.l_indices);
@@ -255,7 +248,7 @@ template <typename T> struct Solver final : mmw_solver {
                     const std::string berr = verify_blocking(HB, K, H.l_indptr, H.l_indices, lim);
                     if (!berr.empty()) return fail(MMW_ERR_STATE, "blocking invariant violated: " + berr);
                     for (int mrows : {64, 32, 7}) {
-                        build_mfma_blocking(HB, K, H.l_indptr, H.l_indices, mrows);
+                        build_mfma_blocking(HB, K, H.l_indptr, H.l_indices, mrows, sw.mf_union_cap);
                         const std::string merr = verify_mfma_blocking(HB, K, H.l_indptr, H.l_indices);
                         if (!merr.empty()) return fail(MMW_ERR_STATE, "blocking invariant violated: " + merr);
                     }
@@ -352,19 +345,14 @@ template <typename T> struct Solver final : mmw_solver {
         // prefix sums of the count pass
         std::vector<int32_t> st_ptr(K + 1, 0), gu_ptr(K + 1, 0), qu_ptr(K + 1, 0), so_ptr(K + 1, 0);
         H.l_indptr.assign(K + 1, 0);
-        int maxdeg = 1, maxq = 1;
         for (int k = 0; k < K; ++k) {
             H.l_indptr[k + 1] = H.l_indptr[k] + c6[k];
             st_ptr[k + 1] = st_ptr[k] + c6[(size_t)K + k];
             gu_ptr[k + 1] = gu_ptr[k] + c6[(size_t)2 * K + k];
             qu_ptr[k + 1] = qu_ptr[k] + c6[(size_t)3 * K + k];
-            const int so_len = (E.h_sptr[k + 1] - E.h_sptr[k]) - c6[(size_t)4 * K + k];
-            so_ptr[k + 1] = so_ptr[k] + so_len;
-            maxdeg = std::max(maxdeg, so_len);
-            maxq = std::max(maxq, E.h_qptr[k + 1] - E.h_qptr[k]);
+            so_ptr[k + 1] = so_ptr[k] + (E.h_sptr[k + 1] - E.h_sptr[k]) - c6[(size_t)4 * K + k];
             if ((int64_t)H.l_indptr[k] + c6[k] > (int64_t)INT32_MAX) return fail(MMW_ERR_ARG, "mmw_create_from_env: pattern too large for int32 indexing");
         }
-        env_maxdeg = maxdeg; env_maxq = maxq;
         const size_t nnz = (size_t)H.l_indptr[K], nst = (size_t)st_ptr[K], ng = (size_t)gu_ptr[K], na = (size_t)qu_ptr[K];
         H.n_st = (int64_t)nst; H.n_gain = (int64_t)ng; H.n_asso = (int64_t)na;
         H.st_indptr = st_ptr;
@@ -389,11 +377,10 @@ template <typename T> struct Solver final : mmw_solver {
         {   // whether the matrix-core blocking is wanted depends on the block's padded width only
             BlockLayout lay0;
             std::string lerr;
-            blk_want_mf = sizeof(T) == 4 && !getenv("MMW_NO_MFMA") && make_layout(Z_ * rr, V16<T>::N, lay0, lerr) == MMW_OK && (double)K * lay0.Dpad * 4.0 < 4.0e9;
+            blk_want_mf = sizeof(T) == 4 && !sw.no_mfma && make_layout(Z_ * rr, V16<T>::N, lay0, lerr) == MMW_OK && (double)K * lay0.Dpad * 4.0 < 4.0e9;
         }
-        const char* blk_env = getenv("MMW_BLOCKING");
-        if (!(blk_env && blk_env[0] == '0')) {
-            if (!getenv("MMW_ENV_RCM")) {  // (MMW_ENV_RCM=1: the pattern-only order of the CSR entry point, for comparisons)
+        if (!sw.no_blocking) {
+            if (!sw.env_rcm) {  // (MMW_ENV_RCM=1: the pattern-only order of the CSR entry point, for comparisons)
                 HB.rcm_cache = spatial_order(K, E.h_sta, 64);
                 HB.grow = false;
             }
@@ -428,10 +415,9 @@ template <typename T> struct Solver final : mmw_solver {
         env_src = nullptr;
         return rc;
     }
-    int env_maxdeg = 1, env_maxq = 1;
     // the rounding's view of the state, from the generator's own CSR of S_gain (diagonal dropped) and Q
     int init_extras_env(EnvDevice& E) {
-        MMW_TRY(extras.init_device(st, K, &kt, env_maxdeg, env_maxq));
+        MMW_TRY(extras.init_device(st, K, &kt));
         std::vector<int32_t> so_ptr_h((size_t)K + 1);
         MMW_TRY(copy_d2h(so_ptr_h.data(), envl.so_ptr.p, so_ptr_h.size() * sizeof(int32_t), st));
         const size_t nso = (size_t)so_ptr_h[K];
@@ -450,7 +436,7 @@ template <typename T> struct Solver final : mmw_solver {
 
     // ---- everything after the pattern is on the device: the iterate's buffers, the engine, the blockings, the rounding side
     int init_common(double t_0, double t_1, double t_struct, EnvDevice* env) {
-        const bool verbose = getenv("MMW_VERBOSE") != nullptr;
+        const bool verbose = live_switch(LIVE_VERBOSE);
         auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const size_t nnz = (size_t)H.nnzL(), C = (size_t)H.C();
         MMW_TRY(lval.alloc(nnz)); MMW_TRY(xval.alloc(nnz)); MMW_TRY(xavg.alloc(nnz));
@@ -482,7 +468,7 @@ template <typename T> struct Solver final : mmw_solver {
         BlkDev B;
         B.nb = HB.nb(); B.rowptr = b_rowptr.p; B.order = b_order.p; B.un_ptr = b_unptr.p; B.un_cols = b_uncols.p;
         B.bptr = b_bptr.p; B.lidx = b_lidx.p; B.self_li = b_selfli.p; B.desc = b_desc.p; B.un_fixed = b_unfixed.p;
-        B.half_tile = HB.fits_half_tile && (double)K * eng.lay.Dpad * sizeof(T) < 4.0e9 && !getenv("MMW_FULL_TILE");  // 32-bit byte offsets
+        B.half_tile = HB.fits_half_tile && (double)K * eng.lay.Dpad * sizeof(T) < 4.0e9 && !sw.full_tile;  // 32-bit byte offsets
         return B;
     }
     // Buffers the loop, the factor and the rounding would otherwise allocate on first use (hipMalloc is a synchronous driver call
@@ -516,9 +502,8 @@ template <typename T> struct Solver final : mmw_solver {
         bool rows_ok = true;
         for (int k = 0; k < Kp && rows_ok; ++k) rows_ok = H.l_indptr[k + 1] - H.l_indptr[k] <= BLK_UNION;
         if (rows_ok && HB.rcm_cache.size() != (size_t)Kp) HB.rcm_cache = rcm_order(Kp, H.l_indptr, H.l_indices);  // (a handle made from the generator brings a spatial order)
-        const int mrows = getenv("MMW_MF_ROWS") ? atoi(getenv("MMW_MF_ROWS")) : 64;
         std::thread mf_thread;
-        if (blk_want_mf && rows_ok) mf_thread = std::thread([&]() { build_mfma_blocking(HB, Kp, H.l_indptr, H.l_indices, std::min(64, std::max(1, mrows))); });
+        if (blk_want_mf && rows_ok) mf_thread = std::thread([&]() { build_mfma_blocking(HB, Kp, H.l_indptr, H.l_indices, std::min(64, std::max(1, sw.mf_rows)), sw.mf_union_cap); });
         build_blocking(HB, Kp, H.l_indptr, H.l_indices, blocking_limits<T>());
         if (mf_thread.joinable()) mf_thread.join();
     }
@@ -540,7 +525,7 @@ template <typename T> struct Solver final : mmw_solver {
             MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sddmm_blk<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
             sddmm_blk = true;
         }
-        if ((double)K * eng.lay.Dpad * sizeof(T) < 4.0e9 && !getenv("MMW_FULL_TILE")) {
+        if ((double)K * eng.lay.Dpad * sizeof(T) < 4.0e9 && !sw.full_tile) {
             MMW_TRY(b_sd2ptr.upload(HB.sd2_ptr, st)); MMW_TRY(b_sd2ab.upload(HB.sd2_ab, st)); MMW_TRY(b_sd2epos.upload(HB.sd2_epos, st));
             {   // Work items.  A workgroup is a latency chain whose length is its number of rounds, and the launch lasts as long
                 // as its longest workgroup; the resident slots the row blocks leave free are used to cut the longest items in two
@@ -576,18 +561,17 @@ template <typename T> struct Solver final : mmw_solver {
         return MMW_OK;
     }
     int setup_blocking() {
-        const char* env = getenv("MMW_BLOCKING");
-        if (env && env[0] == '0') blocking_mode = 0;
+        if (sw.no_blocking) blocking_mode = 0;
         if (!blocking_mode) return MMW_OK;
         if (blk_thread.joinable()) blk_thread.join();  // started under the pattern build (init)
         else host_blockings();
         {
             const bool want_mf = blk_want_mf;
-            if (want_mf && getenv("MMW_VERBOSE"))
+            if (want_mf && live_switch(LIVE_VERBOSE))
                 fprintf(stderr, "[mmw] matrix-core blocking: ok %d blocks %d rows/block %.1f reuse %.2f row tiles %d k-steps %d\n", (int)HB.fits_mfma, HB.nbm(),
                         (double)K / std::max(1, HB.nbm()), HB.m_reuse, HB.mfma_mt, HB.kbase.empty() ? 0 : HB.kbase.back());
         }
-        if (getenv("MMW_VERBOSE"))
+        if (live_switch(LIVE_VERBOSE))
             fprintf(stderr, "[mmw] blocking: usable %d half-tile %d blocks %d rows/block %.1f union/block %.1f entries %lld (nnz %lld, +%.1f%% padding) sd_max %d\n",
                     (int)HB.usable, (int)HB.fits_half_tile, HB.nb(), (double)K / std::max(1, HB.nb()), (double)HB.un_cols.size() / std::max(1, HB.nb()),
                     (long long)HB.nent, (long long)H.nnzL(), 100.0 * ((double)HB.nent / (double)H.nnzL() - 1.0), HB.sd_max);
@@ -615,7 +599,7 @@ template <typename T> struct Solver final : mmw_solver {
             eng.mf.kbase = b_kbase.p;
             eng.mf.afrag = afrag.p;
             eng.mf_mt = HB.mfma_mt;
-            if (!getenv("MMW_NO_MFMA_SDDMM")) {
+            if (!sw.no_mfma_sddmm) {
                 MMW_TRY(b_tbase.upload(HB.m_tbase, st)); MMW_TRY(b_tptr.upload(HB.m_tptr, st)); MMW_TRY(b_trc.upload(HB.m_trc, st));
                 MMW_TRY(b_e2w.upload(HB.m_e2w, st));
                 {   // slot of every association pair: the slot of its upper entry
@@ -752,6 +736,70 @@ template <typename T> struct Solver final : mmw_solver {
                         wgdur / std::max(cnt, 1) * 0.01, t1 / ev.size() * 0.01, t2 / ev.size() * 0.01, t3 / ev.size() * 0.01);
         return MMW_OK;
     }
+    // MMW_DUAL_STAMPS: per-wave phase clocks of one fused DUAL launch (k_dual_h) of `gd` workgroups
+    int dump_dual_stamps(const unsigned long long* dev, int gd) {
+        std::vector<unsigned long long> h((size_t)gd * WAVES_PER_BLOCK * 8);
+        MMW_HIP(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        double sum[5] = {0}, slow[5] = {0};
+        std::vector<std::pair<unsigned long long, size_t>> byl;
+        int nw = 0;
+        for (size_t w = 0; w < h.size() / 8; ++w) {
+            const unsigned long long* q = &h[w * 8];
+            if (!q[5]) continue;
+            ++nw;
+            const unsigned long long p1 = q[1] ? q[1] : q[0], p2 = q[2] ? q[2] : p1, p3 = q[3], p4 = q[4];
+            sum[0] += (double)(p1 - q[0]); sum[1] += (double)(p2 - p1); sum[2] += (double)(p3 - p2); sum[3] += (double)(p4 - p3); sum[4] += (double)(q[5] - p4);
+            byl.push_back({q[5] - q[0], w});
+        }
+        std::sort(byl.rbegin(), byl.rend());
+        const size_t top = std::max<size_t>(1, byl.size() / 20);
+        for (size_t i = 0; i < top && i < byl.size(); ++i) {
+            const unsigned long long* q = &h[byl[i].second * 8];
+            const unsigned long long p1 = q[1] ? q[1] : q[0], p2 = q[2] ? q[2] : p1;
+            slow[0] += (double)(p1 - q[0]); slow[1] += (double)(p2 - p1); slow[2] += (double)(q[3] - p2); slow[3] += (double)(q[4] - q[3]); slow[4] += (double)(q[5] - q[4]);
+        }
+        if (nw)
+            fprintf(stderr, "[dual stamps] %d workgroups, %d waves; clocks per wave: row pointers %.0f, rows (entries + gathers + sums) %.0f, rows' tails %.0f, violation part %.0f, fold + stores %.0f; "
+                            "slowest twentieth: %.0f / %.0f / %.0f / %.0f / %.0f\n",  // (the counters of different XCDs share no origin: no launch-wide span)
+                    gd, nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw, slow[0] / top, slow[1] / top, slow[2] / top, slow[3] / top, slow[4] / top);
+        return MMW_OK;
+    }
+    // MMW_SD_STAMPS: per-wave phase clocks of one matrix-core SDDMM launch (k_sddmm_mfma) of `grid` workgroups, `n_st` stamps
+    int dump_sddmm_stamps(const unsigned long long* dev, size_t n_st, dim3 grid) {
+        std::vector<unsigned long long> h(n_st);
+        MMW_HIP(hipMemcpyAsync(h.data(), dev, n_st * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        double sum[8] = {0}, life_max = 0;
+        int nw = 0;
+        for (size_t w = 0; w < n_st / 8; ++w) {
+            const unsigned long long* q = &h[w * 8];
+            if (!q[4]) continue;
+            ++nw;
+            for (int k = 0; k < 8; ++k) sum[k] += (double)q[k];
+            life_max = std::max(life_max, (double)q[4]);
+        }
+        {   // the slowest twentieth of the waves: where their time went
+            std::vector<std::pair<unsigned long long, size_t>> byl;
+            for (size_t w = 0; w < n_st / 8; ++w) if (h[w * 8 + 4]) byl.push_back({h[w * 8 + 4], w});
+            std::sort(byl.rbegin(), byl.rend());
+            const size_t top = std::max<size_t>(1, byl.size() / 20);
+            double ts[8] = {0};
+            for (size_t i = 0; i < top && i < byl.size(); ++i) for (int k = 0; k < 8; ++k) ts[k] += (double)h[byl[i].second * 8 + k];
+            if (!byl.empty())
+                fprintf(stderr, "[sddmm stamps] slowest %zu waves: prologue %.0f, wait+barrier %.0f, issue %.0f, reads+products %.0f, sums %.0f, stores %.0f, lifetime %.0f; by (wg.y): ", top,
+                        ts[0] / top, ts[1] / top, ts[2] / top, ts[3] / top, ts[5] / top, ts[7] / top, ts[4] / top);
+            int cnt[8] = {0};
+            for (size_t i = 0; i < top && i < byl.size(); ++i) { const size_t wg = byl[i].second / (size_t)(4 * HB.mfma_mt); const unsigned y = (unsigned)(wg / grid.x); if (y < 8) ++cnt[y]; }
+            for (unsigned y = 0; y < grid.y && y < 8; ++y) fprintf(stderr, "%d ", cnt[y]);
+            fprintf(stderr, "\n");
+        }
+        if (nw)
+            fprintf(stderr, "[sddmm stamps] grid %u x %u, %d working waves; shader clocks per wave: prologue %.0f, wait+barrier %.0f, issue %.0f, reads+products %.0f, "
+                            "row/column sums %.0f, tile+stores+atomics %.0f, lifetime %.0f (max %.0f)\n",
+                    grid.x, grid.y, nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[5] / nw, sum[7] / nw, sum[4] / nw, life_max);
+        return MMW_OK;
+    }
     // SpMM micro-benchmark on the current L values: Tm = 0.5 * L * start_block, `reps` launches
     int bench_spmm(int blocked, int reps, double* avg_us) override {
         if (host_only) return fail(MMW_ERR_STATE, "host-only handle");
@@ -764,7 +812,7 @@ template <typename T> struct Solver final : mmw_solver {
         if (blocked == 2 && !eng.use_mfma) return fail(MMW_ERR_STATE, "no matrix-core SpMM for this handle (fp32, blocks of <= 32 rows)");
         eng.use_mfma = blocked == 2;
         DevBuf<unsigned long long> stamps;
-        const bool want_stamps = blocked && getenv("MMW_STAMPS");
+        const bool want_stamps = blocked && live_switch(LIVE_STAMPS);
         if (want_stamps) {
             MMW_TRY(stamps.alloc((size_t)16 * 8192));
             MMW_HIP(hipMemsetAsync(stamps.p, 0, (size_t)16 * 8192 * sizeof(unsigned long long), st));
@@ -772,7 +820,7 @@ template <typename T> struct Solver final : mmw_solver {
         hipEvent_t e0, e1;
         MMW_HIP(hipEventCreate(&e0));
         MMW_HIP(hipEventCreate(&e1));
-        const bool lz = getenv("MMW_BENCH_LANCZOS") != nullptr;  // time the Lanczos epilogue (alpha partials) instead of the plain product
+        const bool lz = live_switch(LIVE_BENCH_LANCZOS);  // time the Lanczos epilogue (alpha partials) instead of the plain product
         const unsigned short* pl = nullptr;
         if (blocked == 2) {  // the planes are the producer's job: outside the timed launches
             eng.planes_ready[0] = false;
@@ -781,7 +829,7 @@ template <typename T> struct Solver final : mmw_solver {
         }
         // MMW_BENCH_FIRST: the first-order product as the loop launches it (fp16 operands and its whole epilogue; the operands are whatever the
         // last iteration left -- only the time is of interest)
-        const bool fo = blocked == 2 && getenv("MMW_BENCH_FIRST") != nullptr && sizeof(T) == 4 && rsfx.p != nullptr;
+        const bool fo = blocked == 2 && live_switch(LIVE_BENCH_FIRST) && sizeof(T) == 4 && rsfx.p != nullptr;
         int ntr1 = 0;
         if (fo) {
             if (xh_planes.n < 2 * eng.bs) MMW_TRY(xh_planes.alloc(2 * eng.bs));
@@ -863,7 +911,7 @@ template <typename T> struct Solver final : mmw_solver {
         MMW_TRY(sync());
         kt.on = enabled != 0;
         kt_shipped = enabled == 2;  // 2: time the launches of the shipped path (chunks without readback, riding workgroups) as they are
-        kt.attach = kt_shipped && !getenv("MMW_KT_MARKERS");  // ... the matrix-core product by the events its launch carries itself
+        kt.attach = kt_shipped && !sw.kt_markers;  // ... the matrix-core product by the events its launch carries itself
         eng.kt_exact = kt.on && !kt_shipped;
         kt.clear();
         return MMW_OK;
@@ -1081,7 +1129,7 @@ template <typename T> struct Solver final : mmw_solver {
         return MMW_OK;
     }
     void say_replay(int viol, const char* how) const {
-        if (!getenv("MMW_VERBOSE")) return;
+        if (!live_switch(LIVE_VERBOSE)) return;
         const ExpmPlan& p = eng.last;
         union { unsigned u; float f; } c1, fe;
         c1.u = p.conv[std::max(0, std::min(p.m_eff, MAX_ORDER))]; fe.u = p.first_est;
@@ -1105,7 +1153,7 @@ template <typename T> struct Solver final : mmw_solver {
         if (viol & VIOL_LAGGED) lagged_missed = true;  // (er-50k: a second chunk missed the same way 32 iterations later)
         say_replay(viol, "discarded");
         MMW_TRY(restore_pending());
-        if (cautious_replay && !operands_only && eng.method == MMW_EXPM_LANCZOS && pend_n > 1) {
+        if (sw.cautious_replay && !operands_only && eng.method == MMW_EXPM_LANCZOS && pend_n > 1) {
             first_guess = false;
             first_a16_guess = false;
             m_guess = std::min(eng.max_order, std::max(std::max(eng.last.m_apriori, eng.last.m_eff), m_guess) + 1);
@@ -1135,7 +1183,7 @@ template <typename T> struct Solver final : mmw_solver {
         if (n < 0) return fail(MMW_ERR_ARG, "n must be >= 0");
         MMW_TRY(settle());
         if (iter + n > nit) return fail(MMW_ERR_STATE, "mmw_iterate: more iterations than announced to mmw_create/mmw_reset");
-        const bool optimistic = randv == nullptr && n > 1 && !kt_exact() && !getenv("MMW_SYNC_PLAN");  // profiling mode 1 counts exact launches
+        const bool optimistic = randv == nullptr && n > 1 && !kt_exact() && !sw.sync_plan;  // profiling mode 1 counts exact launches
         if (!optimistic) {
             chain_ok = false;
             MMW_TRY(iterate_impl(n, randv, seed, false));
@@ -1161,7 +1209,7 @@ template <typename T> struct Solver final : mmw_solver {
             if (plan_seen) m_guess = next_launch_order(chunk);  // before the first readback of a run: the default set by reset()
             first_guess = plan_seen && first_order_ok(chunk);  // (requires that the last plan read back stopped after one step)
             if (first_guess) m_guess = 1;
-            first_a16_guess = first_guess && first_a16_enabled && afrag16.p != nullptr && first_order_ok(chunk, true);
+            first_a16_guess = first_guess && !sw.no_first_a16 && afrag16.p != nullptr && first_order_ok(chunk, true);
             if (warm_fresh) {  // the plan at hand belongs to the previous probe's slot count: one spare step, no first-order form
                 m_guess = std::min(eng.max_order, std::max(2, eng.last.m_eff + 1));
                 first_guess = false;
@@ -1202,7 +1250,7 @@ template <typename T> struct Solver final : mmw_solver {
     // row-sum bound absn, which grows linearly.  a16: the chunk would read the matrix as one half.
     bool first_order_ok(int ahead, bool a16 = false) const {
         const ExpmPlan& p = eng.last;
-        if (!first_enabled || sizeof(T) != 4 || !p.apost || p.m_eff != 1 || p.first_est == 0u) return false;
+        if (sw.no_first_order || sizeof(T) != 4 || !p.apost || p.m_eff != 1 || p.first_est == 0u) return false;
         union { unsigned u; float f; } e;
         e.u = p.first_est;
         const double g1 = growth_ratio(ahead), absn_g = p.absn * g1;
@@ -1253,12 +1301,12 @@ template <typename T> struct Solver final : mmw_solver {
     // the exact one, which must not cost a second product: on graphs without locality a product is 10x the two kernels saved).
     bool lagged_ok() const {
         const ExpmPlan& p = eng.last;
-        if (!lagged_plan || lagged_missed || !p.apost || p.m_eff != 1) return false;
+        if (sw.no_lagged_plan || lagged_missed || !p.apost || p.m_eff != 1) return false;
         union { unsigned u; float f; } e;
         e.u = p.conv[1];
         return (double)e.f <= p.tol / 2.0;
     }
-    int sketch_slabs() const { static const int cap = getenv("MMW_SK_SLABS") ? atoi(getenv("MMW_SK_SLABS")) : 256; return std::min(grid_rows(K), cap); }  // few slabs for the start-norm reduction
+    int sketch_slabs() const { return std::min(grid_rows(K), sw.sk_slabs); }  // few slabs for the start-norm reduction
     int launch_sketch(hipStream_t s, uint64_t seed, uint32_t it, bool planes_f16 = false) {
         const bool lz = eng.method == MMW_EXPM_LANCZOS;
         const int Dpad = eng.lay.Dpad;
@@ -1282,12 +1330,10 @@ template <typename T> struct Solver final : mmw_solver {
         // the DUAL pass's grid: its workgroups stride over the row pairs, and the slabs it leaves (maxima, softmax sums, |L| row sums) are
         // folded by one workgroup afterwards.  One resident round of workgroups (five per CU at the pass's 86 registers) instead of one per
         // eight rows: half the slabs to fold and no second round's tail -- DUAL 21.0 -> 20.0 us per step at the benchmark (640: 22.3; 1920: 20.2)
-        static const int dual_cap = getenv("MMW_DUAL_GRID") ? atoi(getenv("MMW_DUAL_GRID")) : 0;
-        const int gd = std::min(gr, dual_cap > 0 ? dual_cap : 5 * device_cus());
+        const int gd = std::min(gr, 5 * device_cus());
         const int C = (int)H.C();
         const int gc = grid_elems((size_t)C);
-        static const int loss_grid_cap = getenv("MMW_LOSS_GRID") ? atoi(getenv("MMW_LOSS_GRID")) : LOSS_GRID_MAX;
-        const int gl = (int)std::min<size_t>(((size_t)H.nnzL() + BLOCK - 1) / BLOCK, (size_t)std::max(1, std::min(loss_grid_cap, LOSS_GRID_MAX)));  // LOSS: one thread per stored entry, grid-stride
+        const int gl = (int)std::min<size_t>(((size_t)H.nnzL() + BLOCK - 1) / BLOCK, (size_t)LOSS_GRID_MAX);  // LOSS: one thread per stored entry, grid-stride
         const int Dpad = eng.lay.Dpad;
         int m_launch = optimistic ? m_guess : 0;
         // from the plan the last settled chunk ended on; not in the first chunk after a warm restart: with another slot count the matrix grows
@@ -1306,7 +1352,7 @@ template <typename T> struct Solver final : mmw_solver {
         rs_last = false;
         // drawing the next sketch in extra workgroups of the SDDMM launch paid off with 8-wave SDDMM workgroups (+3.7 %); with
         // 16-wave ones (two per CU, every wave slot taken) it costs 1.5 %, so it is opt-in
-        const bool fuse_sketch = !kt_exact() && !timing && getenv("MMW_FUSED_SKETCH") != nullptr;
+        const bool fuse_sketch = !kt_exact() && !timing && sw.fused_sketch;
         sketch_done_for = -1;  // whatever an earlier batch left in the start block is not trusted
         for (int it = 0; it < n; ++it) {
             const int acc = (iter + 1 < nit) ? 1 : 0;  // the last X / Y are not averaged (mmw.py:77-78,203)
@@ -1330,13 +1376,13 @@ template <typename T> struct Solver final : mmw_solver {
             // Inside a chunk (not its first iteration) the softmax rides in k_dual_h, shifted by the previous iteration's maximum
             // instead of this one's: one small workgroup then folds the sums, and the LOSS pass normalises where it reads
             // (kernels_loop.h, k_dual_h / k_dual_scal).  Two launches of the dependent chain fewer.
-            const bool fused_dual = optimistic && (it > 0 || chain) && fuse_dual;
+            const bool fused_dual = optimistic && (it > 0 || chain) && !sw.no_fused_dual;
             if (fused_dual) {
                 ++n_fused_iters;
                 if (yun.n < (size_t)C) MMW_TRY(yun.alloc((size_t)C));
                 // MMW_DUAL_STAMPS=1 (developer aid): per-wave phase clocks of the last iteration's launch, printed to stderr
                 DevBuf<unsigned long long> dh_stamps;
-                const bool want_dst = it + 1 == n && getenv("MMW_DUAL_STAMPS") != nullptr;
+                const bool want_dst = it + 1 == n && live_switch(LIVE_DUAL_STAMPS);
                 if (want_dst) {
                     MMW_TRY(dh_stamps.alloc((size_t)gd * WAVES_PER_BLOCK * 8));
                     MMW_HIP(hipMemsetAsync(dh_stamps.p, 0, (size_t)gd * WAVES_PER_BLOCK * 8 * sizeof(unsigned long long), st));
@@ -1344,33 +1390,7 @@ template <typename T> struct Solver final : mmw_solver {
                 hipLaunchKernelGGL((k_dual_h<T>), dim3(gd), dim3(BLOCK), 0, st, P, rsum.p, e_this.p, e_accu.p, eta, max_part.p,
                                    (const T*)(lagged_it ? lval.p : nullptr), 0.5, eng.row_part.p, (const double*)(scal.p + 4), yun.p, wH.p, sum_part.p,
                                    rs_it, xcur, FirstVerify{}, dh_stamps.p);
-                if (want_dst) {
-                    std::vector<unsigned long long> h((size_t)gd * WAVES_PER_BLOCK * 8);
-                    MMW_HIP(hipMemcpyAsync(h.data(), dh_stamps.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                    MMW_HIP(hipStreamSynchronize(st));
-                    double sum[5] = {0}, slow[5] = {0};
-                    std::vector<std::pair<unsigned long long, size_t>> byl;
-                    int nw = 0;
-                    for (size_t w = 0; w < h.size() / 8; ++w) {
-                        const unsigned long long* q = &h[w * 8];
-                        if (!q[5]) continue;
-                        ++nw;
-                        const unsigned long long p1 = q[1] ? q[1] : q[0], p2 = q[2] ? q[2] : p1, p3 = q[3], p4 = q[4];
-                        sum[0] += (double)(p1 - q[0]); sum[1] += (double)(p2 - p1); sum[2] += (double)(p3 - p2); sum[3] += (double)(p4 - p3); sum[4] += (double)(q[5] - p4);
-                        byl.push_back({q[5] - q[0], w});
-                    }
-                    std::sort(byl.rbegin(), byl.rend());
-                    const size_t top = std::max<size_t>(1, byl.size() / 20);
-                    for (size_t i = 0; i < top && i < byl.size(); ++i) {
-                        const unsigned long long* q = &h[byl[i].second * 8];
-                        const unsigned long long p1 = q[1] ? q[1] : q[0], p2 = q[2] ? q[2] : p1;
-                        slow[0] += (double)(p1 - q[0]); slow[1] += (double)(p2 - p1); slow[2] += (double)(q[3] - p2); slow[3] += (double)(q[4] - q[3]); slow[4] += (double)(q[5] - q[4]);
-                    }
-                    if (nw)
-                        fprintf(stderr, "[dual stamps] %d workgroups, %d waves; clocks per wave: row pointers %.0f, rows (entries + gathers + sums) %.0f, rows' tails %.0f, violation part %.0f, fold + stores %.0f; "
-                                        "slowest twentieth: %.0f / %.0f / %.0f / %.0f / %.0f\n",  // (the counters of different XCDs share no origin: no launch-wide span)
-                                gd, nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw, slow[0] / top, slow[1] / top, slow[2] / top, slow[3] / top, slow[4] / top);
-                }
+                if (want_dst) MMW_TRY(dump_dual_stamps(dh_stamps.p, gd));
                 hipLaunchKernelGGL(k_dual_scal, dim3(1 + fv.nwg), dim3(DSCAL_THREADS), 0, st, sum_part.p, max_part.p, gd, scal.p,
                                    dual_gap, eng.viol_d.p, fv);
             } else {
@@ -1398,7 +1418,7 @@ template <typename T> struct Solver final : mmw_solver {
             // (with the per-iteration phase events of mmw_set_timing on as well: the draw then counts into the LOSS phase's microseconds
             // instead of the exponential's -- the reference draws inside mmw.py:172-181 -- and the iteration's total is unchanged; a launch of
             // its own cost the class path 14 us per iteration)
-            if (!randv && !sketch_have && !kt_exact() && !getenv("MMW_NO_LOSS_SKETCH")) {
+            if (!randv && !sketch_have && !kt_exact() && !sw.no_loss_sketch) {
                 skl.nblocks = sketch_slabs(); skl.K = K; skl.D = D; skl.seed = seed; skl.iter = (uint32_t)iter;
                 skl.R = eng.start_block();
                 skl.colsq_part = lz_m ? eng.partial_sq.p : nullptr;
@@ -1452,7 +1472,7 @@ template <typename T> struct Solver final : mmw_solver {
                 }
             }
             // inside a chunk only the SDDMM reads X_half; the chunk's last iteration leaves the fp32 copy the API hands out
-            eng.planes_only = eng.out_planes != nullptr && optimistic && it + 1 < n && !getenv("MMW_KEEP_XHALF");
+            eng.planes_only = eng.out_planes != nullptr && optimistic && it + 1 < n && !sw.keep_xhalf;
             eng.rownorm_d = drow.p;  // the Lanczos combination also emits the row norms and the trace slabs
             eng.rownorm_part = tr_part.p;
             eng.plan_iter = age();
@@ -1488,21 +1508,20 @@ template <typename T> struct Solver final : mmw_solver {
                         fv_now.u2 = eng.partial_sq.p; fv_now.du2 = fv_measure ? eng.partial_du.p : nullptr; fv_now.rows = K; fv_now.n_u2 = eng.npart_start; fv_now.Dpad = Dpad;
                         fv_now.nwg = Dpad / FV_COLS;
                         fv_now.cA = first_a16_guess ? F16_UNIT : F16_CA_TWO;
-                        fv_now.du_scale = fv_du_scale;
+                        fv_now.du_scale = sw.fv_du_scale;
                     }
-                    const bool fv_rides = first_it && fv_in_sddmm;
+                    const bool fv_rides = first_it && sw.fv_in_sddmm;
                     const dim3 grid((HB.nbm() + 7) / 8 * 8 + (fv_rides ? 8 : 0), (HB.m_ntile_max + SDM_GT - 1) / SDM_GT);
                     SM.tmask = b_tmask.p;
                     long long* rs_out = rs_zeroed ? rsfx.p : nullptr;  // this iteration's LOSS pass zeroed the totals
                     // MMW_SD_STAMPS=1 (developer aid): per-wave phase clocks of the last iteration's launch, printed to stderr
                     DevBuf<unsigned long long> sdm_stamps;
                     const size_t n_st = (size_t)grid.x * grid.y * 16 * 8;
-                    const bool want_st = it + 1 == n && getenv("MMW_SD_STAMPS") != nullptr;
+                    const bool want_st = it + 1 == n && live_switch(LIVE_SD_STAMPS);
                     if (want_st) {
                         MMW_TRY(sdm_stamps.alloc(n_st));
                         MMW_HIP(hipMemsetAsync(sdm_stamps.p, 0, n_st * sizeof(unsigned long long), st));
                     }
-                    static const int sd_nb = getenv("MMW_SD_NB") ? atoi(getenv("MMW_SD_NB")) : 2;  // chunks resident per workgroup (3: measured 1 % slower)
 #define MMW_SDM_LAUNCH(MT, NB)                                                                                                               \
     do {                                                                                                                                     \
         MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_sddmm_mfma<MT, NB>), sdm_lds_bytes<MT, NB>()));                                 \
@@ -1510,42 +1529,11 @@ template <typename T> struct Solver final : mmw_solver {
                            reinterpret_cast<const char*>(xh_planes.p), drow.p, trp, ntr, xs_val.p, xs_avg.p, acc, rs_out, dfx, sdm_stamps.p,  \
                            fv_rides ? fv_now : FirstVerify{});                                                                               \
     } while (0)
-                    if (HB.mfma_mt == 2) { if (sd_nb == 3) MMW_SDM_LAUNCH(2, 3); else MMW_SDM_LAUNCH(2, 2); }
-                    else { if (sd_nb == 3) MMW_SDM_LAUNCH(1, 3); else MMW_SDM_LAUNCH(1, 2); }
+                    // two chunks resident per workgroup (three were built and measured 1 % slower)
+                    if (HB.mfma_mt == 2) MMW_SDM_LAUNCH(2, 2);
+                    else MMW_SDM_LAUNCH(1, 2);
 #undef MMW_SDM_LAUNCH
-                    if (want_st) {
-                        std::vector<unsigned long long> h(n_st);
-                        MMW_HIP(hipMemcpyAsync(h.data(), sdm_stamps.p, n_st * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                        MMW_HIP(hipStreamSynchronize(st));
-                        double sum[8] = {0}, life_max = 0;
-                        int nw = 0;
-                        for (size_t w = 0; w < n_st / 8; ++w) {
-                            const unsigned long long* q = &h[w * 8];
-                            if (!q[4]) continue;
-                            ++nw;
-                            for (int k = 0; k < 8; ++k) sum[k] += (double)q[k];
-                            life_max = std::max(life_max, (double)q[4]);
-                        }
-                        {   // the slowest twentieth of the waves: where their time went
-                            std::vector<std::pair<unsigned long long, size_t>> byl;
-                            for (size_t w = 0; w < n_st / 8; ++w) if (h[w * 8 + 4]) byl.push_back({h[w * 8 + 4], w});
-                            std::sort(byl.rbegin(), byl.rend());
-                            const size_t top = std::max<size_t>(1, byl.size() / 20);
-                            double ts[8] = {0};
-                            for (size_t i = 0; i < top && i < byl.size(); ++i) for (int k = 0; k < 8; ++k) ts[k] += (double)h[byl[i].second * 8 + k];
-                            if (!byl.empty())
-                                fprintf(stderr, "[sddmm stamps] slowest %zu waves: prologue %.0f, wait+barrier %.0f, issue %.0f, reads+products %.0f, sums %.0f, stores %.0f, lifetime %.0f; by (wg.y): ", top,
-                                        ts[0] / top, ts[1] / top, ts[2] / top, ts[3] / top, ts[5] / top, ts[7] / top, ts[4] / top);
-                            int cnt[8] = {0};
-                            for (size_t i = 0; i < top && i < byl.size(); ++i) { const size_t wg = byl[i].second / (size_t)(4 * HB.mfma_mt); const unsigned y = (unsigned)(wg / grid.x); if (y < 8) ++cnt[y]; }
-                            for (unsigned y = 0; y < grid.y && y < 8; ++y) fprintf(stderr, "%d ", cnt[y]);
-                            fprintf(stderr, "\n");
-                        }
-                        if (nw)
-                            fprintf(stderr, "[sddmm stamps] grid %u x %u, %d working waves; shader clocks per wave: prologue %.0f, wait+barrier %.0f, issue %.0f, reads+products %.0f, "
-                                            "row/column sums %.0f, tile+stores+atomics %.0f, lifetime %.0f (max %.0f)\n",
-                                    grid.x, grid.y, nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[5] / nw, sum[7] / nw, sum[4] / nw, life_max);
-                    }
+                    if (want_st) MMW_TRY(dump_sddmm_stamps(sdm_stamps.p, n_st, grid));
                     sd_done = true;
                     // (MMW_FV_IN_SDDMM=0: certified by spare workgroups of the next iteration's DUAL phase, or by a launch of its own after the chunk's last)
                     if (first_it && !fv_rides) fv_pending = fv_now;
@@ -1557,7 +1545,7 @@ template <typename T> struct Solver final : mmw_solver {
             } else if (sddmm_blk2 && eng.use_blk) {
                 unsigned long long* sd_stamps = nullptr;  // MMW_SD_STAMPS=1: phase stamps of the last iteration's SDDMM
                 DevBuf<unsigned long long> stamp_buf;
-                if (it + 1 == n && getenv("MMW_SD_STAMPS")) {
+                if (it + 1 == n && live_switch(LIVE_SD_STAMPS)) {
                     MMW_TRY(stamp_buf.alloc((size_t)16 * 8192));
                     MMW_HIP(hipMemsetAsync(stamp_buf.p, 0, (size_t)16 * 8192 * sizeof(unsigned long long), st));
                     sd_stamps = stamp_buf.p;
@@ -1623,7 +1611,7 @@ template <typename T> struct Solver final : mmw_solver {
         }
         // until settle() finds a violation or something touches the iterate.  A handle that has had to replay a chunk keeps restarting
         // its chunks exactly (measured on er-1pct, whose order rises during the run: 5 100 it/s so, 4 500 chained)
-        chain_ok = optimistic && n > 1 && replays == 0 && !getenv("MMW_NO_CHUNK_CHAIN");
+        chain_ok = optimistic && n > 1 && replays == 0 && !sw.no_chunk_chain;
         rs_last = rs_ok;
         return MMW_OK;
     }
@@ -1789,7 +1777,7 @@ template <typename T> struct Solver final : mmw_solver {
 };
 
 template <typename T>
-int expm_apply_impl(int device, int method, int max_order, double tol, int32_t K, int32_t D, const int32_t* indptr,
+int expm_apply_impl(const Switches& sw, int device, int method, int max_order, double tol, int32_t K, int32_t D, const int32_t* indptr,
                     const int32_t* indices, const double* data, const double* B, double* out, double info[4], int32_t reps,
                     double* kernel_us) {
     MMW_HIP(hipSetDevice(device));
@@ -1808,7 +1796,7 @@ int expm_apply_impl(int device, int method, int max_order, double tol, int32_t K
     MMW_TRY(d_ip.upload(ip, st));
     MMW_TRY(d_ci.upload(ci, st));
     MMW_TRY(d_v.upload_cast(vv, st));
-    ExpmEngine<T> eng;
+    ExpmEngine<T> eng(sw);
     MMW_TRY(eng.init(st, K, D, d_ip.p, d_ci.p, d_v.p));
     eng.method = method; eng.max_order = max_order; eng.tol = tol;
     MMW_TRY(d_out.alloc(eng.bs));
@@ -2066,12 +2054,12 @@ int mmw_create(mmw_solver** out, int device, int dtype, int32_t K, int32_t Z, in
     }
     int rc;
     if (dtype == MMW_F32) {
-        auto s = std::make_unique<Solver<float>>();
+        auto s = std::make_unique<Solver<float>>(Switches::from_env());
         s->host_only = host_only;
         rc = s->init(device, K, Z, rank_radio, eta, nit, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
         if (rc == MMW_OK) *out = s.release();
     } else if (dtype == MMW_F64) {
-        auto s = std::make_unique<Solver<double>>();
+        auto s = std::make_unique<Solver<double>>(Switches::from_env());
         s->host_only = host_only;
         rc = s->init(device, K, Z, rank_radio, eta, nit, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
         if (rc == MMW_OK) *out = s.release();
@@ -2087,11 +2075,11 @@ int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, in
     if (nit < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
     int rc;
     if (dtype == MMW_F32) {
-        auto s = std::make_unique<Solver<float>>();
+        auto s = std::make_unique<Solver<float>>(Switches::from_env());
         rc = s->init_env(env->e.device, env->e, Z, rank_radio, eta, nit);
         if (rc == MMW_OK) *out = s.release();
     } else if (dtype == MMW_F64) {
-        auto s = std::make_unique<Solver<double>>();
+        auto s = std::make_unique<Solver<double>>(Switches::from_env());
         rc = s->init_env(env->e.device, env->e, Z, rank_radio, eta, nit);
         if (rc == MMW_OK) *out = s.release();
     } else {
@@ -2140,8 +2128,9 @@ int mmw_expm_apply(int device, int dtype, int method, int max_order, double tol,
     int ndev = 0;
     MMW_TRY(mmw_device_count(&ndev));
     if (device < 0 || device >= ndev) return fail(MMW_ERR_HIP, "mmw_expm_apply: no such HIP device");
-    if (dtype == MMW_F32) return expm_apply_impl<float>(device, method, max_order, tol, K, D, indptr, indices, data, B, out, info, reps, kernel_us);
-    if (dtype == MMW_F64) return expm_apply_impl<double>(device, method, max_order, tol, K, D, indptr, indices, data, B, out, info, reps, kernel_us);
+    const Switches sw = Switches::from_env();
+    if (dtype == MMW_F32) return expm_apply_impl<float>(sw, device, method, max_order, tol, K, D, indptr, indices, data, B, out, info, reps, kernel_us);
+    if (dtype == MMW_F64) return expm_apply_impl<double>(sw, device, method, max_order, tol, K, D, indptr, indices, data, B, out, info, reps, kernel_us);
     return fail(MMW_ERR_ARG, "dtype must be MMW_F32 or MMW_F64");
 }
 
@@ -2159,7 +2148,8 @@ int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t 
         ~Stream() { if (s) (void)hipStreamDestroy(s); }
     } stream;
     MMW_HIP(hipStreamCreate(&stream.s));
-    mmw::DenseWork<double> dw;
+    const Switches switches = Switches::from_env();
+    mmw::DenseWork<double> dw(switches);
     dw.st = stream.s;
     MMW_TRY(dw.ensure(b, 1));
     MMW_TRY(copy_h2d(dw.G.p, G, (size_t)b * b * sizeof(double), stream.s));

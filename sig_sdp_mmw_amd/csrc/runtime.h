@@ -15,6 +15,7 @@
 
 #include "../../include/mmw_hip.h"
 #include "device_utils.h"
+#include "switches.h"
 
 namespace mmw {
 
@@ -161,8 +162,7 @@ template <typename T> struct DevBuf {
     // Contents are undefined afterwards.  An allocation that is large enough is kept: hipFree waits for the whole device (every
     // stream of every handle), so a handle that shrinks its blocks for the next slot count must not free them.
     int alloc(size_t count) {
-        static const bool exact = getenv("MMW_DEVBUF_EXACT") != nullptr;
-        if (p && count <= cap && !exact) {
+        if (p && count <= cap && !live_switch(LIVE_DEVBUF_EXACT)) {
             n = count;
             return MMW_OK;
         }

@@ -8,6 +8,8 @@
 namespace mmw {
 
 template <typename T> struct Extras {
+    const Switches& sw;
+    explicit Extras(const Switches& s) : sw(s), fac(s) {}
     hipStream_t st = nullptr;
     const HostPattern* H = nullptr;
     KernelTimers* kt = nullptr;
@@ -17,7 +19,7 @@ template <typename T> struct Extras {
     DevBuf<double> so_data, h_max, so_hmax;  // so_hmax[e] = h_max[so_indices[e]]: the greedy reads it like so_data
     DevBuf<GreedyHdr> ghdr;
     DevBuf<double> gX, randv, P, gain, nrm;
-    DevBuf<int> pref, slot, order, rem, glag, rank_part, gsched, gnsteps;
+    DevBuf<int> pref, slot, order, rem, rank_part, gsched, gnsteps;
     DevBuf<unsigned> gmask;
     DevBuf<GreedyHdr> ghdr_s;  // [steps][GB_WAVES]: the users' headers in schedule order
     Factorizer<T> fac;
@@ -25,20 +27,14 @@ template <typename T> struct Extras {
     DevBuf<T> g_x, g_l, g_y, g_e1, g_e2, g_r, g_vec, g_tm;
     DevBuf<double> g_part, g_scal, g_lz, g_colsum;
 
-    int maxdeg_h = 1, maxq_h = 1;  // longest row of S_gain without its diagonal / of Q (the greedy kernels' LDS budget)
     // the rounding's state straight from the device generator (mmw_create_from_env): so_* / q_* / h_max are filled by the caller's kernels
-    int init_device(hipStream_t s, int K_, KernelTimers* k, int maxdeg, int maxq) {
+    int init_device(hipStream_t s, int K_, KernelTimers* k) {
         st = s; H = nullptr; K = K_; kt = k;
-        maxdeg_h = std::max(1, maxdeg); maxq_h = std::max(1, maxq);
         MMW_TRY(ghdr.alloc((size_t)K));
         return fac.init(st, K, kt);
     }
     int init(hipStream_t s, const HostPattern* h, int K_, KernelTimers* k) {
         st = s; H = h; K = K_; kt = k;
-        for (int q = 0; q < K; ++q) {
-            maxdeg_h = std::max(maxdeg_h, H->so_indptr[q + 1] - H->so_indptr[q]);
-            maxq_h = std::max(maxq_h, H->q_indptr[q + 1] - H->q_indptr[q]);
-        }
         MMW_TRY(so_indptr.upload(H->so_indptr, st));
         MMW_TRY(so_indices.upload(H->so_indices, st));
         MMW_TRY(so_data.upload(H->so_data, st));
@@ -123,7 +119,7 @@ template <typename T> struct Extras {
         while (j <= m_max) {
             const int jend = std::min(m_max, j + chunk - 1);
             for (; j <= jend; ++j) {
-                MMW_TRY((spmm_launch<T, SPMM_LANCZOS>(st, K, lay, nblk, indptr, col, val, blk(j), g_tm.p, nullptr, nullptr, 1.0, 0.0, 1.0, part.p)));
+                MMW_TRY((spmm_launch<T, SPMM_LANCZOS>(st, sw, K, lay, nblk, indptr, col, val, blk(j), g_tm.p, nullptr, nullptr, 1.0, 0.0, 1.0, part.p)));
                 hipLaunchKernelGGL((k_colreduce<LZ_ALPHA>), dim3((Dp + 15) / 16), dim3(1024), 0, st, nblk, Dp, part.p, g_colsum.p, j, eps, S, (const ExpmPlan*)nullptr);
                 hipLaunchKernelGGL((k_lz_update<T>), dim3(gr), dim3(BLOCK), shcol, st, K, Dp, j, g_tm.p, blk(j), j > 1 ? blk(j - 1) : blk(j), blk(j + 1), S, part.p, (const ExpmPlan*)nullptr);
                 hipLaunchKernelGGL((k_colreduce<LZ_BETA>), dim3((Dp + 15) / 16), dim3(1024), 0, st, gr, Dp, part.p, g_colsum.p, j, eps, S, (const ExpmPlan*)nullptr);
@@ -177,7 +173,6 @@ template <typename T> struct Extras {
         MMW_TRY(ensure(gX, (size_t)K_ * Dp)); MMW_TRY(ensure(randv, (size_t)nb * Z * Dp));
         MMW_TRY(ensure(P, nP)); MMW_TRY(ensure(pref, nP)); MMW_TRY(ensure(gain, nP));
         MMW_TRY(ensure(slot, (size_t)nb * K_)); MMW_TRY(ensure(nrm, K_)); MMW_TRY(ensure(order, K_)); MMW_TRY(ensure(rem, nb));
-        MMW_TRY(ensure(glag, (size_t)K_));
         MMW_TRY(ensure(rank_part, (size_t)RANK_SPLIT * K_));
         return MMW_OK;
     }
@@ -221,82 +216,38 @@ template <typename T> struct Extras {
         if (kt) MMW_TRY(kt->end());
         MMW_HIP(hipGetLastError());
         if (kt) MMW_TRY(kt->begin(KT_GREEDY));
-        {
-            int maxdeg = maxdeg_h, maxq = maxq_h;
-            maxdeg = (maxdeg + 1) / 2 * 2;  // keep the int arrays after the doubles 8-byte aligned
-            if (getenv("MMW_GREEDY_SEQ") && (maxdeg > 4 * BLOCK || maxq > 4 * BLOCK || Z > 4 * BLOCK))
-                return fail(MMW_ERR_ARG, "mmw_round: more than 1024 neighbours / slots per user is not supported by the sequential greedy kernel");
-            hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, order.p, so_indptr.p, q_indptr.p, h_max.p, ghdr.p);
-            static const bool sequential = getenv("MMW_GREEDY_SEQ") != nullptr;  // the one-user-per-step kernel, kept for comparison
-            static const bool runs_only = getenv("MMW_GREEDY_RUNS") != nullptr;   // contiguous runs instead of the out-of-order schedule
-            if (!sequential && !runs_only) {
-                // steps scheduled out of order (kernels_round.h, k_greedy_schedule): interaction masks of the visiting order, the schedule,
-                // the headers step by step; then one workgroup per attempt follows it
-                MMW_TRY(ensure(gmask, (size_t)K));
-                MMW_TRY(ensure(gsched, (size_t)K * GB_WAVES));
-                MMW_TRY(ensure(gnsteps, 1));
-                MMW_TRY(ensure(ghdr_s, (size_t)K * GB_WAVES));  // (at most K steps)
-                MMW_HIP(hipMemsetAsync(gmask.p, 0, (size_t)K * sizeof(unsigned), st));
-                const size_t pairs = (size_t)K * GS_W;
-                hipLaunchKernelGGL(k_greedy_cmask, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, (const GreedyHdr*)ghdr.p,
-                                   so_indices.p, q_indices.p, gmask.p);
-                hipLaunchKernelGGL(k_greedy_schedule, dim3(1), dim3(WAVE), 0, st, K, (const unsigned*)gmask.p, gsched.p, gnsteps.p);
-                hipLaunchKernelGGL(k_greedy_sched_headers, dim3(grid_elems((size_t)K * 2)), dim3(BLOCK), 0, st, K, (const int*)gnsteps.p, (const int*)gsched.p,
-                                   (const GreedyHdr*)ghdr.p, ghdr_s.p);
-                if (getenv("MMW_VERBOSE")) {
-                    int ns = 0;
-                    MMW_HIP(hipMemcpyAsync(&ns, gnsteps.p, sizeof(int), hipMemcpyDeviceToHost, st));
-                    MMW_HIP(hipStreamSynchronize(st));
-                    fprintf(stderr, "[round] %d users in %d steps (%.1f per step)\n", K, ns, (double)K / std::max(ns, 1));
-                }
-                const size_t baseb = (size_t)GB_WAVES * Z * 4;
-                if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: 64 Z bytes exceed the greedy kernel's LDS");
-                const bool slot_lds = baseb + (size_t)K * 4 <= 150 * 1024;
-                const size_t sh = baseb + (slot_lds ? (size_t)K * 4 : 0);
-                if (slot_lds) {
-                    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                    hipLaunchKernelGGL((k_greedy_b<true, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
-                                       so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
-                } else {
-                    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                    hipLaunchKernelGGL((k_greedy_b<false, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
-                                       so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
-                }
-            } else if (!sequential) {
-                // several mutually non-interacting users per step (k_greedy_b): interaction lags of the visiting order first
-                MMW_TRY(ensure(glag, (size_t)K));
-                MMW_HIP(hipMemsetAsync(glag.p, 0x7F, (size_t)K * sizeof(int), st));
-                const size_t pairs = (size_t)K * (GB_WAVES - 1);
-                hipLaunchKernelGGL(k_greedy_conflicts, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, (const GreedyHdr*)ghdr.p,
-                                   so_indices.p, q_indices.p, glag.p);
-                const size_t baseb = (size_t)GB_WAVES * Z * 4 + (((size_t)K + 3) & ~(size_t)3);
-                if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: K + 32 Z bytes exceed the greedy kernel's LDS");
-                const bool slot_lds = baseb + (size_t)K * 4 <= 150 * 1024;
-                const size_t sh = baseb + (slot_lds ? (size_t)K * 4 : 0);
-                if (slot_lds) {
-                    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                    hipLaunchKernelGGL((k_greedy_b<true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr.p, (const int*)glag.p, pref.p,
-                                       so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p);
-                } else {
-                    MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                    hipLaunchKernelGGL((k_greedy_b<false>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr.p, (const int*)glag.p, pref.p,
-                                       so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p);
-                }
-            } else {
-            const size_t base = (size_t)2 * ((size_t)maxdeg * 20 + (size_t)maxq * 4 + (size_t)Z * 4) + (size_t)Z * 4;
-            const bool slot_lds = base + (size_t)K * 4 <= 150 * 1024;
-            const size_t sh = base + (slot_lds ? (size_t)K * 4 : 0);
-            if (sh > 160 * 1024) return fail(MMW_ERR_ARG, "mmw_round: a user's neighbour list does not fit the greedy kernel's LDS record");
-            if (slot_lds) {
-                MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                hipLaunchKernelGGL((k_greedy<true>), dim3(nb), dim3(BLOCK), sh, st, K, Z, maxdeg, maxq, (const GreedyHdr*)ghdr.p, pref.p, so_indices.p,
-                                   so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p);
-            } else {
-                MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                hipLaunchKernelGGL((k_greedy<false>), dim3(nb), dim3(BLOCK), sh, st, K, Z, maxdeg, maxq, (const GreedyHdr*)ghdr.p, pref.p, so_indices.p,
-                                   so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p);
-            }
-            }
+        hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, order.p, so_indptr.p, q_indptr.p, h_max.p, ghdr.p);
+        // steps scheduled out of order (kernels_round.h, k_greedy_schedule): interaction masks of the visiting order, the schedule,
+        // the headers step by step; then one workgroup per attempt follows it
+        MMW_TRY(ensure(gmask, (size_t)K));
+        MMW_TRY(ensure(gsched, (size_t)K * GB_WAVES));
+        MMW_TRY(ensure(gnsteps, 1));
+        MMW_TRY(ensure(ghdr_s, (size_t)K * GB_WAVES));  // (at most K steps)
+        MMW_HIP(hipMemsetAsync(gmask.p, 0, (size_t)K * sizeof(unsigned), st));
+        const size_t pairs = (size_t)K * GS_W;
+        hipLaunchKernelGGL(k_greedy_cmask, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, (const GreedyHdr*)ghdr.p,
+                           so_indices.p, q_indices.p, gmask.p);
+        hipLaunchKernelGGL(k_greedy_schedule, dim3(1), dim3(WAVE), 0, st, K, (const unsigned*)gmask.p, gsched.p, gnsteps.p);
+        hipLaunchKernelGGL(k_greedy_sched_headers, dim3(grid_elems((size_t)K * 2)), dim3(BLOCK), 0, st, K, (const int*)gnsteps.p, (const int*)gsched.p,
+                           (const GreedyHdr*)ghdr.p, ghdr_s.p);
+        if (live_switch(LIVE_VERBOSE)) {
+            int ns = 0;
+            MMW_HIP(hipMemcpyAsync(&ns, gnsteps.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            MMW_HIP(hipStreamSynchronize(st));
+            fprintf(stderr, "[round] %d users in %d steps (%.1f per step)\n", K, ns, (double)K / std::max(ns, 1));
+        }
+        const size_t baseb = (size_t)GB_WAVES * Z * 4;
+        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: 64 Z bytes exceed the greedy kernel's LDS");
+        const bool slot_lds = baseb + (size_t)K * 4 <= 150 * 1024;
+        const size_t sh = baseb + (slot_lds ? (size_t)K * 4 : 0);
+        if (slot_lds) {
+            MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            hipLaunchKernelGGL((k_greedy_b<true, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
+                               so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
+        } else {
+            MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            hipLaunchKernelGGL((k_greedy_b<false, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
+                               so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
         }
         if (kt) MMW_TRY(kt->end());
         MMW_HIP(hipGetLastError());
