@@ -440,10 +440,8 @@ template <typename T> struct ExpmEngine {
         last = *plan_h;
         last_mfma_ok = last.mfma_ok != 0;
         if (live_switch(LIVE_VERBOSE)) {
-            union { unsigned u; float f; } c1, c2;
-            c1.u = last.conv[1]; c2.u = last.conv[2];
             fprintf(stderr, "[plan] rho %.3e absn %.3e mfma_ok %d tol %.1e m %d (a-priori %d) apost %d m_eff %d est[1] %.3e est[2] %.3e viol %d\n", last.rho,
-                    last.absn, last.mfma_ok, last.tol, last.m, last.m_apriori, last.apost, last.m_eff, c1.f, c2.f, v);
+                    last.absn, last.mfma_ok, last.tol, last.m, last.m_apriori, last.apost, last.m_eff, plan_estimate(last.conv[1]), plan_estimate(last.conv[2]), v);
         }
         if (violated) *violated = v;
         return MMW_OK;

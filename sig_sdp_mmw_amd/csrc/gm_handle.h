@@ -1,0 +1,193 @@
+#pragma once
+#include "kernels_gm.h"
+#include "runtime.h"
+
+using namespace mmw;
+
+// ---- the greedy baselines of sim_src/alg/gm.py (csrc/kernels_gm.h) -----------------------------------------------------------------
+// A light handle: the out-lists of S without diagonal, the Q rows, h_max and the clique structure of Q; none of the MMW pattern.
+struct mmw_gm {
+    GmState S;
+    int device = -1;  // -1: host C++ only
+    hipStream_t st = nullptr;
+    DevBuf<int> so_indptr, so_indices, q_indptr, q_indices, grp, ord, slot, lists, info, rank_part;
+    DevBuf<double> so_data, so_hmax, q_data, h_max, key, gsum, asum;
+    DevBuf<int> mark, owner;
+    // MAX_RAND (the rounding's scheduled greedy, kernels_round.h)
+    DevBuf<int> pref, gsched, gnsteps;
+    DevBuf<unsigned> gmask;
+    DevBuf<GreedyHdr> ghdr, ghdr_s;
+    DevBuf<double> ggain;
+    // host side of the device path
+    std::vector<int> h_info;
+    // host path work
+    std::vector<double> w_gs, w_as;
+    std::vector<int> w_mark, w_owner;
+    int w_stamp = 0;
+    ~mmw_gm() {
+        if (st) (void)hipStreamDestroy(st);
+    }
+    bool lds_fits() const {
+        const size_t b = (size_t)S.K * (S.clique ? 12 : 20) + (S.clique ? (size_t)S.G * 4 : 0);
+        return b <= GM_LDS_MAX;
+    }
+    int init(int dev) {
+        device = dev;
+        if (device < 0) {
+            w_gs.assign(S.K, 0.0); w_as.assign(S.K, 0.0); w_mark.assign(S.K, 0); w_owner.assign(std::max(S.G, 1), -1);
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        MMW_TRY(so_indptr.upload(S.so_indptr, st)); MMW_TRY(so_indices.upload(S.so_indices, st));
+        MMW_TRY(so_data.upload(S.so_data, st)); MMW_TRY(so_hmax.upload(S.so_hmax, st));
+        MMW_TRY(q_indptr.upload(S.q_indptr, st)); MMW_TRY(q_indices.upload(S.q_indices, st)); MMW_TRY(q_data.upload(S.q_data, st));
+        MMW_TRY(h_max.upload(S.h_max, st)); MMW_TRY(grp.upload(S.grp, st));
+        const size_t K = (size_t)S.K;
+        MMW_TRY(ord.alloc(K)); MMW_TRY(slot.alloc(K)); MMW_TRY(lists.alloc(2 * K)); MMW_TRY(info.alloc(GM_INFO_N));
+        if (!lds_fits()) {
+            MMW_TRY(gsum.alloc(K)); MMW_TRY(mark.alloc(K));
+            if (S.clique) MMW_TRY(owner.alloc(std::max(S.G, 1))); else MMW_TRY(asum.alloc(K));
+        }
+        h_info.assign(GM_INFO_N, 0);
+        return MMW_OK;
+    }
+    // one launch of k_gm_slots over ord (already on the device)
+    int launch(int n, int z0, int nslot, int nattempt, int full) {
+        const bool lds = lds_fits();
+        const size_t sh = lds ? (size_t)S.K * (S.clique ? 12 : 20) + (S.clique ? (size_t)S.G * 4 : 0) : 0;
+#define MMW_GM_LAUNCH(L, CQ)                                                                                                              \
+    do {                                                                                                                                  \
+        if (L) MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_gm_slots<L, CQ>), (int)sh));                                       \
+        hipLaunchKernelGGL((k_gm_slots<L, CQ>), dim3(1), dim3(WAVE), sh, st, S.K, n, (const int*)ord.p, z0, nslot, nattempt, full,       \
+                           (const int*)grp.p, S.G, (const double*)h_max.p, (const int*)so_indptr.p, (const int*)so_indices.p,           \
+                           (const double*)so_data.p, (const double*)so_hmax.p, (const int*)q_indptr.p, (const int*)q_indices.p,       \
+                           (const double*)q_data.p, gsum.p, asum.p, mark.p, owner.p, slot.p, lists.p, info.p);                         \
+    } while (0)
+        if (lds && S.clique) MMW_GM_LAUNCH(true, true);
+        else if (lds) MMW_GM_LAUNCH(true, false);
+        else if (S.clique) MMW_GM_LAUNCH(false, true);
+        else MMW_GM_LAUNCH(false, false);
+#undef MMW_GM_LAUNCH
+        MMW_HIP(hipGetLastError());
+        MMW_TRY(copy_d2h(h_info.data(), info.p, GM_INFO_N * sizeof(int), st));
+        return MMW_OK;
+    }
+    int check_order(const int32_t* order, int32_t n, bool perm) {
+        if (n < 0 || n > S.K || (perm && n != S.K)) return fail(MMW_ERR_ARG, "gm: the visiting order has the wrong length");
+        std::vector<char> seen(S.K, 0);
+        for (int32_t i = 0; i < n; ++i) {
+            if (order[i] < 0 || order[i] >= S.K) return fail(MMW_ERR_ARG, "gm: visiting order entry out of range");
+            if (seen[order[i]]) return fail(MMW_ERR_ARG, "gm: a user appears twice in the visiting order");
+            seen[order[i]] = 1;
+        }
+        return MMW_OK;
+    }
+    int pass(const int32_t* order, int32_t n, int32_t nattempt, int32_t* list_out, int32_t* nlist) {
+        MMW_TRY(check_order(order, n, false));
+        if (nattempt < 1) return fail(MMW_ERR_ARG, "gm: nattempt must be >= 1");
+        if (device < 0) {
+            std::vector<int32_t> best;
+            S.pass_host(order, n, nattempt, w_gs, w_as, w_mark, w_owner, w_stamp, best);
+            std::copy(best.begin(), best.end(), list_out);
+            *nlist = (int32_t)best.size();
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        if (n == 0) { *nlist = 0; return MMW_OK; }
+        MMW_TRY(copy_h2d(ord.p, order, (size_t)n * sizeof(int), st));
+        MMW_TRY(launch(n, 0, 1, nattempt, 0));
+        const int len = h_info[GM_INFO_LAST_LEN];
+        if (len < 0 || len > n) return fail(MMW_ERR_STATE, "gm: the pass returned an impossible list length");
+        MMW_TRY(copy_d2h(list_out, lists.p + (size_t)h_info[GM_INFO_LAST_BUF] * S.K, (size_t)len * sizeof(int), st));
+        *nlist = len;
+        return MMW_OK;
+    }
+    int run(const double* key_h, int32_t Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out, int32_t* rem_out) {
+        if (Z < 0) return fail(MMW_ERR_ARG, "gm: Z must be >= 0");
+        if (nattempt < 1) return fail(MMW_ERR_ARG, "gm: nattempt must be >= 1");
+        const int K = S.K;
+        int entered = 0, stop = GM_STOP_SLOTS, total = 0;
+        if (device < 0) {
+            std::vector<int32_t> order(K), cur(K), best;
+            std::iota(order.begin(), order.end(), 0);
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key_h[a] > key_h[b]; });
+            std::fill(z_out, z_out + K, -1);
+            for (int32_t z = 0; z < Z; ++z) {
+                int32_t n = 0;
+                for (int32_t k : order) if (z_out[k] < 0) cur[n++] = k;
+                S.pass_host(cur.data(), n, nattempt, w_gs, w_as, w_mark, w_owner, w_stamp, best);
+                ++entered;
+                for (int32_t k : best) z_out[k] = z;
+                total += (int)best.size();
+                if (best.empty()) { stop = GM_STOP_EMPTY; break; }
+                if (total == K) { stop = GM_STOP_ALL_ASSIGNED; break; }
+            }
+        } else {
+            MMW_HIP(hipSetDevice(device));
+            MMW_TRY(key.alloc(K)); MMW_TRY(rank_part.alloc((size_t)RANK_SPLIT * K));
+            MMW_TRY(copy_h2d(key.p, key_h, (size_t)K * sizeof(double), st));
+            // argsort(-key, kind="stable") on the device: rank by counting, ties by lower index (kernels_round.h)
+            hipLaunchKernelGGL(k_rank_count, dim3((K + BLOCK - 1) / BLOCK, RANK_SPLIT), dim3(BLOCK), 0, st, K, (const double*)key.p, rank_part.p);
+            hipLaunchKernelGGL(k_rank_scatter, dim3((K + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, K, (const int*)rank_part.p, ord.p);
+            MMW_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)K * sizeof(int), st));
+            if (Z > 0) {
+                MMW_TRY(launch(K, 0, Z, nattempt, 1));
+                entered = h_info[GM_INFO_ENTERED]; stop = h_info[GM_INFO_STOP]; total = h_info[GM_INFO_TOTAL];
+            }
+            MMW_TRY(copy_d2h(z_out, slot.p, (size_t)K * sizeof(int), st));
+        }
+        *zz_out = stop == GM_STOP_ALL_ASSIGNED ? entered : Z;  // an empty slot: the reference enters every remaining one (fact a)
+        *rem_out = K - total;
+        return MMW_OK;
+    }
+    int assign(int32_t Z, const int32_t* order, const int32_t* pref_h, int32_t* z_out, int32_t* rem_out) {
+        const int K = S.K;
+        if (Z < 1) return fail(MMW_ERR_ARG, "gm: Z must be >= 1");
+        MMW_TRY(check_order(order, K, true));
+        for (size_t i = 0; i < (size_t)K * Z; ++i)
+            if (pref_h[i] < 0 || pref_h[i] >= Z) return fail(MMW_ERR_ARG, "gm: slot preference entry out of range");
+        if (device < 0) {
+            S.assign_host(Z, order, pref_h, z_out, rem_out);
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        const size_t baseb = (size_t)GB_WAVES * Z * 4;
+        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "gm: 32 Z bytes exceed the greedy kernel's LDS");
+        MMW_TRY(pref.alloc((size_t)K * Z)); MMW_TRY(ggain.alloc((size_t)K * Z)); MMW_TRY(ghdr.alloc(K));
+        MMW_TRY(gmask.alloc(K)); MMW_TRY(gsched.alloc((size_t)K * GB_WAVES)); MMW_TRY(gnsteps.alloc(1)); MMW_TRY(ghdr_s.alloc((size_t)K * GB_WAVES));
+        MMW_TRY(copy_h2d(ord.p, order, (size_t)K * sizeof(int), st));
+        MMW_TRY(copy_h2d(pref.p, pref_h, (size_t)K * Z * sizeof(int), st));
+        MMW_HIP(hipMemsetAsync(ggain.p, 0, (size_t)K * Z * sizeof(double), st));
+        MMW_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)K * sizeof(int), st));
+        MMW_HIP(hipMemsetAsync(gmask.p, 0, (size_t)K * sizeof(unsigned), st));
+        // the rounding's scheduled greedy (solver_extras.h, Extras::round) with this order and preference
+        hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, (const int*)ord.p, (const int*)so_indptr.p,
+                           (const int*)q_indptr.p, (const double*)h_max.p, ghdr.p);
+        const size_t pairs = (size_t)K * GS_W;
+        hipLaunchKernelGGL(k_greedy_cmask, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, (const GreedyHdr*)ghdr.p,
+                           (const int*)so_indices.p, (const int*)q_indices.p, gmask.p);
+        hipLaunchKernelGGL(k_greedy_schedule, dim3(1), dim3(WAVE), 0, st, K, (const unsigned*)gmask.p, gsched.p, gnsteps.p);
+        hipLaunchKernelGGL(k_greedy_sched_headers, dim3(grid_elems((size_t)K * 2)), dim3(BLOCK), 0, st, K, (const int*)gnsteps.p,
+                           (const int*)gsched.p, (const GreedyHdr*)ghdr.p, ghdr_s.p);
+        const bool slot_lds = baseb + (size_t)K * 4 <= 150 * 1024;
+        const size_t sh = baseb + (slot_lds ? (size_t)K * 4 : 0);
+        if (slot_lds) {
+            MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_greedy_b<true, true>), (int)sh));
+            hipLaunchKernelGGL((k_greedy_b<true, true>), dim3(1), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr,
+                               (const int*)pref.p, (const int*)so_indices.p, (const double*)so_data.p, (const double*)so_hmax.p, (const int*)q_indices.p,
+                               ggain.p, slot.p, info.p, (const int*)gnsteps.p);
+        } else {
+            MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_greedy_b<false, true>), (int)sh));
+            hipLaunchKernelGGL((k_greedy_b<false, true>), dim3(1), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr,
+                               (const int*)pref.p, (const int*)so_indices.p, (const double*)so_data.p, (const double*)so_hmax.p, (const int*)q_indices.p,
+                               ggain.p, slot.p, info.p, (const int*)gnsteps.p);
+        }
+        MMW_HIP(hipGetLastError());
+        MMW_TRY(copy_d2h(z_out, slot.p, (size_t)K * sizeof(int), st));
+        int rem = 0;
+        MMW_TRY(copy_d2h(&rem, info.p, sizeof(int), st));
+        *rem_out = rem;
+        return MMW_OK;
+    }
+};

@@ -9,6 +9,8 @@
 // group per nonzero: every gather is a fully coalesced LPR*16-byte row segment); for wider blocks one
 // lane covers NCH chunks 64 lanes apart.  All HBM-bound: ~0.2-2 flop/byte, so no MFMA here.
 #pragma once
+#include <cstring>
+
 #include "blk_config.h"
 #include "device_utils.h"
 
@@ -43,6 +45,12 @@ struct ExpmPlan {      // written by k_plan, read by every expm kernel
     unsigned conv[MAX_ORDER + 2];  // conv[j]: float bits of the largest per-column estimate after j steps (valid once step j's scalars ran)
     unsigned first_est;  // float bits of the largest per-column error bound of the first-order form y = u + (A - mu I) u (first_order_bound)
 };
+// an estimate the device left in a plan as float bits (ExpmPlan::conv[], first_est)
+inline double plan_estimate(unsigned bits) {
+    float f;
+    memcpy(&f, &bits, sizeof f);
+    return (double)f;
+}
 // why an optimistic chunk has to be replayed (bits of the violation word the host reads when it settles the chunk)
 enum : int { VIOL_ORDER = 1 /* the launched Lanczos steps did not meet the tolerance */, VIOL_LAGGED = 2 /* an extrapolated plan did not cover its matrix */,
              VIOL_PLAN = 4 /* substeps / overflow */, VIOL_SOFTMAX = 8 /* the fused softmax's shift ran away */, VIOL_OPERANDS = 16 /* 16-bit operand gate */,

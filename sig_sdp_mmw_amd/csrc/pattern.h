@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/mmw_hip.h"
+
 namespace mmw {
 
 struct HostPattern {
@@ -244,6 +246,23 @@ static inline std::string build_pattern(HostPattern& P, int32_t K, int32_t Z, co
             }
     }
     return "";
+}
+
+// the int32 list behind an MMW_I_* field of the read entries (null: no such field)
+inline const std::vector<int32_t>* host_list_i32(const HostPattern& H, int which) {
+    switch (which) {
+        case MMW_I_L_INDPTR: return &H.l_indptr;
+        case MMW_I_L_INDICES: return &H.l_indices;
+        case MMW_I_ST_INDPTR: return &H.st_indptr;
+        case MMW_I_ST_INDICES: return &H.st_indices;
+        case MMW_I_GAIN_X: return &H.gain_x;
+        case MMW_I_GAIN_Y: return &H.gain_y;
+        case MMW_I_ASSO_X: return &H.asso_x;
+        case MMW_I_ASSO_Y: return &H.asso_y;
+        case MMW_I_DIAG_POS: return &H.diag_pos;
+        case MMW_I_ASSO_POS: return &H.asso_pos;
+        default: return nullptr;
+    }
 }
 
 }  // namespace mmw

@@ -6,9 +6,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <map>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -44,6 +47,50 @@ inline int fail(int code, const std::string& msg) {
         int rc__ = (expr);         \
         if (rc__ != MMW_OK) return rc__; \
     } while (0)
+
+// No C++ exception (std::bad_alloc from a host vector, ...) crosses the C boundary: every extern "C" entry runs its body inside this.
+// `prefix` names the entry (the batch entries share their handle's name) in front of the exception's text.
+template <typename F> int guarded(const char* prefix, F&& f) {
+    try {
+        return f();
+    } catch (const std::exception& ex) {
+        return fail(MMW_ERR_ARG, std::string(prefix) + ": " + ex.what());
+    } catch (...) {
+        return fail(MMW_ERR_ARG, std::string(prefix) + ": unknown exception");
+    }
+}
+
+// an entry that refuses null pointers (`bad`) with `msg` and then is one call: both inside the guard, under the name `who`
+template <typename F> int entry(const char* who, bool bad, const char* msg, F&& call) {
+    return guarded(who, [&]() -> int { return bad ? fail(MMW_ERR_ARG, msg) : call(); });
+}
+
+inline int device_count(int* n) {
+    if (!n) return fail(MMW_ERR_ARG, "null pointer");
+    int c = 0;
+    hipError_t e = hipGetDeviceCount(&c);
+    if (e != hipSuccess) {
+        *n = 0;
+        return fail(MMW_ERR_HIP, std::string("hipGetDeviceCount failed: ") + hipGetErrorString(e));
+    }
+    *n = c;
+    return MMW_OK;
+}
+// `device` names a visible HIP device, or the entry `who` refuses it; the entries differ in how much the refusal says
+enum DeviceText { DEV_BARE, DEV_ID, DEV_ID_VISIBLE };
+inline int check_device(const char* who, int device, DeviceText text) {
+    int ndev = 0;
+    MMW_TRY(device_count(&ndev));
+    if (device >= 0 && device < ndev) return MMW_OK;
+    std::string msg = std::string(who) + ": no such HIP device";
+    if (text != DEV_BARE) msg += " " + std::to_string(device);
+    if (text == DEV_ID_VISIBLE) msg += " (" + std::to_string(ndev) + " visible)";
+    return fail(MMW_ERR_HIP, msg);
+}
+struct ScopedStream {  // a stream of a handle-less call
+    hipStream_t s = nullptr;
+    ~ScopedStream() { if (s) (void)hipStreamDestroy(s); }
+};
 
 // Per-device one-time setup.  A kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) and the CU count belong to the
 // CURRENT device, and handles of one process may sit on different devices and be driven from different host threads (bench.py's
@@ -142,6 +189,13 @@ inline int copy_d2h(void* dst_host, const void* src_dev, size_t bytes, hipStream
     MMW_HIP(hipMemcpyAsync(L.b->p, src_dev, bytes, hipMemcpyDeviceToHost, st));
     MMW_HIP(hipStreamSynchronize(st));
     memcpy(dst_host, L.b->p, bytes);
+    return MMW_OK;
+}
+
+// a host vector handed out by a read entry `who`, whose caller must have announced its exact length
+template <typename V> int export_vec(const std::vector<V>& v, V* out, int64_t have, const char* who) {
+    if ((int64_t)v.size() != have) return fail(MMW_ERR_ARG, std::string(who) + ": wrong length");
+    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(V));
     return MMW_OK;
 }
 
@@ -249,6 +303,83 @@ struct KernelTimers {
     }
     void clear() { for (int i = 0; i < KT_NSLOT; ++i) { total_us[i] = 0; count[i] = 0; } }
 };
+
+// Phase timers of the loop (mmw_set_timing): four events per timed iteration on the solver's stream, one row of MMW_F_PHASE_US per iteration.
+// Timing every iteration costs the loop four event records per iteration (each one a barrier packet between two launches of
+// the dependent chain).  With a stride S > 1 only iteration 0 and the iterations i = S/2 (mod S) carry events; every other row of
+// MMW_F_PHASE_US repeats the sample of its group of S iterations (the harness takes means over the rows, sim_mmw_time.py:48-52).
+struct PhaseTimers {
+    bool timing = false;
+    int timing_stride = 1;
+    std::vector<hipEvent_t> events;      // 4 per timed iteration
+    std::vector<hipEvent_t> event_pool;  // events of earlier runs, kept for reuse
+    std::vector<int> ev_iter;            // iteration of every group of four pending events
+    struct PhaseSample { int it; double us[4]; };
+    std::vector<PhaseSample> phase_samples;  // the iterations that carried events (set_timing)
+    std::vector<double> phase_us;
+    ~PhaseTimers() {
+        for (auto e : events) (void)hipEventDestroy(e);
+        for (auto e : event_pool) (void)hipEventDestroy(e);
+    }
+    bool timed(int iter) const { return timing && (timing_stride <= 1 || iter == 0 || iter % timing_stride == timing_stride / 2); }
+    void clear_samples() { phase_us.clear(); phase_samples.clear(); }
+    int record(int slot, int iter, hipStream_t st) {
+        if (!timed(iter)) return MMW_OK;
+        if (slot == 0) ev_iter.push_back(iter);
+        hipEvent_t e;
+        if (!event_pool.empty()) {  // events are kept across runs: creating four per iteration cost the class path ~20 us per iteration
+            e = event_pool.back();
+            event_pool.pop_back();
+        } else
+            MMW_HIP(hipEventCreate(&e));
+        MMW_HIP(hipEventRecord(e, st));
+        events.push_back(e);
+        return MMW_OK;
+    }
+    // the events recorded so far / dropping those recorded since (the timers of a discarded chunk; earlier chunks keep theirs)
+    size_t mark() const { return events.size(); }
+    int drop_since(size_t mark0, hipStream_t st) {
+        if (!timing) return MMW_OK;
+        MMW_HIP(hipStreamSynchronize(st));
+        for (size_t i = mark0; i < events.size(); ++i) event_pool.push_back(events[i]);
+        events.resize(std::min(events.size(), mark0));
+        ev_iter.resize(events.size() / 4);
+        return MMW_OK;
+    }
+    int flush(int iter, hipStream_t st) {  // `iter`: iterations done
+        if (events.empty()) return MMW_OK;
+        MMW_HIP(hipStreamSynchronize(st));
+        for (size_t i = 0; i + 3 < events.size(); i += 4) {
+            float a = 0, b = 0, c = 0, t = 0;
+            MMW_HIP(hipEventElapsedTime(&a, events[i], events[i + 1]));
+            MMW_HIP(hipEventElapsedTime(&b, events[i + 1], events[i + 2]));
+            MMW_HIP(hipEventElapsedTime(&c, events[i + 2], events[i + 3]));
+            MMW_HIP(hipEventElapsedTime(&t, events[i], events[i + 3]));
+            phase_samples.push_back({ev_iter[i / 4], {a * 1e3, b * 1e3, c * 1e3, t * 1e3}});
+        }
+        for (auto e : events) event_pool.push_back(e);
+        events.clear();
+        ev_iter.clear();
+        // one row per iteration done: its own sample, else the sample of its group of `timing_stride` iterations, else the nearest one
+        phase_us.clear();
+        if (phase_samples.empty()) return MMW_OK;
+        std::sort(phase_samples.begin(), phase_samples.end(), [](const PhaseSample& x, const PhaseSample& y) { return x.it < y.it; });
+        const int S = std::max(1, timing_stride);
+        for (int i = 0; i < iter; ++i) {
+            const int want = (i == 0 || S <= 1) ? i : (i / S) * S + S / 2;
+            const PhaseSample* best = nullptr;
+            for (const PhaseSample& q : phase_samples) {
+                if (q.it == want) { best = &q; break; }
+                if (q.it == 0 && i != 0 && phase_samples.size() > 1) continue;  // the first iteration of a run is not like the others
+                if (!best || std::abs(q.it - i) < std::abs(best->it - i)) best = &q;
+            }
+            for (int k = 0; k < 4; ++k) phase_us.push_back(best->us[k]);
+        }
+        return MMW_OK;
+    }
+};
+
+inline double tnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }  // seconds, monotonic
 
 inline int grid_rows(int rows) {  // one wavefront per row, 4 rows per workgroup, grid-stride beyond the cap
     int g = (rows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;

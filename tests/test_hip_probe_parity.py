@@ -4,7 +4,7 @@ test_hip_timed_path.py holds the benchmark's 48-iteration fast path to the CPU o
 
 * the probes of a bisection (`binary_search.py` -> `mmw._run`): 150 iterations in ONE `mmw_iterate` call on a handle that
   `mmw_set_slots` rebinds from probe to probe, at slot counts where the matrix grows fast enough for chunks to be discarded
-  and tried again (`settle` in csrc/mmw_api.hip), and the probe after such a probe, which runs with `replays > 0`;
+  and tried again (`settle` in csrc/solver.h), and the probe after such a probe, which runs with `replays > 0`;
 * the cautious second attempt at a discarded chunk and the synchronous replay behind it, each forced;
 * er-5pct-2k (fp64 and fp32) and er-50k on the chunked device-RNG path, and er-50k's synchronous path.
 

@@ -2,7 +2,7 @@
 
 `mmw_iterate(n > 1, NULL, seed)` is the shipped fast path: chunks enqueued without plan readback, lagged plans, the softmax
 inside the violation pass, row sums of X from the matrix-core SDDMM, and exp(L/2)R as ONE certified first-order product on
-fp16 operands (csrc/mmw_api.hip, `optimistic`).  Every other trajectory test uploads its sketches and therefore runs the
+fp16 operands (csrc/solver.h, `optimistic`).  Every other trajectory test uploads its sketches and therefore runs the
 synchronous path.  Here the run draws its sketches on the device; `mmw_sketch` regenerates the Philox block of every
 (seed, iteration) -- the generator is counter-based, so the blocks are exactly the ones the chunks multiplied -- and the
 CPU oracle (reference loop mmw.py:124-197 restated) follows the same run on them.  Compared: every quantity of the loop

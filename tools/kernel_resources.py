@@ -13,4 +13,4 @@ for b in re.split(r"remark: Function Name: ", t)[1:]:
     name = b.split()[0]
     if want and not any(w in name for w in want): continue
     g = lambda k: (re.search(re.escape(k) + r": (\d+)", b) or [None, "?"])[1]
-    print("%-70s VGPR %3s AGPR %3s spill %2s scratch %3s waves/SIMD %s LDS %6s" % (name[:70], g("VGPRs"), g("AGPRs"), g("VGPRs Spill"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"), g("LDS Size [bytes/block]")))
+    print("%-70s VGPR %3s AGPR %3s spill %2s scratch %3s waves/SIMD %s LDS %6s" % (name, g("VGPRs"), g("AGPRs"), g("VGPRs Spill"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"), g("LDS Size [bytes/block]")))
