@@ -66,6 +66,8 @@ enum mmw_field {
     MMW_F_DUAL_INFO = 19, /* [4]      iterations since mmw_create {whose DUAL phase took the row sums of X from the matrix-core SDDMM instead of a
                              pass of its own, whose softmax ran inside the violation pass, whose exponential was ONE first-order product,
                              ... with the matrix in one fp16 half} */
+    MMW_F_FACTOR_INFO = 20, /* [5]    mmw_batch_factor's record of an instance: {Jacobi sweeps, largest |cos| of a row pair as met in the last sweep (<= 1e-15 when it ended without a rotation),
+                             rank, sigma_rank, sigma_rank+1 (0 if rank = K)}; batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -351,6 +353,41 @@ int mmw_batch_sketch(mmw_batch* b, int32_t inst, uint64_t seed, int32_t iteratio
  * differ.
  */
 int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h);
+/*
+ * The epilogue of a probe inside the batch (csrc/kernels_batch_epilogue.h): X_half and the rounding of every instance in ONE launch
+ * each, one workgroup per instance, instead of one mmw_batch_export + mmw_factor + mmw_round trip per instance.  Opt-in: nothing
+ * else changes, the arenas and every field mmw_batch_read_f64 hands out stay bitwise as they were (the work space is a buffer of
+ * its own, made on first use and sized for the taking instances), and an instance's factor and slots are bitwise independent of its
+ * batch neighbours.  Limits: K <= MMW_BATCH_EPILOGUE_MAX_K and the batch's own D <= 512; a taking instance over the limit is refused
+ * by name with MMW_ERR_ARG before anything runs (it stays on the handle path), a host-only batch answers MMW_ERR_STATE.
+ *
+ * mmw_batch_factor: X_half = U sqrt(S) of the top-`rank` singular triplets of Xbar = (sum of X) / nit (mmw.py:201, 213-216) for every
+ * taking instance, by a dense one-sided Jacobi on the rows of the symmetric Xbar: the row norms at convergence are |lambda|, the
+ * singular values svds ranks by, so a kept set that is mostly negative eigenvalues comes out as svds gives it.  Columns are in
+ * ascending sigma (svds' order); a kept singular value of exactly 0 gives a zero column.  take[B]: non-zero = the instance takes
+ * part, NULL = every active instance.  rank[B]: NULL = min(K - 1, (Z - 1) * rank_radio) (mmw.py:214); 1 <= rank <= K.  An instance
+ * that has not run its `nit` iterations gets MMW_ERR_STATE -- unless xavg[b] is non-NULL (parity mode): then instance b's Xbar is
+ * the nnzL values xavg[b] on its pattern, in MMW_F_XAVG's order (taken as given, not divided; symmetric), instead of the run's.
+ * The factor stays on the device for mmw_batch_round; mmw_batch_read_f64(MMW_F_FACTOR) copies it out ([K*rank], row-major) and
+ * MMW_F_FACTOR_INFO its record.  An instance still rotating at the cap of 30 sweeps keeps its factor and is named on stderr.  The factors of a call stand until the next mmw_batch_factor, mmw_batch_set_slots or mmw_batch_reset.
+ *
+ * mmw_batch_round: sdp_solver.rounding (sdp_solver.py:18-107) of the resident factor of every taking instance (take as above; a
+ * taking instance without a factor gets MMW_ERR_STATE).  Attempt a of instance b draws randv[Z, rank] from Philox keyed by
+ * (seeds[b], a), row-normalised (:48-49); users are visited by descending ||gX_k|| (:51) and take the first slot of their descending
+ * inprod order (:56-57, ties to the lower slot) that passes the three checks of :78-92, as mmw_round.  Attempts run one after
+ * another; stop_at_first != 0 ends an instance after its first attempt that leaves nobody over (:23-24).  z_out: nattempt * K slots
+ * per TAKING instance, instance after instance, attempt-major; -1 = the user was left unassigned (the caller draws those,
+ * :104-105), -2 = the attempt was not run.  rem_out[B * nattempt]: users left over per attempt (-1: not run, or the instance did
+ * not take part); used_out[B]: attempts run.
+ *
+ * mmw_batch_round_randv: the randv[Z * rank] that attempt `attempt` of instance `inst` draws with `seed`, bitwise (n must be
+ * Z * rank of the instance's resident factor).
+ */
+#define MMW_BATCH_EPILOGUE_MAX_K 1024
+int mmw_batch_factor(mmw_batch* b, const int32_t* take, const int32_t* rank, const double* const* xavg);
+int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out,
+                    int32_t* rem_out, int32_t* used_out);
+int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n);
 
 #ifdef __cplusplus
 }

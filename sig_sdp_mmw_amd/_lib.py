@@ -18,6 +18,8 @@ EXPM_LANCZOS, EXPM_TAYLOR = 0, 1
 # enum mmw_field / mmw_ifield
 F_Y, F_E_ACCU, F_E_THIS, F_LVAL, F_XVAL, F_XAVG, F_YAVG, F_XHALF, F_SKETCH = range(9)
 F_S_SUM, F_NORM_H, F_ST_DATA, F_PHASE_US, F_EXPM_INFO, F_FACTOR, F_KERNEL_US, F_BLOCKING, F_SPMM_KIND, F_E_MAX, F_DUAL_INFO = range(9, 20)
+F_FACTOR_INFO = 20
+BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
 
@@ -27,7 +29,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds", "mmw_gm_create", "mmw_gm_destroy", "mmw_gm_sizes", "mmw_gm_pass",
            "mmw_gm_run", "mmw_gm_assign", "mmw_batch_create", "mmw_batch_destroy", "mmw_batch_sizes", "mmw_batch_set_slots",
            "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
-           "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap"]
+           "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
+           "mmw_batch_round_randv"]
 
 
 class MMWError(RuntimeError):
@@ -106,6 +109,9 @@ def lib():
     L.mmw_batch_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mmw_batch_set_gap.argtypes = [C.c_void_p, C.c_int, C.c_int32]
     L.mmw_batch_read_gap.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_int64]
+    L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
+    L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
+    L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -523,6 +529,75 @@ class BatchSolver:
         """The instance's iterate into `solver` (an fp64 `Solver` of the same state and Z), which then factors / rounds it."""
         check(lib().mmw_batch_export(self._h, int(inst), solver._h))
         solver._timed = 0
+
+    # ---- the epilogue inside the batch (csrc/kernels_batch_epilogue.h): one launch for all factors, one for all roundings
+    def _take(self, take):
+        if take is None:
+            return None, [i for i in range(self.B) if self.active[i]]
+        t = _i32([1 if x else 0 for x in take])
+        if t.size != self.B:
+            raise MMWError("take: one flag per instance")
+        return t, [i for i in range(self.B) if t[i]]
+
+    def factor(self, take=None, ranks=None, xavg=None):
+        """X_half of every taking instance (take: one flag per instance, None = every active one) in one launch; it stays on the
+        device for `round`, `read_factor(i)` copies it out.  ranks: one per instance (None: min(K-1, (Z-1) rank_radio)).  xavg: parity
+        mode, a list with per instance None or its Xbar values on the pattern (F_XAVG's order) to factor instead of the run's."""
+        t, _ = self._take(take)
+        r = None if ranks is None else _i32(ranks)
+        if r is not None and r.size != self.B:
+            raise MMWError("factor: one rank per instance")
+        xp, keep = None, []
+        if xavg is not None:
+            if len(xavg) != self.B:
+                raise MMWError("factor: one entry per instance in xavg")
+            xp = (C.POINTER(C.c_double) * self.B)()
+            for i, x in enumerate(xavg):
+                if x is None:
+                    continue
+                a = _f64(x).ravel()
+                if a.size != self.sizes[i]["nnzL"]:
+                    raise MMWError("factor: xavg of instance %d must hold nnzL = %d values" % (i, self.sizes[i]["nnzL"]))
+                keep.append(a)
+                xp[i] = _pd(a)
+        check(lib().mmw_batch_factor(self._h, None if t is None else _pi(t), None if r is None else _pi(r), xp))
+
+    def factor_info(self, inst):
+        """{"sweeps", "max_cos" (largest |cos| of a row pair as met in the last sweep), "rank", "sigma_rank", "sigma_next"} of the last factor."""
+        v = self.read(inst, F_FACTOR_INFO, 5)
+        return {"sweeps": int(v[0]), "max_cos": float(v[1]), "rank": int(v[2]), "sigma_rank": float(v[3]), "sigma_next": float(v[4])}
+
+    def read_factor(self, inst):
+        """X_half (K, rank) of the instance's last `factor`, columns in ascending singular value."""
+        rank = self.factor_info(inst)["rank"]
+        K = self.sizes[inst]["K"]
+        return self.read(inst, F_FACTOR, K * rank).reshape(K, rank)
+
+    def round(self, nattempt, seeds, take=None, stop_at_first=True):
+        """sdp_solver.rounding of every taking instance's resident factor in one launch, attempt a of instance i drawn from
+        (seeds[i], a).  Returns (z, rem, used): z[i] is None or int32 (nattempt, K) with -1 = unassigned and -2 = attempt not run,
+        rem int32 (B, nattempt) with -1 = not run, used int32 (B,) attempts run."""
+        t, who = self._take(take)
+        nattempt = int(nattempt)
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
+        zflat = np.empty(max(1, nattempt * sum(self.sizes[i]["K"] for i in who)), dtype=np.int32)
+        rem = np.empty((self.B, max(1, nattempt)), dtype=np.int32)
+        used = np.empty(self.B, dtype=np.int32)
+        check(lib().mmw_batch_round(self._h, None if t is None else _pi(t), nattempt, 1 if stop_at_first else 0,
+                                    sd.ctypes.data_as(C.POINTER(C.c_uint64)), _pi(zflat), _pi(rem), _pi(used)))
+        z, o = [None] * self.B, 0
+        for i in who:
+            K = self.sizes[i]["K"]
+            z[i] = zflat[o:o + nattempt * K].reshape(nattempt, K)
+            o += nattempt * K
+        return z, rem, used
+
+    def round_randv(self, inst, seed, attempt):
+        """The (Z, rank) row-normalised projection vectors attempt `attempt` of `round` draws for the instance with `seed`, bitwise."""
+        Z, rank = self.sizes[inst]["Z"], self.factor_info(inst)["rank"]
+        out = np.empty((Z, rank), dtype=np.float64)
+        check(lib().mmw_batch_round_randv(self._h, int(inst), C.c_uint64(int(seed)), int(attempt), _pd(out), int(out.size)))
+        return out
 
 
 class DeviceFactor(np.lib.mixins.NDArrayOperatorsMixin):

@@ -6,8 +6,12 @@ sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_searc
 
     curves   = convergence_many(Zs, states, nit=625, eta=0.04)                         # [{"gap": [nit, 3], "lanczos_steps": [nit]}, ...]
 
-The iterations of every instance run in one launch per call; X_half comes from the tested per-handle epilogue: the instance's
-iterate is exported into an fp64 handle of the same state (mmw_batch_export) and `mmw_factor` / `mmw_round` run there.
+The iterations of every instance run in one launch per call.  The epilogue of a probe (X_half and the rounding) is chosen by
+`epilogue=`: "handle" (the default) exports the instance's iterate into an fp64 handle of the same state (mmw_batch_export) and runs
+`mmw_factor` / `mmw_round` there, one instance after another; "batch" runs both inside the batch (csrc/kernels_batch_epilogue.h):
+a round of probes is then one `iterate`, one `factor` and one `round`, and instances over `_lib.BATCH_EPILOGUE_MAX_K` take the
+handle path inside the same call.  The two factor by different methods, so their bases differ: the same bisection, not bitwise
+the same slots.
 
 `search_many` runs the bisection of binary_search_relaxation.py:44-72 for all instances in lockstep: each instance keeps its own
 bounds, all current probes run in one `mmw_batch_iterate`, and an instance whose search has ended sits out.  Sketches are the
@@ -16,6 +20,7 @@ way, so `single(state, index)` -- the reference's `run_with_state` / `rounding` 
 `binary_search_relaxation` makes the same probes and ends at the same Z (instances are bitwise independent of their batch).
 """
 import math
+import time
 
 import numpy as np
 
@@ -75,16 +80,43 @@ def _round(handle, Z, X_half, state, seed, nattempt):
     return z_vec, Z, int(rem[a])
 
 
-def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0):
+def _check_epilogue(epilogue):
+    if epilogue not in ("handle", "batch"):
+        raise ValueError('epilogue must be "handle" or "batch", got %r' % (epilogue,))
+    return epilogue == "batch"
+
+
+def _fits(b, i):
+    return b.sizes[i]["K"] <= _lib.BATCH_EPILOGUE_MAX_K
+
+
+def _finish(z, rem, used, i, Z, seed):
+    """The attempt sdp_solver.rounding returns (sdp_solver.py:21-25: the first with remainder 0, else the last) out of a batch `round`,
+    users left over drawn from a generator keyed by the probe seed (:104-105)."""
+    a = int(used[i]) - 1
+    z_vec = z[i][a].astype(np.float64)
+    un = z[i][a] < 0
+    if np.any(un):
+        z_vec[un] = np.random.default_rng(seed).integers(0, Z, int(un.sum()))
+    return z_vec, Z, int(rem[i][a])
+
+
+def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle"):
     """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
-    X_half per instance through export + mmw_factor on one reused fp64 handle per state.  Returns [(True, X_half), ...]."""
+    X_half per instance through export + mmw_factor on one reused fp64 handle per state, or with epilogue="batch" all of them in one
+    more launch (instances over the epilogue limit still go through a handle).  Returns [(True, X_half), ...]."""
     del bs_iteration  # the log index of the reference's signature; nothing here depends on it
+    in_batch = _check_epilogue(epilogue)
     seeds = np.arange(len(states), dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
     b = _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device)
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
         b.iterate(nit, None, seeds)
-        return [(True, _factor(b, i, hs.get(i, int(Z)), int(Z), rank_radio, factor_seed)) for i, Z in enumerate(Zs)]
+        take = [in_batch and _fits(b, i) for i in range(len(states))]
+        if any(take):
+            b.factor(take)
+        return [(True, b.read_factor(i) if take[i] else _factor(b, i, hs.get(i, int(Z)), int(Z), rank_radio, factor_seed))
+                for i, Z in enumerate(Zs)]
     finally:
         hs.close()
         b.close()
@@ -113,9 +145,13 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0):
         b.close()
 
 
-def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0):
+def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
-    Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}."""
+    Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
+    factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
+    one {"probes", "iterate_s", "epilogue_s"} per round (epilogue_s: everything of the round after `iterate`, the bisection's own
+    bookkeeping included)."""
+    in_batch = _check_epilogue(epilogue)
     B = len(states)
     bs = binary_search_relaxation()
     bounds = [bs.set_bounds(st) for st in states]
@@ -132,19 +168,30 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
             b.set_slots(mids, nit)
             seeds = np.array([probe_seed(seed, i, len(probes[i])) for i in range(B)], dtype=np.uint64)
+            t0 = time.perf_counter()
             b.iterate(nit, None, seeds)
+            t1 = time.perf_counter()
+            take = [in_batch and not done[i] and _fits(b, i) for i in range(B)]
+            if any(take):
+                b.factor(take)
+                zs, rems, used = b.round(nattempt, seeds, take)
             for i in range(B):
                 if done[i]:
                     continue
                 Z = mids[i]
-                h = hs.get(i, Z)
-                Xh = _factor(b, i, h, Z, rank_radio, 0)
-                z_vec, Z, rem = _round(h, Z, Xh, states[i], probe_seed(seed, i, len(probes[i])), nattempt)
+                if take[i]:
+                    z_vec, Z, rem = _finish(zs, rems, used, i, Z, int(seeds[i]))
+                else:
+                    h = hs.get(i, Z)
+                    Xh = _factor(b, i, h, Z, rank_radio, 0)
+                    z_vec, Z, rem = _round(h, Z, Xh, states[i], probe_seed(seed, i, len(probes[i])), nattempt)
                 probes[i].append(Z)
                 left[i], right[i], fin = binary_search_relaxation._step(left[i], right[i], Z, rem)
                 if fin:
                     done[i] = True
                     out[i] = {"Z": Z, "z_vec": z_vec, "remainder": rem, "probes": probes[i], "bounds": bounds[i]}
+            if timings is not None:
+                timings.append({"probes": int(sum(1 for m in mids if m > 0)), "iterate_s": t1 - t0, "epilogue_s": time.perf_counter() - t1})
         return out
     finally:
         hs.close()
@@ -155,9 +202,10 @@ class single:
     """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
     one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0):
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle"):
         self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
         self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
+        self._in_batch = _check_epilogue(epilogue) and state[0].shape[0] <= _lib.BATCH_EPILOGUE_MAX_K
         self.probes = []
         self._b = None
         self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
@@ -168,10 +216,18 @@ class single:
             self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
         self._b.set_slots([Z], self.nit)
         self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])
+        if self._in_batch:
+            self._b.factor()
+            return True, self._b.read_factor(0)
         self._h = self._hs.get(0, Z)
         return True, _factor(self._b, 0, self._h, Z, self.rank_radio, 0)
 
     def rounding(self, Z, gX, state):
+        if self._in_batch:  # the factor `run_with_state` just made is resident in the batch: gX is its copy
+            sd = probe_seed(self.seed, self.index, len(self.probes))
+            z_vec, Z, rem = _finish(*self._b.round(self.nattempt, [sd]), 0, int(Z), sd)
+            self.probes.append(int(Z))
+            return z_vec, Z, rem
         z_vec, Z, rem = _round(self._h, int(Z), gX, state, probe_seed(self.seed, self.index, len(self.probes)), self.nattempt)
         self.probes.append(int(Z))
         return z_vec, Z, rem

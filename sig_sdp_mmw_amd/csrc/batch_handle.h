@@ -4,6 +4,7 @@
 #include <limits>
 
 #include "kernels_batch.h"
+#include "kernels_batch_epilogue.h"
 #include "solver.h"
 
 struct mmw_batch {
@@ -26,6 +27,15 @@ struct mmw_batch {
     std::vector<GapDesc> gdesc;
     DevBuf<double> ga;
     DevBuf<GapDesc> d_gdesc;
+    // the epilogue (mmw_batch_factor / mmw_batch_round, kernels_batch_epilogue.h): buffers of its own, made on first use and sized for
+    // the taking instances of the call; the state's rounding lists go up once (they do not depend on the slot count)
+    std::vector<FactorDesc> fdesc;  // per instance: where its factor of the last mmw_batch_factor lies (rank 0: none)
+    DevBuf<double> ew, rw, rs_f, rvbuf;
+    DevBuf<int> ei, ri, rs_i;
+    DevBuf<FactorDesc> d_fdesc;
+    DevBuf<RoundDesc> d_rdesc;
+    struct RoundLists { int64_t soptr, soidx, qptr, qidx, sodata, sohmax, hmax; };
+    std::vector<RoundLists> rlists;
     ~mmw_batch() {
         if (host_only || !st) return;
         (void)hipSetDevice(device);
@@ -161,6 +171,7 @@ struct mmw_batch {
             MMW_TRY(reset_one(b));
         }
         if (gap_ever) MMW_TRY(gap_layout());  // an empty log for the new run
+        fdesc.clear();
         return MMW_OK;
     }
     int reset_one(int b) {
@@ -224,6 +235,7 @@ struct mmw_batch {
             MMW_TRY(reset_one(b));
         }
         if (gap_ever) MMW_TRY(gap_layout());
+        fdesc.clear();
         return MMW_OK;
     }
     int check_inst(int b) const {
@@ -261,6 +273,15 @@ struct mmw_batch {
                 if (iter[b] == 0) return fail(MMW_ERR_STATE, "mmw_batch_read_f64: no iteration has run on this instance");
                 return read_dev(d.o_R, KD, out, n);
             case MMW_F_EXPM_INFO: return read_dev(d.o_info, 4, out, n);
+            case MMW_F_FACTOR:
+            case MMW_F_FACTOR_INFO: {
+                if (fdesc.empty() || fdesc[b].rank == 0) return fail(MMW_ERR_STATE, "mmw_batch_read_f64: instance " + std::to_string(b) + " has no factor (mmw_batch_factor)");
+                const FactorDesc& f = fdesc[b];
+                const int64_t len = which == MMW_F_FACTOR ? (int64_t)f.K * f.rank : EPI_INFO;
+                if (n != len) return fail(MMW_ERR_ARG, "mmw_batch_read_f64: wrong length " + std::to_string(n) + ", expected " + std::to_string(len));
+                MMW_HIP(hipSetDevice(device));
+                return copy_d2h(out, ew.p + (which == MMW_F_FACTOR ? f.o_fac : f.o_info), (size_t)len * sizeof(double), st);
+            }
             default: return fail(MMW_ERR_ARG, "mmw_batch_read_f64: field not held by a batch");
         }
     }
@@ -281,6 +302,178 @@ struct mmw_batch {
         hipLaunchKernelGGL(k_batch_sketch, dim3(1), dim3(BATCH_THREADS), 0, st, d.K, d.D, seed, (uint32_t)iteration, skbuf.p);
         MMW_HIP(hipGetLastError());
         return copy_d2h(out, skbuf.p, (size_t)KD * sizeof(double), st);
+    }
+    // ---- the epilogue on the device
+    int takers(const char* who, const int32_t* take, std::vector<int>& tk) const {
+        tk.clear();
+        for (int b = 0; b < B; ++b) {
+            if (take ? take[b] == 0 : !active[b]) continue;
+            if (!active[b]) return fail(MMW_ERR_STATE, std::string(who) + ": instance " + std::to_string(b) + " sits out (mmw_batch_set_slots gave it no slot count)");
+            tk.push_back(b);
+        }
+        if (tk.empty()) return fail(MMW_ERR_ARG, std::string(who) + ": no instance takes part");
+        return MMW_OK;
+    }
+    int factor(const int32_t* take, const int32_t* rank, const double* const* xavg) {
+        if (host_only) return host_only_batch();
+        std::vector<int> tk;
+        MMW_TRY(takers("mmw_batch_factor", take, tk));
+        std::vector<int> rk(B, 0);
+        for (int b : tk) {
+            const BatchDesc& d = desc[b];
+            const std::string who = "mmw_batch_factor: instance " + std::to_string(b);
+            if (d.K > EPI_MAX_K) return fail(MMW_ERR_ARG, who + ": K = " + std::to_string(d.K) + " exceeds the epilogue limit " + std::to_string(EPI_MAX_K) + " (factor it on a handle: mmw_batch_export)");
+            if (!(xavg && xavg[b]) && iter[b] < nit[b])
+                return fail(MMW_ERR_STATE, who + " has run " + std::to_string(iter[b]) + " of its " + std::to_string(nit[b]) + " iterations");
+            rk[b] = rank ? rank[b] : std::min(d.K - 1, (d.Z - 1) * rank_radio);
+            if (rk[b] < 1 || rk[b] > d.K) return fail(MMW_ERR_ARG, who + ": rank must be in [1, K]");
+        }
+        auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };
+        std::vector<FactorDesc> fd(B, FactorDesc{});
+        std::vector<FactorDesc> launch;
+        int64_t of = a32((int64_t)tk.size() * EPI_INFO_STRIDE), oi = 0;  // the records first, side by side: one copy brings them back
+        int64_t ninfo = 0;
+        for (int b : tk) {
+            const BatchDesc& d = desc[b];
+            FactorDesc& f = fd[b];
+            const int64_t K = d.K;
+            f.o_info = EPI_INFO_STRIDE * ninfo++;
+            f.K = d.K; f.rank = rk[b]; f.nnzL = d.nnzL; f.cap = EPI_SWEEP_CAP;
+            f.o_lrow = d.o_lrow; f.o_col = d.o_col;
+            const bool parity = xavg && xavg[b];
+            f.src_work = parity ? 1 : 0;
+            f.div = parity ? 1.0 : (double)nit[b];
+            f.o_src = d.o_xavg;
+            if (parity) { f.o_src = of; of = a32(of + d.nnzL); }
+            f.o_A = of; of = a32(of + K * K);
+            f.o_fac = of; of = a32(of + K * f.rank);
+            f.o_nrm = of; of = a32(of + K);
+            f.o_ord = oi; oi = a32(oi + K);
+            launch.push_back(f);
+        }
+        fdesc.clear();  // the buffers are laid out anew: earlier factors are gone whatever happens below
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(ew.alloc((size_t)of));
+        MMW_TRY(ei.alloc((size_t)oi));
+        for (int b : tk)
+            if (fd[b].src_work) MMW_TRY(copy_h2d(ew.p + fd[b].o_src, xavg[b], (size_t)fd[b].nnzL * sizeof(double), st));
+        MMW_TRY(d_fdesc.alloc(launch.size()));
+        MMW_TRY(copy_h2d(d_fdesc.p, launch.data(), launch.size() * sizeof(FactorDesc), st));
+        hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, st, d_fdesc.p, ia.p, fa.p, ew.p, ei.p);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        // A factor that used up its sweeps while rows still rotated is handed out (its rows are orthogonal to the |cos| it reports),
+        // and said so: nothing above looks at the record on its own.
+        std::vector<double> rec((size_t)tk.size() * EPI_INFO_STRIDE);
+        MMW_TRY(copy_d2h(rec.data(), ew.p, rec.size() * sizeof(double), st));
+        for (size_t t = 0; t < tk.size(); ++t) {
+            const double* r = rec.data() + t * EPI_INFO_STRIDE;
+            if (r[0] >= EPI_SWEEP_CAP && r[1] > EPI_ROT_TOL)
+                fprintf(stderr, "mmw_batch_factor: instance %d (K = %d): still rotating after the cap of %d sweeps, largest |cos| of a row pair %.3g\n",
+                        tk[t], desc[tk[t]].K, EPI_SWEEP_CAP, r[1]);
+        }
+        fdesc = std::move(fd);
+        return MMW_OK;
+    }
+    // the state's rounding lists (S_gain without its diagonal, Q_asso, h_max: csrc/pattern.h), all instances, once
+    int round_lists() {
+        if (!rlists.empty()) return MMW_OK;
+        std::vector<RoundLists> rl(B);
+        std::vector<int> hi;
+        std::vector<double> hf;
+        auto pad = [](auto& v) { v.resize((v.size() + 31) & ~(size_t)31); };
+        for (int b = 0; b < B; ++b) {
+            const HostPattern& P = H[b];
+            RoundLists& r = rl[b];
+            r.soptr = (int64_t)hi.size(); hi.insert(hi.end(), P.so_indptr.begin(), P.so_indptr.end());
+            r.soidx = (int64_t)hi.size(); hi.insert(hi.end(), P.so_indices.begin(), P.so_indices.end());
+            r.qptr = (int64_t)hi.size(); hi.insert(hi.end(), P.q_indptr.begin(), P.q_indptr.end());
+            r.qidx = (int64_t)hi.size(); hi.insert(hi.end(), P.q_indices.begin(), P.q_indices.end());
+            pad(hi);
+            r.sodata = (int64_t)hf.size(); hf.insert(hf.end(), P.so_data.begin(), P.so_data.end());
+            r.sohmax = (int64_t)hf.size();
+            for (int32_t n : P.so_indices) hf.push_back(P.h_max[n]);
+            r.hmax = (int64_t)hf.size(); hf.insert(hf.end(), P.h_max.begin(), P.h_max.end());
+            pad(hf);
+        }
+        MMW_TRY(rs_i.upload(hi, st));
+        MMW_TRY(rs_f.upload(hf, st));
+        rlists = std::move(rl);
+        return MMW_OK;
+    }
+    int round(const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+        if (host_only) return host_only_batch();
+        if (nattempt < 1 || nattempt > 4096) return fail(MMW_ERR_ARG, "mmw_batch_round: nattempt must be in [1, 4096]");
+        std::vector<int> tk;
+        MMW_TRY(takers("mmw_batch_round", take, tk));
+        for (int b : tk)
+            if (fdesc.empty() || fdesc[b].rank == 0 || fdesc[b].K != desc[b].K)
+                return fail(MMW_ERR_STATE, "mmw_batch_round: instance " + std::to_string(b) + " has no factor (mmw_batch_factor)");
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(round_lists());
+        auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };
+        std::vector<RoundDesc> rd;
+        int64_t of = 0, oi = 0;
+        for (int b : tk) oi += (int64_t)nattempt * fdesc[b].K + nattempt + 1;  // slots, remainders and attempts run of every instance: what goes back
+        const int64_t nback = oi;
+        oi = a32(oi);
+        int64_t oz = 0;
+        for (int b : tk) {
+            const FactorDesc& f = fdesc[b];
+            const RoundLists& l = rlists[b];
+            const int64_t K = f.K, Z = desc[b].Z;
+            RoundDesc r{};
+            r.K = f.K; r.Z = desc[b].Z; r.Dp = f.rank; r.nattempt = nattempt; r.stop_first = stop_at_first != 0;
+            r.seed = seeds[b];
+            r.o_fac = f.o_fac;
+            r.s_soptr = l.soptr; r.s_soidx = l.soidx; r.s_qptr = l.qptr; r.s_qidx = l.qidx;
+            r.s_sodata = l.sodata; r.s_sohmax = l.sohmax; r.s_hmax = l.hmax;
+            r.r_randv = of; of = a32(of + Z * f.rank);
+            r.r_inprod = of; of = a32(of + K * Z);
+            r.r_gain = of; of = a32(of + K * Z);
+            r.r_nrm = of; of = a32(of + K);
+            r.r_order = oi; oi = a32(oi + K);
+            r.r_pref = oi; oi = a32(oi + K * Z);
+            r.r_z = oz; oz += (int64_t)nattempt * K;
+            r.r_rem = oz; oz += nattempt + 1;
+            rd.push_back(r);
+        }
+        MMW_TRY(rw.alloc((size_t)of));
+        MMW_TRY(ri.alloc((size_t)oi));
+        MMW_TRY(d_rdesc.alloc(rd.size()));
+        MMW_TRY(copy_h2d(d_rdesc.p, rd.data(), rd.size() * sizeof(RoundDesc), st));
+        hipLaunchKernelGGL(k_batch_round, dim3((unsigned)rd.size()), dim3(BATCH_THREADS), 0, st, d_rdesc.p, ew.p, rs_i.p, rs_f.p, rw.p, ri.p);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        std::vector<int> host((size_t)nback);
+        MMW_TRY(copy_d2h(host.data(), ri.p, host.size() * sizeof(int), st));
+        for (int b = 0; b < B; ++b) {
+            used_out[b] = 0;
+            for (int a = 0; a < nattempt; ++a) rem_out[(size_t)b * nattempt + a] = -1;
+        }
+        int32_t* z = z_out;
+        for (size_t t = 0; t < tk.size(); ++t) {
+            const RoundDesc& r = rd[t];
+            const size_t nz = (size_t)nattempt * r.K;
+            std::copy(host.begin() + r.r_z, host.begin() + r.r_z + nz, z);
+            z += nz;
+            std::copy(host.begin() + r.r_rem, host.begin() + r.r_rem + nattempt, rem_out + (size_t)tk[t] * nattempt);
+            used_out[tk[t]] = host[r.r_rem + nattempt];
+        }
+        return MMW_OK;
+    }
+    int round_randv(int b, uint64_t seed, int32_t attempt, double* out, int64_t n) {
+        MMW_TRY(check_inst(b));
+        if (host_only) return host_only_batch();
+        if (attempt < 0) return fail(MMW_ERR_ARG, "mmw_batch_round_randv: attempt must be >= 0");
+        if (fdesc.empty() || fdesc[b].rank == 0) return fail(MMW_ERR_STATE, "mmw_batch_round_randv: instance " + std::to_string(b) + " has no factor (mmw_batch_factor)");
+        const int Z = desc[b].Z, Dp = fdesc[b].rank;
+        if (n != (int64_t)Z * Dp) return fail(MMW_ERR_ARG, "mmw_batch_round_randv: wrong length for a Z x rank block");
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(rvbuf.alloc((size_t)n));
+        hipLaunchKernelGGL(k_batch_randv, dim3(1), dim3(BATCH_THREADS), 0, st, Z, Dp, seed, (uint32_t)attempt, rvbuf.p);
+        MMW_HIP(hipGetLastError());
+        return copy_d2h(out, rvbuf.p, (size_t)n * sizeof(double), st);
     }
 };
 // mmw_batch_export: the instance's iterate into an fp64 handle of the same (state, Z), as if the handle had run those iterations.

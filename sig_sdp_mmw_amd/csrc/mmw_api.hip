@@ -247,4 +247,15 @@ int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h) {
         return batch_export_into(b, inst, s);
     });
 }
+int mmw_batch_factor(mmw_batch* b, const int32_t* take, const int32_t* rank, const double* const* xavg) {
+    return entry("mmw_batch", !b, "null batch handle", [&] { return b->factor(take, rank, xavg); });
+}
+int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out,
+                    int32_t* rem_out, int32_t* used_out) {
+    return entry("mmw_batch", !b || !seeds || !z_out || !rem_out || !used_out, "null pointer",
+                 [&] { return b->round(take, nattempt, stop_at_first, seeds, z_out, rem_out, used_out); });
+}
+int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n) {
+    return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->round_randv(inst, seed, attempt, out, n); });
+}
 }  // extern "C"
