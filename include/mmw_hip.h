@@ -389,6 +389,46 @@ int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int sto
                     int32_t* rem_out, int32_t* used_out);
 int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n);
 
+/*
+ * The generator and the scorer for many small instances (csrc/kernels_batch_env.h), one workgroup per instance: the state of
+ * every time point of the reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78 -- per seed and variant,
+ * at 11 time points, alg.rounding(Z_fin, gX, e.generate_S_Q_hmax()) on the stations as they have moved, e.evaluate_bler(z_vec, Z_fin),
+ * e.step_time(...)) without one mmw_env_create, one solver handle and one mmw_env_evaluate per instance and point.  No atomics,
+ * nothing waits across workgroups, every reduction runs in a fixed order: an instance's results are bitwise independent of its
+ * batch neighbours, and its state is bitwise the one mmw_env_create builds at the same positions.
+ * Limits: K <= MMW_BATCH_EPILOGUE_MAX_K, A <= 1024; an instance over the limit is refused by name with MMW_ERR_ARG before anything
+ * runs, and so is device == -1 (there is no host form).
+ *
+ * mmw_batch_env_create: env.__init__'s parameters (sim_src/env/env.py:12-37) for B instances with K[b] stations and the A[b] access
+ * points ap_xy[b][A][2].  It holds no positions yet: every other entry answers MMW_ERR_STATE until the first move.
+ * mmw_batch_env_move: env.generate_S_Q_hmax (env.py:136-196) of every instance for the stations at sta_xy[b][K][2] -- where
+ * mob_env.step_time (sim_src/env/mob_env.py:20-21, env.py:74-87; the caller's, graphs.mobile_drop) has taken them: all positions go
+ * up in one copy, a count pass, one readback of the B totals, the fill pass.  The lists live in a grow-only arena.
+ * mmw_batch_env_sizes / mmw_batch_env_state: mmw_env_sizes / mmw_env_state for instance `inst`.
+ * mmw_batch_env_evaluate: env.evaluate_sinr / evaluate_bler (env.py:198-233) of one colouring z_vec[b][K] with Z[b] slots per
+ * instance, ONE launch for all: interference summed member by member in ascending user order, the one-survivor rule per (AP, slot),
+ * users with z outside [0, Z) keep 1e-3; sinr_out[b][K], and bler_out[b][K] unless bler_out is NULL.
+ *
+ * mmw_batch_round_env: mmw_batch_round (sdp_solver.py:18-107) of the batch's resident factors against the state the environment
+ * holds instead of the one the batch was built from -- the reference's alg.rounding(Z_fin, gX, e.generate_S_Q_hmax()) after
+ * e.step_time (sim_mmw_online.py:43-47).  The factor, the Philox draws (mmw_batch_round_randv stays valid) and the greedy pass are
+ * mmw_batch_round's; take / seeds / z_out / rem_out / used_out as there.  The environment must hold as many instances as the batch,
+ * on the same device; a taking instance whose K differs between the two is refused by name with MMW_ERR_ARG.  Nothing of the
+ * batch changes: the arenas, the resident factors and every mmw_batch_read_* field stay bitwise as they were.
+ */
+typedef struct mmw_batch_env mmw_batch_env;
+int mmw_batch_env_create(mmw_batch_env** out, int device, int32_t B, const int32_t* K, const int32_t* A, const double* const* ap_xy,
+                         double fre_Hz, double txp_offset, double min_s_n_ratio, double min_sinr, double noise_floor_dbm);
+int mmw_batch_env_destroy(mmw_batch_env* e);
+int mmw_batch_env_move(mmw_batch_env* e, const double* const* sta_xy);
+int mmw_batch_env_sizes(mmw_batch_env* e, int32_t inst, int64_t out[4]);
+int mmw_batch_env_state(mmw_batch_env* e, int32_t inst, int32_t* S_indptr, int32_t* S_indices, double* S_data, int32_t* Q_indptr,
+                        int32_t* Q_indices, double* Q_data, double* h_max);
+int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const int32_t* Z, double packet_bit, double bandwidth,
+                           double slot_time, double* const* sinr_out, double* const* bler_out);
+int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first,
+                        const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_gm_run", "mmw_gm_assign", "mmw_batch_create", "mmw_batch_destroy", "mmw_batch_sizes", "mmw_batch_set_slots",
            "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
-           "mmw_batch_round_randv"]
+           "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
+           "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env"]
 
 
 class MMWError(RuntimeError):
@@ -112,6 +113,14 @@ def lib():
     L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
     L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
+    L.mmw_batch_env_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, p_i32, p_i32, pp_f64, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_double]
+    L.mmw_batch_env_destroy.argtypes = [C.c_void_p]
+    L.mmw_batch_env_move.argtypes = [C.c_void_p, pp_f64]
+    L.mmw_batch_env_sizes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+    L.mmw_batch_env_state.argtypes = [C.c_void_p, C.c_int32, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64]
+    L.mmw_batch_env_evaluate.argtypes = [C.c_void_p, pp_f64, p_i32, C.c_double, C.c_double, C.c_double, pp_f64, pp_f64]
+    L.mmw_batch_round_env.argtypes = [C.c_void_p, C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -573,24 +582,30 @@ class BatchSolver:
         K = self.sizes[inst]["K"]
         return self.read(inst, F_FACTOR, K * rank).reshape(K, rank)
 
-    def round(self, nattempt, seeds, take=None, stop_at_first=True):
+    def round(self, nattempt, seeds, take=None, stop_at_first=True, env=None):
         """sdp_solver.rounding of every taking instance's resident factor in one launch, attempt a of instance i drawn from
         (seeds[i], a).  Returns (z, rem, used): z[i] is None or int32 (nattempt, K) with -1 = unassigned and -2 = attempt not run,
-        rem int32 (B, nattempt) with -1 = not run, used int32 (B,) attempts run."""
+        rem int32 (B, nattempt) with -1 = not run, used int32 (B,) attempts run.  env: see `round_env`."""
         t, who = self._take(take)
         nattempt = int(nattempt)
         sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
         zflat = np.empty(max(1, nattempt * sum(self.sizes[i]["K"] for i in who)), dtype=np.int32)
         rem = np.empty((self.B, max(1, nattempt)), dtype=np.int32)
         used = np.empty(self.B, dtype=np.int32)
-        check(lib().mmw_batch_round(self._h, None if t is None else _pi(t), nattempt, 1 if stop_at_first else 0,
-                                    sd.ctypes.data_as(C.POINTER(C.c_uint64)), _pi(zflat), _pi(rem), _pi(used)))
+        args = (None if t is None else _pi(t), nattempt, 1 if stop_at_first else 0, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _pi(zflat), _pi(rem),
+                _pi(used))
+        check(lib().mmw_batch_round(self._h, *args) if env is None else lib().mmw_batch_round_env(self._h, env._h, *args))
         z, o = [None] * self.B, 0
         for i in who:
             K = self.sizes[i]["K"]
             z[i] = zflat[o:o + nattempt * K].reshape(nattempt, K)
             o += nattempt * K
         return z, rem, used
+
+    def round_env(self, env, nattempt, seeds, take=None, stop_at_first=True):
+        """`round` against the state a `BatchEnv` holds (the stations as they have moved) instead of the one the batch was built
+        from: same factors, same draws, same greedy pass (mmw_batch_round_env).  Nothing of the batch changes."""
+        return self.round(nattempt, seeds, take=take, stop_at_first=stop_at_first, env=env)
 
     def round_randv(self, inst, seed, attempt):
         """The (Z, rank) row-normalised projection vectors attempt `attempt` of `round` draws for the instance with `seed`, bitwise."""
@@ -691,6 +706,71 @@ class DeviceEnv:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().mmw_env_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchEnv:
+    """Owning wrapper of one `mmw_batch_env*`: the generator and the scorer (env.py:136-233) for B small instances, one workgroup
+    each (csrc/kernels_batch_env.h).  ap_locs: one (A, 2) array per instance; Ks: stations per instance.  `move` takes the
+    stations' positions, one (K, 2) array per instance, and regenerates every state; until the first move nothing else answers."""
+
+    def __init__(self, ap_locs, Ks, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1, min_sinr=1.0, noise_floor_dbm=-94.0, device=0):
+        aps = [_f64(a) for a in ap_locs]
+        self.B = B = len(aps)
+        if B < 1 or len(Ks) != B or any(a.ndim != 2 or a.shape[1] != 2 for a in aps):
+            raise MMWError("BatchEnv: one (A, 2) array of AP locations and one station count per instance, at least one instance")
+        self.Ks, self.As = [int(k) for k in Ks], [int(a.shape[0]) for a in aps]
+        self._h = C.c_void_p()
+        check(lib().mmw_batch_env_create(C.byref(self._h), int(device), B, _pi(_i32(self.Ks)), _pi(_i32(self.As)), self._ptrs(aps), float(fre_Hz),
+                                         float(txp_offset), float(min_s_n_ratio), float(min_sinr), float(noise_floor_dbm)))
+
+    def _ptrs(self, arrays):
+        return (C.POINTER(C.c_double) * self.B)(*[_pd(a) for a in arrays])
+
+    def move(self, sta_locs):
+        """generate_S_Q_hmax of every instance at the positions sta_locs[i] (K_i, 2): two launches for all instances."""
+        sta = [_f64(x) for x in sta_locs]
+        if len(sta) != self.B or any(x.shape != (k, 2) for x, k in zip(sta, self.Ks)):
+            raise MMWError("move: one (K, 2) array of station locations per instance")
+        check(lib().mmw_batch_env_move(self._h, self._ptrs(sta)))
+
+    def sizes(self, inst):
+        sz = (C.c_int64 * 4)()
+        check(lib().mmw_batch_env_sizes(self._h, int(inst), sz))
+        return {"K": int(sz[0]), "A": int(sz[1]), "nnzS": int(sz[2]), "nnzQ": int(sz[3])}
+
+    def state(self, inst):
+        """(S_gain csr, Q_asso csr, h_max) of instance `inst` at its last positions, as env.generate_S_Q_hmax returns them."""
+        import scipy.sparse
+        sz = self.sizes(inst)
+        K, ns, nq = sz["K"], sz["nnzS"], sz["nnzQ"]
+        sp = np.empty(K + 1, dtype=np.int32); si = np.empty(ns, dtype=np.int32); sx = np.empty(ns, dtype=np.float64)
+        qp = np.empty(K + 1, dtype=np.int32); qi = np.empty(nq, dtype=np.int32); qx = np.empty(nq, dtype=np.float64)
+        h = np.empty(K, dtype=np.float64)
+        check(lib().mmw_batch_env_state(self._h, int(inst), _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(h)))
+        return scipy.sparse.csr_matrix((sx, si, sp), shape=(K, K)), scipy.sparse.csr_matrix((qx, qi, qp), shape=(K, K)), h
+
+    def evaluate(self, zs, Zs, packet_bit=800, bandwidth=5e6, slot_time=1.25e-4, bler=True):
+        """env.evaluate_sinr / evaluate_bler of one colouring per instance in one launch: zs[i] (K_i,) slot numbers, Zs[i] slots.
+        Returns (sinr, bler): one array per instance each (bler None when not asked for)."""
+        z = [_f64(x) for x in zs]
+        if len(z) != self.B or len(Zs) != self.B or any(x.shape != (k,) for x, k in zip(z, self.Ks)):
+            raise MMWError("evaluate: one colouring with one slot per user, and one slot count, per instance")
+        sinr = [np.empty(k, dtype=np.float64) for k in self.Ks]
+        bl = [np.empty(k, dtype=np.float64) for k in self.Ks] if bler else None
+        check(lib().mmw_batch_env_evaluate(self._h, self._ptrs(z), _pi(_i32(Zs)), float(packet_bit), float(bandwidth), float(slot_time),
+                                           self._ptrs(sinr), self._ptrs(bl) if bler else None))
+        return sinr, bl
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().mmw_batch_env_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

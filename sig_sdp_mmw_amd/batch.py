@@ -5,6 +5,7 @@ sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_searc
     results  = search_many(states, nit=150, eta=0.04, seed=0)                          # [{"Z", "z_vec", "remainder", "probes"}, ...]
 
     curves   = convergence_many(Zs, states, nit=625, eta=0.04)                         # [{"gap": [nit, 3], "lanczos_steps": [nit]}, ...]
+    online   = online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1)       # [{"Z", "probes", "z_vec", "remainder", "bler"}, ...]
 
 The iterations of every instance run in one launch per call.  The epilogue of a probe (X_half and the rounding) is chosen by
 `epilogue=`: "handle" (the default) exports the instance's iterate into an fp64 handle of the same state (mmw_batch_export) and runs
@@ -26,6 +27,7 @@ import numpy as np
 
 from . import _lib
 from .binary_search import binary_search_relaxation
+from .graphs import _NOISE_FLOOR_DBM, min_sinr_dec
 
 
 def probe_seed(seed, index, probe):
@@ -195,6 +197,53 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
         return out
     finally:
         hs.close()
+        b.close()
+
+
+def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
+                rank_radio=2, device=0, timings=None):
+    """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
+    many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
+    the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
+    index after the search's last -- and then, per time point, for all instances together: the state of the stations where they
+    are now (`BatchEnv.move`), `rounding(Z, gX, that state)` on the resident factors (`round_env`, draws keyed by
+    probe_seed(seed, i, 0x80000 | point), users left over drawn as in the search) and `evaluate_bler` of the colouring; then every
+    drop walks `step_us` microseconds (one value, or one per instance: the reference passes its own measured search time; 0 is its
+    "ideal" variant -- nobody moves, fresh draws per point).  The drops are moved in place.
+    Returns per instance {"Z", "probes", "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]}.  timings: a list
+    that receives one {"device_s" (move + round + evaluate), "step_s" (the host's walk)} per point."""
+    B = len(drops)
+    for i, d in enumerate(drops):
+        if d.K > _lib.BATCH_EPILOGUE_MAX_K:
+            raise ValueError("online_many: instance %d has K = %d users, over the batch epilogue's limit %d" % (i, d.K, _lib.BATCH_EPILOGUE_MAX_K))
+    steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
+    states = [d.state() for d in drops]
+    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch")
+    Zs = [int(r["Z"]) for r in found]
+    out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
+            "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
+    b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
+    env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
+    try:
+        b.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
+        b.factor()
+        for p in range(n_points):
+            t0 = time.perf_counter()
+            env.move([d.sta_locs for d in drops])
+            seeds = np.array([probe_seed(seed, i, 0x80000 | p) for i in range(B)], dtype=np.uint64)
+            z, rem, used = b.round_env(env, nattempt, seeds)
+            fin = [_finish(z, rem, used, i, Zs[i], int(seeds[i])) for i in range(B)]
+            _, bler = env.evaluate([f[0] for f in fin], Zs)
+            for i in range(B):
+                out[i]["z_vec"][p], out[i]["remainder"][p], out[i]["bler"][p] = fin[i][0], fin[i][2], bler[i]
+            t1 = time.perf_counter()
+            for d, t in zip(drops, steps):
+                d.step_time(t, mob_spd_meter_s, resolution_us)
+            if timings is not None:
+                timings.append({"device_s": t1 - t0, "step_s": time.perf_counter() - t1})
+        return out
+    finally:
+        env.close()
         b.close()
 
 

@@ -401,16 +401,31 @@ struct mmw_batch {
         rlists = std::move(rl);
         return MMW_OK;
     }
-    int round(const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+    // The rounding lists of another state of the same users (mmw_batch_round_env, batch_env_handle.h): where they lie, and per
+    // instance their offsets.  Null: the lists of the state the batch was built from.
+    struct RoundSource {
+        const char* who;
+        const int* si;
+        const double* sf;
+        const RoundLists* lists;  // [B]
+        const int* K;             // [B] users of every instance of the other state
+    };
+    int round(const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out,
+              const RoundSource* src = nullptr) {
+        const std::string who = src ? src->who : "mmw_batch_round";
         if (host_only) return host_only_batch();
-        if (nattempt < 1 || nattempt > 4096) return fail(MMW_ERR_ARG, "mmw_batch_round: nattempt must be in [1, 4096]");
+        if (nattempt < 1 || nattempt > 4096) return fail(MMW_ERR_ARG, who + ": nattempt must be in [1, 4096]");
         std::vector<int> tk;
-        MMW_TRY(takers("mmw_batch_round", take, tk));
-        for (int b : tk)
+        MMW_TRY(takers(who.c_str(), take, tk));
+        for (int b : tk) {
             if (fdesc.empty() || fdesc[b].rank == 0 || fdesc[b].K != desc[b].K)
-                return fail(MMW_ERR_STATE, "mmw_batch_round: instance " + std::to_string(b) + " has no factor (mmw_batch_factor)");
+                return fail(MMW_ERR_STATE, who + ": instance " + std::to_string(b) + " has no factor (mmw_batch_factor)");
+            if (src && src->K[b] != desc[b].K)
+                return fail(MMW_ERR_ARG, who + ": instance " + std::to_string(b) + ": K = " + std::to_string(desc[b].K) + " in the batch, " +
+                                             std::to_string(src->K[b]) + " in the environment");
+        }
         MMW_HIP(hipSetDevice(device));
-        MMW_TRY(round_lists());
+        if (!src) MMW_TRY(round_lists());
         auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };
         std::vector<RoundDesc> rd;
         int64_t of = 0, oi = 0;
@@ -420,7 +435,7 @@ struct mmw_batch {
         int64_t oz = 0;
         for (int b : tk) {
             const FactorDesc& f = fdesc[b];
-            const RoundLists& l = rlists[b];
+            const RoundLists& l = src ? src->lists[b] : rlists[b];
             const int64_t K = f.K, Z = desc[b].Z;
             RoundDesc r{};
             r.K = f.K; r.Z = desc[b].Z; r.Dp = f.rank; r.nattempt = nattempt; r.stop_first = stop_at_first != 0;
@@ -442,7 +457,8 @@ struct mmw_batch {
         MMW_TRY(ri.alloc((size_t)oi));
         MMW_TRY(d_rdesc.alloc(rd.size()));
         MMW_TRY(copy_h2d(d_rdesc.p, rd.data(), rd.size() * sizeof(RoundDesc), st));
-        hipLaunchKernelGGL(k_batch_round, dim3((unsigned)rd.size()), dim3(BATCH_THREADS), 0, st, d_rdesc.p, ew.p, rs_i.p, rs_f.p, rw.p, ri.p);
+        hipLaunchKernelGGL(k_batch_round, dim3((unsigned)rd.size()), dim3(BATCH_THREADS), 0, st, d_rdesc.p, ew.p, src ? src->si : rs_i.p,
+                           src ? src->sf : rs_f.p, rw.p, ri.p);
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(st));
         std::vector<int> host((size_t)nback);

@@ -38,6 +38,13 @@ __device__ __forceinline__ double env_dist(double x0, double y0, double x1, doub
 }
 __device__ __forceinline__ double env_loss(const EnvParams& P, double dis) { return __dadd_rn(P.L0, __dmul_rn(28.0, log10(__dadd_rn(dis, 1.0)))); }
 
+// the block error rate of the finite-blocklength model at SINR s (env.py:107-111)
+__device__ __forceinline__ double env_bler(double s, double Lbits, double Bw, double Tslot) {
+    const double nu = -Lbits * 0.6931471805599453 + Bw * Tslot * log(1.0 + s);
+    const double dn = sqrt(Bw * Tslot * (1.0 - 1.0 / ((1.0 + s) * (1.0 + s))));
+    return 0.5 * erfc((nu / dn) * 0.7071067811865476);  // scipy.stats.norm.sf
+}
+
 // one wavefront per user: rx[k][a] (unthresholded), association = argmax of the thresholded row (first maximum), row count
 __global__ __launch_bounds__(BLOCK) void k_env_rx(int K, int A, EnvParams P, const double* __restrict__ sta, const double* __restrict__ ap,
                                                   double* __restrict__ rx, int* __restrict__ asso) {
@@ -204,11 +211,7 @@ __global__ __launch_bounds__(BLOCK) void k_env_collide_bler(int K, int Z, const 
             if (lose) s = 1e-3;
         }
         sinr_out[i] = s;
-        if (bler) {
-            const double nu = -Lbits * 0.6931471805599453 + Bw * Tslot * log(1.0 + s);
-            const double dn = sqrt(Bw * Tslot * (1.0 - 1.0 / ((1.0 + s) * (1.0 + s))));
-            bler[i] = 0.5 * erfc((nu / dn) * 0.7071067811865476);  // scipy.stats.norm.sf
-        }
+        if (bler) bler[i] = env_bler(s, Lbits, Bw, Tslot);
     }
 }
 

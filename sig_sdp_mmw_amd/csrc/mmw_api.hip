@@ -1,5 +1,6 @@
 // C-ABI of the MI355X MMW hot path (include/mmw_hip.h), the library's one translation unit.  The handles: solver.h (mmw_solver, mmw_env),
-// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
+// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch), batch_env_handle.h (mmw_batch_env).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
+#include "batch_env_handle.h"
 #include "batch_handle.h"
 #include "gm_handle.h"
 
@@ -257,5 +258,53 @@ int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int sto
 }
 int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n) {
     return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->round_randv(inst, seed, attempt, out, n); });
+}
+// ---- the batched generator and scorer (batch_env_handle.h): the online sweeps' state per time point
+int mmw_batch_env_create(mmw_batch_env** out, int device, int32_t B, const int32_t* K, const int32_t* A, const double* const* ap_xy, double fre_Hz,
+                         double txp_offset, double min_s_n_ratio, double min_sinr, double noise_floor_dbm) {
+    return guarded("mmw_batch_env", [&]() -> int {
+        if (!out || !K || !A || !ap_xy) return fail(MMW_ERR_ARG, "mmw_batch_env_create: null pointer");
+        *out = nullptr;
+        if (B < 1 || B > 65535) return fail(MMW_ERR_ARG, "mmw_batch_env_create: B must be in [1, 65535]");
+        if (!(min_sinr > 0.0) || !(txp_offset > 0.0) || !(fre_Hz > 0.0)) return fail(MMW_ERR_ARG, "mmw_batch_env_create: min_sinr, txp_offset and fre_Hz must be positive");
+        for (int b = 0; b < B; ++b) {
+            const std::string who = "mmw_batch_env_create: instance " + std::to_string(b);
+            if (!ap_xy[b]) return fail(MMW_ERR_ARG, who + ": null pointer");
+            if (K[b] < 1 || A[b] < 1) return fail(MMW_ERR_ARG, who + ": K and A must be positive");
+            if (K[b] > EPI_MAX_K) return fail(MMW_ERR_ARG, who + ": K = " + std::to_string(K[b]) + " exceeds the limit " + std::to_string(EPI_MAX_K) + " (run it on mmw_env_create)");
+            if (A[b] > BENV_MAX_A) return fail(MMW_ERR_ARG, who + ": A = " + std::to_string(A[b]) + " exceeds the limit " + std::to_string(BENV_MAX_A) + " (run it on mmw_env_create)");
+        }
+        if (device == -1) return fail(MMW_ERR_ARG, "mmw_batch_env_create: device -1 (host only) is not served: the generator and the scorer run on the device");
+        MMW_TRY(check_device("mmw_batch_env_create", device, DEV_ID));
+        auto h = std::make_unique<mmw_batch_env>();
+        MMW_TRY(h->init(device, B, K, A, ap_xy, fre_Hz, txp_offset, min_s_n_ratio, min_sinr, noise_floor_dbm));
+        *out = h.release();
+        return MMW_OK;
+    });
+}
+int mmw_batch_env_destroy(mmw_batch_env* e) { return guarded("mmw_batch_env", [&]() -> int { delete e; return MMW_OK; }); }
+int mmw_batch_env_move(mmw_batch_env* e, const double* const* sta_xy) {
+    return guarded("mmw_batch_env", [&]() -> int {
+        if (!e || !sta_xy) return fail(MMW_ERR_ARG, "mmw_batch_env_move: null pointer");
+        for (int b = 0; b < e->B; ++b)
+            if (!sta_xy[b]) return fail(MMW_ERR_ARG, "mmw_batch_env_move: instance " + std::to_string(b) + ": null pointer");
+        return e->move(sta_xy);
+    });
+}
+int mmw_batch_env_sizes(mmw_batch_env* e, int32_t inst, int64_t out[4]) { return entry("mmw_batch_env", !e || !out, "null pointer", [&] { return e->sizes(inst, out); }); }
+int mmw_batch_env_state(mmw_batch_env* e, int32_t inst, int32_t* S_indptr, int32_t* S_indices, double* S_data, int32_t* Q_indptr, int32_t* Q_indices,
+                        double* Q_data, double* h_max) {
+    return entry("mmw_batch_env", !e || !S_indptr || !S_indices || !S_data || !Q_indptr || !Q_indices || !Q_data || !h_max, "mmw_batch_env_state: null pointer",
+                 [&] { return e->state(inst, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max); });
+}
+int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const int32_t* Z, double packet_bit, double bandwidth, double slot_time,
+                           double* const* sinr_out, double* const* bler_out) {
+    return entry("mmw_batch_env", !e || !z_vec || !Z || !sinr_out, "mmw_batch_env_evaluate: null pointer",
+                 [&] { return e->evaluate(z_vec, Z, packet_bit, bandwidth, slot_time, sinr_out, bler_out); });
+}
+int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
+                        int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+    return entry("mmw_batch", !b || !e || !seeds || !z_out || !rem_out || !used_out, "null pointer",
+                 [&] { return batch_round_env(b, e, take, nattempt, stop_at_first, seeds, z_out, rem_out, used_out); });
 }
 }  // extern "C"

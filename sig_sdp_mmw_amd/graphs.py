@@ -23,7 +23,7 @@ import scipy.sparse
 import scipy.spatial.distance
 import scipy.stats
 
-__all__ = ["journal_graph", "journal_graph_device", "journal_geometry", "er_contention_graph", "min_sinr_dec", "instance_stats"]
+__all__ = ["journal_graph", "journal_graph_device", "journal_geometry", "mobile_drop", "er_contention_graph", "min_sinr_dec", "instance_stats"]
 
 _NOISE_FLOOR_DBM = -94.0  # env.py:9
 
@@ -65,15 +65,16 @@ def journal_graph(cell_size=20, sta_density_per_1m2=5e-3, seed=1, cell_edge=20.0
     transmit power is set so its strongest AP receives ``txp_offset * min_sinr`` over the noise floor;
     receive powers below ``min_s_n_ratio`` are dropped.
     """
-    grid_edge = cell_edge * cell_size
-    n_ap = int(cell_size ** 2)
-    n_sta = int(cell_size ** 2 * (sta_density_per_1m2 * cell_edge ** 2))
-    off = cell_edge / 2.0
-    ax = np.linspace(0 + off, grid_edge - off, cell_size)
-    xx, yy = np.meshgrid(ax, ax)
-    ap_locs = np.array((xx.ravel(), yy.ravel())).T
-    sta_locs = np.random.default_rng(seed).uniform(low=0.0, high=grid_edge, size=(n_sta, 2))
+    sta_locs, ap_locs = journal_geometry(cell_size, sta_density_per_1m2, seed, cell_edge)
+    state, asso = _state_at(sta_locs, ap_locs, fre_Hz, txp_offset, min_s_n_ratio)
+    if return_geometry:
+        return state, {"sta_locs": sta_locs, "ap_locs": ap_locs, "asso": asso}
+    return state
 
+
+def _state_at(sta_locs, ap_locs, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1):
+    """generate_S_Q_hmax (env.py:136-196) for stations at `sta_locs`: ((S_gain, Q_asso, h_max), asso)."""
+    n_sta, n_ap = sta_locs.shape[0], ap_locs.shape[0]
     dis = scipy.spatial.distance.cdist(sta_locs, ap_locs)
     L0 = 20.0 * math.log10(fre_Hz / 1e6) + 16 - 28
     loss = L0 + 28 * np.log10(dis + 1)
@@ -98,9 +99,7 @@ def journal_graph(cell_size=20, sta_density_per_1m2=5e-3, seed=1, cell_edge=20.0
     S.eliminate_zeros()
     S.sort_indices()
     h_max = S.diagonal() / msinr - 1.0
-    if return_geometry:
-        return (S, Q, h_max), {"sta_locs": sta_locs, "ap_locs": ap_locs, "asso": asso}
-    return S, Q, h_max
+    return (S, Q, h_max), asso
 
 
 def journal_geometry(cell_size=20, sta_density_per_1m2=5e-3, seed=1, cell_edge=20.0):
@@ -113,6 +112,45 @@ def journal_geometry(cell_size=20, sta_density_per_1m2=5e-3, seed=1, cell_edge=2
     ap_locs = np.array((xx.ravel(), yy.ravel())).T
     sta_locs = np.random.default_rng(seed).uniform(low=0.0, high=grid_edge, size=(n_sta, 2))
     return sta_locs, ap_locs
+
+
+class mobile_drop:
+    """`mob_env(cell_size=..., sta_density_per_1m2=..., seed=...)` restated (sim_src/env/mob_env.py:20-21 on env.py:13-15, 58-67,
+    74-87): the station drop of `journal_graph`, one unit direction per station from a mobility stream `default_rng(seed)` of its
+    own (first draw: the (K, 2) block of env._config_sta_dirs), and `step_time`, which walks every station along its direction in
+    steps of `resolution_us`; a station whose next step would leave the grid stays and draws a new direction instead.  Positions
+    and directions are bitwise the reference's: the steps are vectorised over the stations (a station's move depends on nobody
+    else), the redraws are made one station at a time in ascending order inside a step, as the reference's loop makes them
+    (`standard_normal(2)` over `np.linalg.norm` of that pair -- an `(n, 2)` draw normalised along axis 1 differs in the last bit).
+    """
+
+    def __init__(self, cell_size, sta_density_per_1m2, seed, cell_edge=20.):
+        self.cell_size, self.sta_density_per_1m2, self.seed, self.cell_edge = cell_size, sta_density_per_1m2, seed, cell_edge
+        self.grid_edge = cell_edge * cell_size
+        self.sta_locs, self.ap_locs = journal_geometry(cell_size, sta_density_per_1m2, seed, cell_edge)
+        self.rand_gen_mob = np.random.default_rng(seed)
+        dd = self.rand_gen_mob.standard_normal(size=(self.sta_locs.shape[0], 2))
+        self.sta_dirs = dd / np.linalg.norm(dd, axis=1, keepdims=True)
+
+    @property
+    def K(self):
+        return int(self.sta_locs.shape[0])
+
+    def step_time(self, t_us, mob_spd_meter_s, resolution_us=1e5):
+        """mob_env.step_time -> env.rand_user_mobility (env.py:74-87)."""
+        if mob_spd_meter_s == 0. or t_us == 0.:
+            return
+        for _ in range(math.ceil(t_us / resolution_us)):
+            new = self.sta_locs + self.sta_dirs * mob_spd_meter_s * resolution_us / 1e6
+            ok = np.all((0 <= new) & (new <= self.grid_edge), axis=1)
+            self.sta_locs[ok] = new[ok]
+            for i in np.flatnonzero(~ok):
+                dd = self.rand_gen_mob.standard_normal(2)
+                self.sta_dirs[i] = dd / np.linalg.norm(dd)
+
+    def state(self, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1):
+        """`generate_S_Q_hmax()` at the current positions: the `journal_graph` state of them."""
+        return _state_at(self.sta_locs, self.ap_locs, fre_Hz, txp_offset, min_s_n_ratio)[0]
 
 
 def journal_graph_device(cell_size=20, sta_density_per_1m2=5e-3, seed=1, cell_edge=20.0, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1,
