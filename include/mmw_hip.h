@@ -388,6 +388,47 @@ int mmw_batch_factor(mmw_batch* b, const int32_t* take, const int32_t* rank, con
 int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out,
                     int32_t* rem_out, int32_t* used_out);
 int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n);
+/*
+ * The baselines the reference's sweep scripts run beside the MMW search on every instance (sim_script/journal_version/
+ * sim_all_bler.py:30-72: rand_sdp_solver, MAX_GAIN.run and MAX_ASSO.run at Z_fin; ton_major_rv/sim_mmw_online_cmp_methods.py:79-88:
+ * MAX_GAIN.run(-1, not_Z_bound=True) once per drop), inside the batch: one launch per call, one workgroup per taking instance
+ * (csrc/kernels_batch_gm.h), instead of one mmw_gm_create, one host-made key and one single-wave mmw_gm_run per instance.  Opt-in:
+ * the arenas, the resident MMW fields and (for mmw_batch_gm) the resident factors stay bitwise as they were; an instance's result is
+ * bitwise independent of its batch neighbours and of `take`.
+ *
+ * mmw_batch_gm: gm.MAX_GAIN.run (kind 0, sim_src/alg/gm.py:9-66) or gm.MAX_ASSO.run (kind 1, gm.py:69-127) of every taking instance on
+ * the state the batch was built from, in the stable visiting order (argsort(-key, kind="stable"): ties to the lower user index, the
+ * rule of mmw_gm_run).  The key is formed on the device and is bitwise the reference's expression: kind 0, the column sums of S_gain
+ * with the diagonal zeroed accumulated in ascending row (gm.py:11-18: scipy's CSC matvec behind S.transpose().sum(axis=1)); kind 1,
+ * the row sums of Q_asso in stored order (gm.py:81).  The slot loop is gm.py:24-58 / 85-115 as mmw_gm_run runs it: the sums zeroed
+ * once per slot, `nattempt` attempts on them, the first longest list wins, a slot that accepts nobody ends the loop with ZZ = Z, and
+ * the loop ends early when everybody is assigned.  take[B]: as in mmw_batch_round.  Z[B]: the slot bound per instance; Z[b] <= 0 is
+ * not_Z_bound (gm.py:22-23): the bound is K and the caller's fill range is ZZ (gm.py:60-64).  z_out: K entries per TAKING instance,
+ * instance after instance, the slot or -1 for a user left over (the caller draws those, gm.py:60-64); zz_out[B] / rem_out[B]: ZZ and
+ * the users left over, -1 for an instance that did not take part; key_out: NULL, or the key of every taking instance laid out as
+ * z_out.  One copy of the descriptors in, one launch, one copy of the results back.
+ * Refused by name with MMW_ERR_ARG before anything runs (the outputs stay untouched): a taking instance with
+ * K > MMW_BATCH_EPILOGUE_MAX_K, or whose Q_asso is not a union of cliques with weights >= 1 -- every state env.generate_S_Q_hmax
+ * makes is one (env.py:182-189), mmw_batch_create decides it; such an instance stays on a GreedyHandle (mmw_gm_create) --, kind
+ * outside {0, 1}, nattempt < 1, and a call in which no instance takes part.  A host-only batch (device -1) answers with the same
+ * procedure as plain host C++, key and order included.
+ *
+ * mmw_batch_env_gm (declared with the environment below): the same on the state the environment holds after its last move
+ * (MAX_GAIN.run on e.generate_S_Q_hmax(), sim_mmw_online_cmp_methods.py:79-81); the association is the group id.  take: non-zero =
+ * the instance takes part, NULL = every instance.  MMW_ERR_STATE before the first move.
+ *
+ * mmw_batch_factor_random: rand_sdp_solver.run_with_state (sim_src/alg/sdp_solver.py:109-114), a K x (Z * rank_radio) block of
+ * normals with its rows normalised, as the RESIDENT FACTOR of every taking instance, rank = D = Z * rank_radio (D may exceed K).  The
+ * block of instance b with seeds[b] is bitwise mmw_batch_sketch(b, inst, seeds[b], 0).  No iteration needs to have run.  As with
+ * mmw_batch_factor the work buffers are laid out anew (earlier factors are gone) and a host-only batch answers MMW_ERR_STATE;
+ * mmw_batch_round, mmw_batch_round_env, mmw_batch_round_randv and MMW_F_FACTOR / MMW_F_FACTOR_INFO ({0, 0, D, 0, 0}) then work on it,
+ * with one rule of its own: every row has norm 1, so the rounding's visiting order (descending norm, sdp_solver.py:51) is one tie
+ * over all users, and the rounding visits such a block in index order (ties to the lower index) without forming the norms, whose
+ * last bits would decide the order otherwise.  A factor of mmw_batch_factor is rounded exactly as before.
+ */
+int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
+                 int32_t* rem_out, double* key_out);
+int mmw_batch_factor_random(mmw_batch* b, const int32_t* take, const uint64_t* seeds);
 
 /*
  * The generator and the scorer for many small instances (csrc/kernels_batch_env.h), one workgroup per instance: the state of
@@ -428,6 +469,9 @@ int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const i
                            double slot_time, double* const* sinr_out, double* const* bler_out);
 int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first,
                         const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out);
+/* mmw_batch_gm on the state of the environment's last move: see there */
+int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out,
+                     int32_t* zz_out, int32_t* rem_out, double* key_out);
 
 #ifdef __cplusplus
 }

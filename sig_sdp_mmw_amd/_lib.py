@@ -31,7 +31,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
-           "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env"]
+           "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
+           "mmw_batch_factor_random"]
 
 
 class MMWError(RuntimeError):
@@ -121,6 +122,9 @@ def lib():
     L.mmw_batch_env_state.argtypes = [C.c_void_p, C.c_int32, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64]
     L.mmw_batch_env_evaluate.argtypes = [C.c_void_p, pp_f64, p_i32, C.c_double, C.c_double, C.c_double, pp_f64, pp_f64]
     L.mmw_batch_round_env.argtypes = [C.c_void_p, C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
+    L.mmw_batch_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
+    L.mmw_batch_env_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
+    L.mmw_batch_factor_random.argtypes = [C.c_void_p, p_i32, C.POINTER(C.c_uint64)]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -147,6 +151,24 @@ def _i32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _gm_call(fn, handle, B, Ks, who, kind, Zs, nattempt, t, keys):
+    """mmw_batch_gm / mmw_batch_env_gm: (z list with None for instances left out, ZZ int32[B], rem int32[B][, keys list])."""
+    Z = _i32(np.broadcast_to(np.asarray(Zs, dtype=np.int32), (B,)))
+    n = max(1, sum(Ks[i] for i in who))
+    zflat = np.empty(n, dtype=np.int32)
+    kflat = np.empty(n, dtype=np.float64) if keys else None
+    zz = np.empty(B, dtype=np.int32)
+    rem = np.empty(B, dtype=np.int32)
+    check(fn(handle, int(kind), None if t is None else _pi(t), _pi(Z), int(nattempt), _pi(zflat), _pi(zz), _pi(rem), _pd(kflat) if keys else None))
+    z, ks, o = [None] * B, [None] * B, 0
+    for i in who:
+        z[i] = zflat[o:o + Ks[i]]
+        if keys:
+            ks[i] = kflat[o:o + Ks[i]]
+        o += Ks[i]
+    return (z, zz, rem, ks) if keys else (z, zz, rem)
 
 
 def device_count():
@@ -602,6 +624,21 @@ class BatchSolver:
             o += nattempt * K
         return z, rem, used
 
+    def factor_random(self, seeds, take=None):
+        """rand_sdp_solver.run_with_state (sdp_solver.py:109-114) of every taking instance: its resident factor becomes the
+        row-normalised K x D block of normals `sketch(i, seeds[i], 0)`, rank D; `round` / `round_env` / `read_factor` then work on it.
+        All its rows have norm 1, so the rounding visits the users of such a block in index order (include/mmw_hip.h)."""
+        t, _ = self._take(take)
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
+        check(lib().mmw_batch_factor_random(self._h, None if t is None else _pi(t), sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def gm(self, kind, Zs, nattempt=1, take=None, keys=False):
+        """gm.MAX_GAIN.run (kind 0) / gm.MAX_ASSO.run (kind 1) in the stable order for every taking instance's own state, one launch
+        (mmw_batch_gm).  Zs: the slot bound, one for all or one per instance, <= 0 = not_Z_bound.  Returns (z, ZZ, rem[, keys]): z[i]
+        None or int32 (K,) with -1 = left over, ZZ / rem int32 (B,) with -1 for instances left out, keys[i] the visiting key."""
+        t, who = self._take(take)
+        return _gm_call(lib().mmw_batch_gm, self._h, self.B, [s["K"] for s in self.sizes], who, kind, Zs, nattempt, t, keys)
+
     def round_env(self, env, nattempt, seeds, take=None, stop_at_first=True):
         """`round` against the state a `BatchEnv` holds (the stations as they have moved) instead of the one the batch was built
         from: same factors, same draws, same greedy pass (mmw_batch_round_env).  Nothing of the batch changes."""
@@ -767,6 +804,14 @@ class BatchEnv:
         check(lib().mmw_batch_env_evaluate(self._h, self._ptrs(z), _pi(_i32(Zs)), float(packet_bit), float(bandwidth), float(slot_time),
                                            self._ptrs(sinr), self._ptrs(bl) if bler else None))
         return sinr, bl
+
+    def gm(self, kind, Zs, nattempt=1, take=None, keys=False):
+        """`BatchSolver.gm` on the states of the last `move` (mmw_batch_env_gm); take: one flag per instance, None = all."""
+        t = None if take is None else _i32([1 if x else 0 for x in take])
+        if t is not None and t.size != self.B:
+            raise MMWError("take: one flag per instance")
+        who = [i for i in range(self.B) if t is None or t[i]]
+        return _gm_call(lib().mmw_batch_env_gm, self._h, self.B, self.Ks, who, kind, Zs, nattempt, t, keys)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -6,6 +6,9 @@ sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_searc
 
     curves   = convergence_many(Zs, states, nit=625, eta=0.04)                         # [{"gap": [nit, 3], "lanczos_steps": [nit]}, ...]
     online   = online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1)       # [{"Z", "probes", "z_vec", "remainder", "bler"}, ...]
+    base     = baselines_many(batch_solver, Zs)                                        # [{"rand" / "mgain" / "masso": (z_vec, Z, remainder)}, ...]
+    cmp      = compare_many(drops, nit=150, eta=0.04)                                  # [{"Z", "probes", "bler": {"mmw", "rand", "mgain", "masso"}}, ...]
+    greedy   = online_greedy_many(drops, n_points=11, step_us=1e6)                     # [{"Z", "z_vec", "remainder", "bler"}, ...]
 
 The iterations of every instance run in one launch per call.  The epilogue of a probe (X_half and the rounding) is chosen by
 `epilogue=`: "handle" (the default) exports the instance's iterate into an fp64 handle of the same state (mmw_batch_export) and runs
@@ -245,6 +248,122 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     finally:
         env.close()
         b.close()
+
+
+METHODS = ("rand", "mgain", "masso")  # the baselines of sim_all_bler.py:42-72 that run inside the batch, in its order
+
+
+def _fill(slot, rem, high, seed):
+    """gm.py:60-64: the users a greedy baseline left over (-1) drawn from [0, high), from a generator keyed by `seed`."""
+    z_vec = slot.astype(np.float64)
+    un = slot < 0
+    if np.any(un):
+        z_vec[un] = np.random.default_rng(seed).integers(0, high, int(un.sum()))
+    return z_vec, int(rem)
+
+
+def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, nattempt_gm=1):
+    """The baselines the reference runs at each instance's Z (sim_all_bler.py:42-72) for all instances at once: "rand"
+    (rand_sdp_solver: `factor_random` then `round`, both keyed by probe_seed(seed, i, 0x40000 | m) with m the method's index in
+    METHODS), "mgain" and "masso" (gm.MAX_GAIN / MAX_ASSO in the stable order: `gm`, one launch each).  source: a `BatchSolver` (the
+    states it was built from) or a `(BatchSolver, BatchEnv)` pair (the states the environment holds: `round_env`, `BatchEnv.gm`).
+    Zs: one slot count per instance; the solver's slot counts must be these for "rand" (its embedding is K x Z rank_radio).  Users
+    left over are drawn from a generator keyed by the same seed.  The resident factors are replaced by "rand".
+    Returns per instance {method: (z_vec float64[K], Z, remainder)}."""
+    b, env = source if isinstance(source, tuple) else (source, None)
+    B = b.B
+    Zs = [int(z) for z in Zs]
+    if len(Zs) != B:
+        raise ValueError("baselines_many: one slot count per instance")
+    out = [{} for _ in range(B)]
+    for name in methods:
+        if name not in METHODS:
+            raise ValueError("baselines_many: method must be one of %s, got %r" % (METHODS, name))
+        m = METHODS.index(name)
+        seeds = np.array([probe_seed(seed, i, 0x40000 | m) for i in range(B)], dtype=np.uint64)
+        if name == "rand":
+            if any(b.sizes[i]["Z"] != Zs[i] for i in range(B)):
+                raise ValueError("baselines_many: the batch's slot counts are not Zs (set_slots first)")
+            b.factor_random(seeds)
+            z, rem, used = b.round(nattempt_round, seeds) if env is None else b.round_env(env, nattempt_round, seeds)
+            for i in range(B):
+                out[i][name] = _finish(z, rem, used, i, Zs[i], int(seeds[i]))
+        else:
+            slot, _, rem = (b if env is None else env).gm(m - 1, Zs, nattempt_gm)
+            for i in range(B):
+                out[i][name] = (_fill(slot[i], rem[i], Zs[i], int(seeds[i]))[0], Zs[i], int(rem[i]))
+    return out
+
+
+def _geometry(d):
+    return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
+
+
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None):
+    """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
+    (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
+    (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
+    "mgain", "masso"}}.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"}."""
+    geo = [_geometry(d) for d in drops_or_geometries]
+    B = len(geo)
+    env = _lib.BatchEnv([g[1] for g in geo], [g[0].shape[0] for g in geo], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
+    b = None
+    try:
+        env.move([g[0] for g in geo])
+        states = [env.state(i) for i in range(B)]
+        t0 = time.perf_counter()
+        found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch")
+        t1 = time.perf_counter()
+        Zs = [int(r["Z"]) for r in found]
+        b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
+        base = baselines_many((b, env), Zs, seed=seed, nattempt_round=nattempt)
+        t2 = time.perf_counter()
+        out = [{"Z": Zs[i], "probes": found[i]["probes"], "bler": {}} for i in range(B)]
+        for name, zs in [("mmw", [r["z_vec"] for r in found])] + [(m, [base[i][m][0] for i in range(B)]) for m in METHODS]:
+            _, bler = env.evaluate(zs, Zs)
+            for i in range(B):
+                out[i]["bler"][name] = bler[i]
+        if timings is not None:
+            timings.update(search_s=t1 - t0, baselines_s=t2 - t1, evaluate_s=time.perf_counter() - t2)
+        return out
+    finally:
+        if b is not None:
+            b.close()
+        env.close()
+
+
+def online_greedy_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e4, seed=0, device=0, timings=None):
+    """The greedy arm of the reference's online comparison (sim_mmw_online_cmp_methods.py:79-88) for many `graphs.mobile_drop`s:
+    MAX_GAIN.run(-1, not_Z_bound=True) once on the drops' states (`BatchEnv.move`, `BatchEnv.gm(0, Z <= 0)`; users left over drawn
+    from [0, ZZ), keyed by probe_seed(seed, i, 0x40000 | 1)), then per time point the state where the stations are now (`move`),
+    `evaluate` of that ONE colouring with Z = ZZ, and every drop walks `step_us` microseconds (one value or one per instance) in
+    `resolution_us` steps.  The drops are moved in place.
+    Returns per instance {"Z", "probes": [], "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]} (the colouring
+    repeated per point: `online_many`'s shape); timings as there."""
+    B = len(drops)
+    steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
+    env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
+    try:
+        env.move([d.sta_locs for d in drops])
+        slot, ZZ, rem = env.gm(0, 0)
+        Zs = [int(z) for z in ZZ]
+        zv = [_fill(slot[i], rem[i], Zs[i], probe_seed(seed, i, 0x40000 | 1))[0] for i in range(B)]
+        out = [{"Z": Zs[i], "probes": [], "z_vec": np.tile(zv[i], (n_points, 1)), "remainder": np.full(n_points, int(rem[i]), dtype=np.int64),
+                "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
+        for p in range(n_points):
+            t0 = time.perf_counter()
+            env.move([d.sta_locs for d in drops])
+            _, bler = env.evaluate(zv, Zs)
+            for i in range(B):
+                out[i]["bler"][p] = bler[i]
+            t1 = time.perf_counter()
+            for d, t in zip(drops, steps):
+                d.step_time(t, mob_spd_meter_s, resolution_us)
+            if timings is not None:
+                timings.append({"device_s": t1 - t0, "step_s": time.perf_counter() - t1})
+        return out
+    finally:
+        env.close()
 
 
 class single:

@@ -9,6 +9,8 @@
 #include "batch_handle.h"
 #include "kernels_batch_env.h"
 
+static_assert(BENV_MAX_A <= BGM_MAX_G, "the association is k_batch_gm's group id: one owner word per access point in LDS");
+
 struct mmw_batch_env {
     int device = 0, B = 0;
     hipStream_t st = nullptr;
@@ -23,6 +25,7 @@ struct mmw_batch_env {
     DevBuf<BatchEnvDesc> d_desc;
     DevBuf<double> fa, zbuf, obuf;
     DevBuf<int> ia, d_tot;
+    GmWork gmw;
     ~mmw_batch_env() {
         if (!st) return;
         (void)hipSetDevice(device);
@@ -167,6 +170,30 @@ struct mmw_batch_env {
             if (bler_out) std::copy(ho.begin() + Ktot + desc[b].o_k, ho.begin() + Ktot + desc[b].o_k + K[b], bler_out[b]);
         }
         return MMW_OK;
+    }
+    // MAX_GAIN / MAX_ASSO (kernels_batch_gm.h) on the state of the last move: the association is the group id, Q's values are the
+    // fill pass's ones
+    int gm(int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out, int32_t* rem_out, double* key_out) {
+        const std::string who = "mmw_batch_env_gm";
+        if (!moved) return fail(MMW_ERR_STATE, who + ": no positions yet (mmw_batch_env_move)");
+        MMW_TRY(batch_gm_args(who, kind, nattempt));
+        std::vector<int> tk;
+        for (int b = 0; b < B; ++b)
+            if (!take || take[b]) tk.push_back(b);
+        if (tk.empty()) return fail(MMW_ERR_ARG, who + ": no instance takes part");
+        std::vector<GmDesc> gd;
+        for (int b : tk) {
+            const BatchEnvDesc& d = desc[b];
+            const mmw_batch::RoundLists& l = rlists[b];
+            GmDesc g{};
+            g.K = d.K; g.G = d.A; g.kind = kind; g.Zb = Z[b] <= 0 ? d.K : Z[b]; g.nattempt = nattempt;
+            g.s_soptr = l.soptr; g.s_soidx = l.soidx; g.s_qptr = l.qptr;
+            g.s_sodata = l.sodata; g.s_sohmax = l.sohmax; g.s_hmax = l.hmax;
+            g.g_grp = d.i_asso; g.g_qdata = d.f_qval;
+            gd.push_back(g);
+        }
+        MMW_HIP(hipSetDevice(device));
+        return gmw.run(st, B, tk, gd, ia.p, fa.p, ia.p, fa.p, z_out, zz_out, rem_out, key_out);
     }
 };
 // mmw_batch_round_env: mmw_batch_round of the batch's resident factors against the state the environment holds

@@ -5,6 +5,7 @@
 
 #include "kernels_batch.h"
 #include "kernels_batch_epilogue.h"
+#include "kernels_batch_gm.h"
 #include "solver.h"
 
 struct mmw_batch {
@@ -34,8 +35,33 @@ struct mmw_batch {
     DevBuf<int> ei, ri, rs_i;
     DevBuf<FactorDesc> d_fdesc;
     DevBuf<RoundDesc> d_rdesc;
+    DevBuf<FactorRandomDesc> d_frdesc;
     struct RoundLists { int64_t soptr, soidx, qptr, qidx, sodata, sohmax, hmax; };
     std::vector<RoundLists> rlists;
+    // the greedy baselines (mmw_batch_gm, kernels_batch_gm.h): what the pattern does not keep of Q -- its values, and the clique
+    // structure decided at creation (GmState::find_cliques) -- goes up once, beside the rounding lists; the call's buffers
+    struct GmExtra {
+        std::vector<double> q_data;
+        std::vector<int32_t> grp;  // clique id per user, -1: no Q row
+        int G = 0;
+        bool clique = false;
+    };
+    std::vector<GmExtra> gmx;
+    std::vector<int64_t> gm_ogrp, gm_oq;
+    DevBuf<int> gm_i;
+    DevBuf<double> gm_f;
+    GmWork gmw;
+    void gm_extra(int b, const int32_t* Qp, const double* Qx) {
+        GmState g;
+        g.K = H[b].K;
+        g.q_indptr = H[b].q_indptr; g.q_indices = H[b].q_indices;
+        g.q_data.assign(Qx, Qx + Qp[g.K]);
+        GmExtra& x = gmx[b];
+        x.clique = g.find_cliques();
+        x.G = g.G;
+        x.grp = std::move(g.grp);
+        x.q_data = std::move(g.q_data);
+    }
     ~mmw_batch() {
         if (host_only || !st) return;
         (void)hipSetDevice(device);
@@ -439,6 +465,7 @@ struct mmw_batch {
             const int64_t K = f.K, Z = desc[b].Z;
             RoundDesc r{};
             r.K = f.K; r.Z = desc[b].Z; r.Dp = f.rank; r.nattempt = nattempt; r.stop_first = stop_at_first != 0;
+            r.index_order = f.unit_rows;
             r.seed = seeds[b];
             r.o_fac = f.o_fac;
             r.s_soptr = l.soptr; r.s_soidx = l.soidx; r.s_qptr = l.qptr; r.s_qidx = l.qidx;
@@ -490,6 +517,103 @@ struct mmw_batch {
         hipLaunchKernelGGL(k_batch_randv, dim3(1), dim3(BATCH_THREADS), 0, st, Z, Dp, seed, (uint32_t)attempt, rvbuf.p);
         MMW_HIP(hipGetLastError());
         return copy_d2h(out, rvbuf.p, (size_t)n * sizeof(double), st);
+    }
+    // ---- the sweeps' baselines
+    // rand_sdp_solver.run_with_state (sdp_solver.py:109-114): the instance's sketch of (seed, iteration 0) as its resident factor, rank D
+    int factor_random(const int32_t* take, const uint64_t* seeds) {
+        if (host_only) return host_only_batch();
+        std::vector<int> tk;
+        MMW_TRY(takers("mmw_batch_factor_random", take, tk));
+        for (int b : tk)
+            if (desc[b].K > EPI_MAX_K)
+                return fail(MMW_ERR_ARG, "mmw_batch_factor_random: instance " + std::to_string(b) + ": K = " + std::to_string(desc[b].K) +
+                                             " exceeds the epilogue limit " + std::to_string(EPI_MAX_K) + " (round it on a handle)");
+        auto a32 = [](int64_t x) { return (x + 31) & ~(int64_t)31; };
+        std::vector<FactorDesc> fd(B, FactorDesc{});
+        std::vector<FactorRandomDesc> launch;
+        int64_t of = a32((int64_t)tk.size() * EPI_INFO_STRIDE), ninfo = 0;
+        for (int b : tk) {
+            FactorDesc& f = fd[b];
+            f.K = desc[b].K; f.rank = desc[b].D; f.unit_rows = 1;
+            f.o_info = EPI_INFO_STRIDE * ninfo++;
+            f.o_fac = of; of = a32(of + (int64_t)f.K * f.rank);
+            launch.push_back(FactorRandomDesc{f.K, f.rank, seeds[b], f.o_fac, f.o_info});
+        }
+        fdesc.clear();  // the buffers are laid out anew: earlier factors are gone whatever happens below
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(ew.alloc((size_t)of));
+        MMW_TRY(d_frdesc.upload(launch, st));
+        hipLaunchKernelGGL(k_batch_factor_random, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, st, d_frdesc.p, ew.p);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        fdesc = std::move(fd);
+        return MMW_OK;
+    }
+    // the instance's state as the greedy procedures read it (host-only batch)
+    GmState gm_state(int b) const {
+        const HostPattern& P = H[b];
+        GmState g;
+        g.K = P.K; g.G = gmx[b].G; g.clique = gmx[b].clique;
+        g.so_indptr = P.so_indptr; g.so_indices = P.so_indices; g.so_data = P.so_data;
+        for (int32_t n : P.so_indices) g.so_hmax.push_back(P.h_max[n]);
+        g.q_indptr = P.q_indptr; g.q_indices = P.q_indices; g.q_data = gmx[b].q_data;
+        g.grp = gmx[b].grp; g.h_max = P.h_max;
+        return g;
+    }
+    int gm_lists() {
+        if (!gm_ogrp.empty()) return MMW_OK;
+        std::vector<int> hi;
+        std::vector<double> hf;
+        std::vector<int64_t> og(B), oq(B);
+        for (int b = 0; b < B; ++b) {
+            og[b] = (int64_t)hi.size(); hi.insert(hi.end(), gmx[b].grp.begin(), gmx[b].grp.end());
+            oq[b] = (int64_t)hf.size(); hf.insert(hf.end(), gmx[b].q_data.begin(), gmx[b].q_data.end());
+        }
+        MMW_TRY(gm_i.upload(hi, st));
+        MMW_TRY(gm_f.upload(hf, st));
+        gm_ogrp = std::move(og); gm_oq = std::move(oq);
+        return MMW_OK;
+    }
+    int gm(int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out, int32_t* rem_out, double* key_out) {
+        const std::string who = "mmw_batch_gm";
+        MMW_TRY(batch_gm_args(who, kind, nattempt));
+        std::vector<int> tk;
+        MMW_TRY(takers(who.c_str(), take, tk));
+        for (int b : tk) {
+            const std::string inst = who + ": instance " + std::to_string(b);
+            if (H[b].K > EPI_MAX_K) return fail(MMW_ERR_ARG, inst + ": K = " + std::to_string(H[b].K) + " exceeds the limit " + std::to_string(EPI_MAX_K) + " (it stays on a GreedyHandle)");
+            if (!gmx[b].clique) return fail(MMW_ERR_ARG, inst + ": Q_asso is not a union of cliques with weights >= 1 (it stays on a GreedyHandle)");
+        }
+        if (host_only) {
+            for (int b = 0; b < B; ++b) zz_out[b] = rem_out[b] = -1;
+            std::vector<double> key;
+            for (int b : tk) {
+                const GmState g = gm_state(b);
+                const int K = g.K, Zb = Z[b] <= 0 ? K : Z[b];
+                g.key_host(kind, key);
+                int entered = 0, stop = GM_STOP_SLOTS, total = 0;
+                g.run_host(key.data(), Zb, nattempt, z_out, entered, stop, total);
+                zz_out[b] = stop == GM_STOP_ALL_ASSIGNED ? entered : Zb;
+                rem_out[b] = K - total;
+                z_out += K;
+                if (key_out) { std::copy(key.begin(), key.end(), key_out); key_out += K; }
+            }
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(round_lists());
+        MMW_TRY(gm_lists());
+        std::vector<GmDesc> gd;
+        for (int b : tk) {
+            const RoundLists& l = rlists[b];
+            GmDesc g{};
+            g.K = H[b].K; g.G = gmx[b].G; g.kind = kind; g.Zb = Z[b] <= 0 ? g.K : Z[b]; g.nattempt = nattempt;
+            g.s_soptr = l.soptr; g.s_soidx = l.soidx; g.s_qptr = l.qptr;
+            g.s_sodata = l.sodata; g.s_sohmax = l.sohmax; g.s_hmax = l.hmax;
+            g.g_grp = gm_ogrp[b]; g.g_qdata = gm_oq[b];
+            gd.push_back(g);
+        }
+        return gmw.run(st, B, tk, gd, rs_i.p, rs_f.p, gm_i.p, gm_f.p, z_out, zz_out, rem_out, key_out);
     }
 };
 // mmw_batch_export: the instance's iterate into an fp64 handle of the same (state, Z), as if the handle had run those iterations.

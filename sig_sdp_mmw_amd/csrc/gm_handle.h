@@ -109,20 +109,7 @@ struct mmw_gm {
         const int K = S.K;
         int entered = 0, stop = GM_STOP_SLOTS, total = 0;
         if (device < 0) {
-            std::vector<int32_t> order(K), cur(K), best;
-            std::iota(order.begin(), order.end(), 0);
-            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key_h[a] > key_h[b]; });
-            std::fill(z_out, z_out + K, -1);
-            for (int32_t z = 0; z < Z; ++z) {
-                int32_t n = 0;
-                for (int32_t k : order) if (z_out[k] < 0) cur[n++] = k;
-                S.pass_host(cur.data(), n, nattempt, w_gs, w_as, w_mark, w_owner, w_stamp, best);
-                ++entered;
-                for (int32_t k : best) z_out[k] = z;
-                total += (int)best.size();
-                if (best.empty()) { stop = GM_STOP_EMPTY; break; }
-                if (total == K) { stop = GM_STOP_ALL_ASSIGNED; break; }
-            }
+            S.run_host(key_h, Z, nattempt, z_out, entered, stop, total);
         } else {
             MMW_HIP(hipSetDevice(device));
             MMW_TRY(key.alloc(K)); MMW_TRY(rank_part.alloc((size_t)RANK_SPLIT * K));

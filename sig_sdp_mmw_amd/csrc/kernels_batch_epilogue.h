@@ -38,7 +38,8 @@ static_assert(EPI_MAX_K % WAVE == 0 && EPI_MAX_K / WAVE <= 16, "the Jacobi keeps
 struct FactorDesc {
     int K, rank, nnzL, cap;
     double div;             // Xbar = values / div (the run's sum: nit; parity mode: 1)
-    int src_work, pad0;     // the values lie in the work buffer (parity mode) instead of the arena
+    int src_work;           // the values lie in the work buffer (parity mode) instead of the arena
+    int unit_rows;          // the rows are unit by construction (k_batch_factor_random): the rounding visits them in index order
     int64_t o_lrow, o_col;  // int32 arena
     int64_t o_src;          // [nnzL] values on the pattern
     int64_t o_A, o_fac, o_nrm, o_info;  // fp64 work: K x K, K x rank, K, EPI_INFO
@@ -201,9 +202,26 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor(const FactorDesc
     }
 }
 
+// ---- the random embedding (rand_sdp_solver.run_with_state, sdp_solver.py:109-114): K x D row-normalised normals as the resident factor.
+// The block is the batch's own sketch of (seed, iteration 0), bitwise (batch_sketch_rows, kernels_batch.h); its record says rank = D.
+// Every row has norm 1, so the rounding's visiting order (descending norm, sdp_solver.py:51) is one tie over all users: the reference
+// sorts the last-bit noise of its norms there, an arbitrary permutation of exchangeable rows.  The batch takes the tie rule literally
+// instead, the lower index first (RoundDesc::index_order), so the result depends on no summation order.
+struct FactorRandomDesc {
+    int K, D;
+    uint64_t seed;
+    int64_t o_fac, o_info;  // fp64 work: K x D, EPI_INFO
+};
+__global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor_random(const FactorRandomDesc* __restrict__ descs, double* ew) {
+    const FactorRandomDesc d = descs[blockIdx.x];
+    batch_sketch_rows(d.K, d.D, d.seed, 0u, ew + d.o_fac);
+    if ((int)threadIdx.x < EPI_INFO) ew[d.o_info + threadIdx.x] = threadIdx.x == 2 ? (double)d.D : 0.0;
+}
+
 // ---- the rounding ------------------------------------------------------------------------------------------------------------------
 struct RoundDesc {
-    int K, Z, Dp, nattempt, stop_first, pad0;
+    int K, Z, Dp, nattempt, stop_first;
+    int index_order;                                     // unit rows (FactorDesc::unit_rows): all norms tie, visit by index
     uint64_t seed;
     int64_t o_fac;                                       // fp64 factor work: gX = X_half [K, Dp]
     int64_t s_soptr, s_soidx, s_qptr, s_qidx;            // int32 lists of the state: S_gain without its diagonal, Q_asso
@@ -273,24 +291,28 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_round(const RoundDesc* 
     for (size_t i = tid; i < (size_t)d.nattempt * K; i += NT) zout[i] = -2;  // attempts not run
     for (int a = tid; a < d.nattempt; a += NT) rem[a] = -1;
     // ---- the visiting order, once: descending ||gX_k|| (sdp_solver.py:51), ties to the lower index
-    for (int row = wv; row < K; row += BATCH_WAVES) {
-        double s = 0.0;
-        for (int c = lane; c < Dp; c += WAVE) {
-            const double x = gX[(size_t)row * Dp + c];
-            s += x * x;
+    if (d.index_order) {  // (workgroup-uniform) unit rows: one tie over all users
+        for (int k = tid; k < K; k += NT) order[k] = k;
+    } else {
+        for (int row = wv; row < K; row += BATCH_WAVES) {
+            double s = 0.0;
+            for (int c = lane; c < Dp; c += WAVE) {
+                const double x = gX[(size_t)row * Dp + c];
+                s += x * x;
+            }
+            s = wave_sum(s);
+            if (lane == 0) nrm[row] = sqrt(s);
         }
-        s = wave_sum(s);
-        if (lane == 0) nrm[row] = sqrt(s);
-    }
-    __syncthreads();
-    for (int k = tid; k < K; k += NT) {
-        const double mine = nrm[k];
-        int r = 0;
-        for (int j = 0; j < K; ++j) {
-            const double o = nrm[j];
-            r += (o > mine) || (o == mine && j < k);
+        __syncthreads();
+        for (int k = tid; k < K; k += NT) {
+            const double mine = nrm[k];
+            int r = 0;
+            for (int j = 0; j < K; ++j) {
+                const double o = nrm[j];
+                r += (o > mine) || (o == mine && j < k);
+            }
+            order[r] = k;
         }
-        order[r] = k;
     }
     int used = 0;
     for (int a = 0; a < d.nattempt; ++a) {

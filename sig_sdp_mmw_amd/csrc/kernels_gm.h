@@ -292,6 +292,42 @@ struct GmState {
             if (cur.size() > best.size()) best = cur;
         }
     }
+    // The keys of gm.py:11-18 / :81 in scipy's summation orders: kind 0, the column sums of S without its diagonal, accumulated in
+    // ascending row (the CSC matvec behind S.transpose().sum(axis=1)); kind 1, the row sums of Q in stored order.
+    void key_host(int kind, std::vector<double>& key) const {
+        key.assign(K, 0.0);
+        if (kind == 0) {
+            for (int32_t j = 0; j < K; ++j)
+                for (int32_t e = so_indptr[j]; e < so_indptr[j + 1]; ++e) key[so_indices[e]] += so_data[e];
+        } else {
+            for (int32_t k = 0; k < K; ++k) {
+                double s = 0.0;
+                for (int32_t e = q_indptr[k]; e < q_indptr[k + 1]; ++e) s += q_data[e];
+                key[k] = s;
+            }
+        }
+    }
+    // MAX_GAIN / MAX_ASSO in the stable order of -key: pass_host slot by slot; z_out[k] = slot or -1, returns {slots entered, stop, total}
+    void run_host(const double* key, int32_t Z, int32_t nattempt, int32_t* z_out, int& entered, int& stop, int& total) const {
+        std::vector<double> gs(K, 0.0), as(K, 0.0);
+        std::vector<int> mark(K, 0), owner(std::max(G, 1), -1);
+        int stamp = 0;
+        std::vector<int32_t> order(K), cur(K), best;
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] > key[b]; });
+        std::fill(z_out, z_out + K, -1);
+        entered = 0; stop = GM_STOP_SLOTS; total = 0;
+        for (int32_t z = 0; z < Z; ++z) {
+            int32_t n = 0;
+            for (int32_t k : order) if (z_out[k] < 0) cur[n++] = k;
+            pass_host(cur.data(), n, nattempt, gs, as, mark, owner, stamp, best);
+            ++entered;
+            for (int32_t k : best) z_out[k] = z;
+            total += (int)best.size();
+            if (best.empty()) { stop = GM_STOP_EMPTY; break; }
+            if (total == K) { stop = GM_STOP_ALL_ASSIGNED; break; }
+        }
+    }
     // MAX_RAND's user-major assignment: the rounding's greedy (sdp_solver.py:70-101 = gm.py:158-193) for a given user order and
     // per-user slot preference pref[k * Z + r]
     void assign_host(int32_t Z, const int32_t* order, const int32_t* pref, int32_t* z_out, int32_t* rem) const {

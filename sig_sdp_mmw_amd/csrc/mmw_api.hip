@@ -175,6 +175,7 @@ int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, c
         bt->rank_radio = rank_radio;
         bt->eta.assign(B, eta);
         bt->H.resize(B);
+        bt->gmx.resize(B);
         bt->nit.assign(nit, nit + B);
         bt->iter.assign(B, 0);
         bt->active.assign(B, 1);
@@ -187,6 +188,7 @@ int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, c
             const std::string err = build_pattern(bt->H[b], K[b], Z[b], S_indptr[b], S_indices[b], S_data[b], Q_indptr[b], Q_indices[b],
                                                   Q_data[b], h_max[b]);
             if (!err.empty()) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": " + err);
+            bt->gm_extra(b, Q_indptr[b], Q_data[b]);
         }
         if (!bt->host_only) {
             MMW_TRY(check_device("mmw_batch_create", device, DEV_ID));
@@ -259,6 +261,14 @@ int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int sto
 int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t attempt, double* out, int64_t n) {
     return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->round_randv(inst, seed, attempt, out, n); });
 }
+int mmw_batch_factor_random(mmw_batch* b, const int32_t* take, const uint64_t* seeds) {
+    return entry("mmw_batch", !b || !seeds, "null pointer", [&] { return b->factor_random(take, seeds); });
+}
+int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
+                 int32_t* rem_out, double* key_out) {
+    return entry("mmw_batch", !b || !Z || !z_out || !zz_out || !rem_out, "null pointer",
+                 [&] { return b->gm(kind, take, Z, nattempt, z_out, zz_out, rem_out, key_out); });
+}
 // ---- the batched generator and scorer (batch_env_handle.h): the online sweeps' state per time point
 int mmw_batch_env_create(mmw_batch_env** out, int device, int32_t B, const int32_t* K, const int32_t* A, const double* const* ap_xy, double fre_Hz,
                          double txp_offset, double min_s_n_ratio, double min_sinr, double noise_floor_dbm) {
@@ -301,6 +311,11 @@ int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const i
                            double* const* sinr_out, double* const* bler_out) {
     return entry("mmw_batch_env", !e || !z_vec || !Z || !sinr_out, "mmw_batch_env_evaluate: null pointer",
                  [&] { return e->evaluate(z_vec, Z, packet_bit, bandwidth, slot_time, sinr_out, bler_out); });
+}
+int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
+                     int32_t* rem_out, double* key_out) {
+    return entry("mmw_batch_env", !e || !Z || !z_out || !zz_out || !rem_out, "null pointer",
+                 [&] { return e->gm(kind, take, Z, nattempt, z_out, zz_out, rem_out, key_out); });
 }
 int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
                         int32_t* z_out, int32_t* rem_out, int32_t* used_out) {

@@ -126,3 +126,32 @@ class sdp_solver:
         if np.any(not_assigned):
             z_vec[not_assigned] = np.random.randint(Z, size=int(not_assigned.sum()))
         return z_vec, Z, np.sum(not_assigned)
+
+
+class rand_sdp_solver(sdp_solver):
+    """The reference's random embedding (sdp_solver.py:109-114): K x (Z * rank_radio) normals from the global NumPy stream, rows
+    normalised, handed to the device rounding above.  The draw is the reference's own expression, so a seeded script continues
+    with the same stream.
+
+    Every row of the embedding has norm 1, so the rounding's visiting order (descending norm, sdp_solver.py:51) is one tie over all
+    users: sorting the norms as computed sorts their last-bit noise, which changes with the summation order.  `rounding_one_attempt`
+    therefore visits the users in index order, the tie rule taken literally (and what the batch does, `BatchSolver.factor_random`):
+    it hands the device `index_ordered(gX)`, whose norms fall with the index by steps far above the noise.  Scaling a row by a
+    positive number leaves its user's slot preferences as they are."""
+
+    @staticmethod
+    def index_ordered(gX):
+        K = gX.shape[0]
+        return np.asarray(gX, dtype=np.float64) * (1.0 - np.arange(K) * 2.0 ** -32)[:, None]
+
+    def rounding_one_attempt(self, Z, gX, state):
+        return super().rounding_one_attempt(Z, self.index_ordered(gX), state)
+
+    def _rounding_batched(self, Z, gX, state, nattempt):
+        return super()._rounding_batched(Z, self.index_ordered(gX), state, nattempt)
+
+    def run_with_state(self, bs_iteration, Z, state):
+        K = self._state_K(state)
+        randv = np.random.randn(K, Z * self.rank_radio)
+        randv = randv / np.linalg.norm(randv, axis=1, keepdims=True)
+        return True, randv
