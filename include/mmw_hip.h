@@ -337,6 +337,22 @@ int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64
  */
 int mmw_batch_set_gap(mmw_batch* b, int enabled, int32_t m_cap);
 int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n);
+/*
+ * Several workgroups for a large instance (csrc/kernels_batch_split.h).  A batch launch lasts as long as its largest instance runs
+ * on its one workgroup; mmw_batch_set_split gives instance b parts[b] workgroups, 1 ... MMW_BATCH_MAX_PARTS (a value outside is
+ * refused by instance with MMW_ERR_ARG and leaves the setting as it was).  While any instance that runs has parts > 1,
+ * mmw_batch_iterate enqueues every iteration as three launches for all instances together -- head (gap row, averaging, DUAL, softmax,
+ * LOSS: one workgroup per instance), exp(L/2)R (one workgroup per column slice of the sketch: width 8 ceil(ceil(D / parts) / 8)
+ * columns, ceil(D / width) slices, so D < 8 has one) and X on the pattern (one workgroup per range of nnzL / parts stored entries)
+ * -- on the batch's stream, kernel boundaries being the only synchronisation, and returns when all are done.  Every column and every
+ * entry is computed by the same sums in the same order as in the single launch: all fields, the gap log and EXPM_INFO are bitwise
+ * what they are without the split, whatever the parts, the batch neighbours and the split of the iterations into calls.  NULL or all
+ * ones selects the single launch (the default).  The setting survives mmw_batch_reset and mmw_batch_set_slots; the slices follow
+ * the current D at every mmw_batch_iterate.  The work tables live in buffers of their own: the arenas do not move.  MMW_ERR_STATE on
+ * a host-only batch.
+ */
+#define MMW_BATCH_MAX_PARTS 32
+int mmw_batch_set_split(mmw_batch* b, const int32_t* parts);
 /* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
  * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);

@@ -19,6 +19,7 @@ EXPM_LANCZOS, EXPM_TAYLOR = 0, 1
 F_Y, F_E_ACCU, F_E_THIS, F_LVAL, F_XVAL, F_XAVG, F_YAVG, F_XHALF, F_SKETCH = range(9)
 F_S_SUM, F_NORM_H, F_ST_DATA, F_PHASE_US, F_EXPM_INFO, F_FACTOR, F_KERNEL_US, F_BLOCKING, F_SPMM_KIND, F_E_MAX, F_DUAL_INFO = range(9, 20)
 F_FACTOR_INFO = 20
+BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split)
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
@@ -32,7 +33,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
-           "mmw_batch_factor_random"]
+           "mmw_batch_factor_random", "mmw_batch_set_split"]
 
 
 class MMWError(RuntimeError):
@@ -111,6 +112,7 @@ def lib():
     L.mmw_batch_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mmw_batch_set_gap.argtypes = [C.c_void_p, C.c_int, C.c_int32]
     L.mmw_batch_read_gap.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_int64]
+    L.mmw_batch_set_split.argtypes = [C.c_void_p, p_i32]
     L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
     L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
@@ -434,6 +436,8 @@ class BatchSolver:
         self.device = int(device)
         self.nits = [int(x) for x in nits]
         self.active = [True] * B
+        self._auto_split = None
+        self.split_parts = None  # workgroups per instance as last accepted by set_split (None: the single-launch kernel)
         self._load_sizes()
 
     def _load_sizes(self):
@@ -481,6 +485,8 @@ class BatchSolver:
         self.nits = [int(nit)] * self.B
         self.active = [int(x) > 0 for x in z]
         self._load_sizes()
+        if self._auto_split is not None:  # "auto" follows the slot counts
+            self._apply_split(self.suggest_split(self._auto_split))
 
     def iterate(self, n, randv=None, seeds=None):
         """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the
@@ -555,6 +561,47 @@ class BatchSolver:
         check(lib().mmw_batch_read_gap(self._h, int(inst), _pd(out), int(out.size)))
         st = out[:, 3]
         return out[:, :3].copy(), np.where(np.isnan(st), 0, st).astype(np.int64)
+
+    # ---- several workgroups per instance (csrc/kernels_batch_split.h)
+    @staticmethod
+    def split_slices(D, parts):
+        """(W, G): the column slices `parts` workgroups cut D sketch columns into -- G = ceil(D / W) slices of W = 8 ceil(ceil(D / parts) / 8)
+        columns, the last one possibly narrower."""
+        W = 8 * -(-(-(-int(D) // int(parts))) // 8)
+        return W, -(-int(D) // W)
+
+    def suggest_split(self, cus=256):
+        """The rule of set_split("auto"): instance i weighs w_i = nnzL_i D_i (the work of one Taylor term) and gets
+        parts_i = clamp(round(w_i cus / sum w), 1, min(32, ceil(D_i / 8))) workgroups -- its share of `cus` compute units, at most
+        one per 8 sketch columns.  Instances that sit out get 1 and do not weigh."""
+        w = [float(s["nnzL"]) * s["D"] if a else 0.0 for s, a in zip(self.sizes, self.active)]
+        tot = sum(w)
+        if tot <= 0.0:
+            return [1] * self.B
+        return [max(1, min(int(round(wi * cus / tot)), BATCH_MAX_PARTS, -(-s["D"] // 8))) for wi, s in zip(w, self.sizes)]
+
+    def _apply_split(self, parts):
+        p = _i32(np.broadcast_to(np.asarray(parts, dtype=np.int64), (self.B,)))
+        check(lib().mmw_batch_set_split(self._h, _pi(p)))
+        self.split_parts = [int(x) for x in p] if np.any(p > 1) else None
+
+    def set_split(self, parts, cus=256):
+        """Workgroups per instance for the iterations that follow: an int for all, one per instance, "auto" (`suggest_split(cus)`,
+        taken again after every `set_slots`), or None / all ones for the single-launch kernel.  Every field stays bitwise what the
+        single launch gives; an instance gains when it is the straggler of its batch."""
+        if parts is None:
+            check(lib().mmw_batch_set_split(self._h, None))
+            self._auto_split = self.split_parts = None
+        elif isinstance(parts, str):
+            if parts != "auto":
+                raise MMWError("set_split: parts must be an int, one int per instance, \"auto\" or None")
+            self._apply_split(self.suggest_split(cus))
+            self._auto_split = int(cus)
+        else:
+            if np.ndim(parts) and len(parts) != self.B:
+                raise MMWError("set_split: one part count per instance")
+            self._apply_split(parts)
+            self._auto_split = None
 
     def export(self, inst, solver):
         """The instance's iterate into `solver` (an fp64 `Solver` of the same state and Z), which then factors / rounds it."""

@@ -95,6 +95,13 @@ def _fits(b, i):
     return b.sizes[i]["K"] <= _lib.BATCH_EPILOGUE_MAX_K
 
 
+def _split(b, split):
+    """The `split=` keyword of the workflows: None is the single-launch kernel; an int, one int per instance or "auto" goes to
+    `BatchSolver.set_split` (every result stays bitwise the same; see there)."""
+    if split is not None:
+        b.set_split(split)
+
+
 def _finish(z, rem, used, i, Z, seed):
     """The attempt sdp_solver.rounding returns (sdp_solver.py:21-25: the first with remainder 0, else the last) out of a batch `round`,
     users left over drawn from a generator keyed by the probe seed (:104-105)."""
@@ -106,7 +113,7 @@ def _finish(z, rem, used, i, Z, seed):
     return z_vec, Z, int(rem[i][a])
 
 
-def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle"):
+def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle", split=None):
     """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
     X_half per instance through export + mmw_factor on one reused fp64 handle per state, or with epilogue="batch" all of them in one
     more launch (instances over the epilogue limit still go through a handle).  Returns [(True, X_half), ...]."""
@@ -116,6 +123,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
     b = _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device)
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
+        _split(b, split)
         b.iterate(nit, None, seeds)
         take = [in_batch and _fits(b, i) for i in range(len(states))]
         if any(take):
@@ -127,7 +135,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
         b.close()
 
 
-def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0):
+def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, split=None):
     """The reference's convergence sweeps (sim_convergence_rho.py, sim_all_mmw.py: LOG_GAP = True, one run per instance) as one
     batch: `nit` and `eta` are one value for all or one per instance, the gap is logged inside the launch (mmw.py:79-117) and all
     iterations of all instances run in ONE `iterate`.  Returns per instance {"gap": [nit, 3], "lanczos_steps": [nit]}; the three
@@ -140,6 +148,7 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0):
     try:
         b.set_eta(etas)
         b.set_gap(True)
+        _split(b, split)
         b.iterate(max(nits), None, seeds)
         out = []
         for i in range(B):
@@ -150,12 +159,13 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0):
         b.close()
 
 
-def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None):
+def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
     Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
     factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
     one {"probes", "iterate_s", "epilogue_s"} per round (epilogue_s: everything of the round after `iterate`, the bisection's own
-    bookkeeping included)."""
+    bookkeeping included).  split: workgroups per instance (`BatchSolver.set_split`: an int, one per instance or "auto", which
+    follows the slot counts of every round; None: one each); the results are bitwise the same."""
     in_batch = _check_epilogue(epilogue)
     B = len(states)
     bs = binary_search_relaxation()
@@ -169,6 +179,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     b = _lib.BatchSolver(mids, states, nit, eta, rank_radio=rank_radio, device=device)
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
+        _split(b, split)
         while not all(done):
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
             b.set_slots(mids, nit)
@@ -204,7 +215,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
 
 
 def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
-                rank_radio=2, device=0, timings=None):
+                rank_radio=2, device=0, timings=None, split=None):
     """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
     many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
     the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
@@ -221,13 +232,14 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
             raise ValueError("online_many: instance %d has K = %d users, over the batch epilogue's limit %d" % (i, d.K, _lib.BATCH_EPILOGUE_MAX_K))
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
-    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch")
+    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
     b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
     env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
     try:
+        _split(b, split)
         b.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
         b.factor()
         for p in range(n_points):
@@ -299,7 +311,7 @@ def _geometry(d):
     return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
 
 
-def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None):
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
     (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
@@ -312,7 +324,7 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         env.move([g[0] for g in geo])
         states = [env.state(i) for i in range(B)]
         t0 = time.perf_counter()
-        found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch")
+        found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split)
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -370,18 +382,20 @@ class single:
     """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
     one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle"):
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None):
         self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
         self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
         self._in_batch = _check_epilogue(epilogue) and state[0].shape[0] <= _lib.BATCH_EPILOGUE_MAX_K
         self.probes = []
         self._b = None
+        self._split = split
         self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
 
     def run_with_state(self, bs_iteration, Z, state):
         Z = int(Z)
         if self._b is None:
             self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
+            _split(self._b, self._split)
         self._b.set_slots([Z], self.nit)
         self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])
         if self._in_batch:

@@ -6,6 +6,7 @@
 #include "kernels_batch.h"
 #include "kernels_batch_epilogue.h"
 #include "kernels_batch_gm.h"
+#include "kernels_batch_split.h"
 #include "solver.h"
 
 struct mmw_batch {
@@ -28,6 +29,12 @@ struct mmw_batch {
     std::vector<GapDesc> gdesc;
     DevBuf<double> ga;
     DevBuf<GapDesc> d_gdesc;
+    // the split (mmw_batch_set_split, kernels_batch_split.h): workgroups per instance (empty: one each, the single-launch kernel); the
+    // work tables and the slab of per-slice Taylor degrees are buffers of its own, rebuilt from `parts` and the current D per call
+    std::vector<int> parts;
+    DevBuf<SplitSlice> d_wexpm;
+    DevBuf<SplitRange> d_wx;
+    DevBuf<double> slab;
     // the epilogue (mmw_batch_factor / mmw_batch_round, kernels_batch_epilogue.h): buffers of its own, made on first use and sized for
     // the taking instances of the call; the state's rounding lists go up once (they do not depend on the slot count)
     std::vector<FactorDesc> fdesc;  // per instance: where its factor of the last mmw_batch_factor lies (rank 0: none)
@@ -178,6 +185,45 @@ struct mmw_batch {
         gap_mcap = m_cap <= 0 ? GAP_DEFAULT_M : m_cap;
         return MMW_OK;
     }
+    int set_split(const int32_t* p) {
+        if (host_only) return host_only_batch();
+        bool any = false;
+        for (int b = 0; p && b < B; ++b) {
+            if (p[b] < 1 || p[b] > BATCH_MAX_PARTS)
+                return fail(MMW_ERR_ARG, "mmw_batch_set_split: instance " + std::to_string(b) + ": parts = " + std::to_string(p[b]) + " is outside [1, " +
+                                             std::to_string(BATCH_MAX_PARTS) + "]");
+            any = any || p[b] > 1;
+        }
+        if (any) parts.assign(p, p + B);
+        else parts.clear();
+        return MMW_OK;
+    }
+    // One iteration as three launches for all instances (kernels_batch_split.h); `dd` is on the device already.
+    int iterate_split(const std::vector<BatchDesc>& dd, const double* rv) {
+        std::vector<SplitSlice> we;
+        std::vector<SplitRange> wx;
+        int nmax = 0;
+        for (int b = 0; b < B; ++b) {
+            const BatchDesc& d = dd[b];
+            if (d.nrun <= 0) continue;
+            nmax = std::max(nmax, d.nrun);
+            const int W = split_width(d.D, parts[b]), G = split_slices(d.D, parts[b]), slab0 = (int)we.size();
+            for (int g = 0; g < G; ++g) we.push_back(SplitSlice{b, g, W, slab0 + g});
+            for (int p = 0; p < parts[b]; ++p) wx.push_back(SplitRange{b, p, parts[b], slab0, G});
+        }
+        MMW_TRY(d_wexpm.upload(we, st));
+        MMW_TRY(d_wx.upload(wx, st));
+        MMW_TRY(slab.alloc(we.size()));
+        for (int it = 0; it < nmax; ++it) {
+            if (gap_on)
+                hipLaunchKernelGGL(k_batch_split_head<true>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, d_gdesc.p, ga.p, it);
+            else
+                hipLaunchKernelGGL(k_batch_split_head<false>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, (const GapDesc*)nullptr, (double*)nullptr, it);
+            hipLaunchKernelGGL(k_batch_split_expm, dim3((unsigned)we.size()), dim3(BATCH_THREADS), 0, st, d_desc.p, d_wexpm.p, ia.p, fa.p, rv, slab.p, it);
+            hipLaunchKernelGGL(k_batch_split_x, dim3((unsigned)wx.size()), dim3(BATCH_THREADS), 0, st, d_desc.p, d_wx.p, ia.p, fa.p, slab.p, it);
+        }
+        return MMW_OK;
+    }
     int read_gap(int b, double* out, int64_t n) {
         MMW_TRY(check_inst(b));
         if (host_only) return host_only_batch();
@@ -217,6 +263,7 @@ struct mmw_batch {
         std::vector<BatchDesc> dd = desc;
         int64_t off = 0;
         int runs = 0;
+        bool split = false;
         for (int b = 0; b < B; ++b) {
             BatchDesc& d = dd[b];
             d.nrun = active[b] ? std::min(n, nit[b] - iter[b]) : 0;
@@ -225,6 +272,7 @@ struct mmw_batch {
             d.seed = seeds ? seeds[b] : 0;
             if (randv && d.nrun > 0) { d.o_randv = off; off += (int64_t)d.nrun * d.K * d.D; }
             runs += d.nrun > 0;
+            split = split || (d.nrun > 0 && !parts.empty() && parts[b] > 1);
         }
         if (!runs) return fail(MMW_ERR_STATE, "mmw_batch_iterate: every instance has run its announced iterations");
         if (randv) MMW_TRY(rbuf.alloc((size_t)off));
@@ -234,6 +282,10 @@ struct mmw_batch {
         if (gap_on) {
             for (int b = 0; b < B; ++b) gdesc[b].m_cap = gap_mcap;
             MMW_TRY(copy_h2d(d_gdesc.p, gdesc.data(), gdesc.size() * sizeof(GapDesc), st));
+        }
+        if (split) {
+            MMW_TRY(iterate_split(dd, rv));
+        } else if (gap_on) {
             hipLaunchKernelGGL(k_mmw_batch<true>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, rv, d_gdesc.p, ga.p);
         } else {
             hipLaunchKernelGGL(k_mmw_batch<false>, dim3(B), dim3(BATCH_THREADS), 0, st, d_desc.p, ia.p, fa.p, rv, (const GapDesc*)nullptr, (double*)nullptr);

@@ -55,8 +55,9 @@ struct BatchDesc {
 
 // The row-normalised Philox sketch of (seed, iteration) with the layout of kernels_loop.h's sketch_rows for fp64 (one wave per row,
 // lane l draws column pairs l + 64 i, i < 4; the squared norm in the same order and the same wave reduction): the block is bitwise
-// the one a handle's mmw_sketch returns for that (seed, iteration).  R is K x D, row-major, stride D.
-__device__ __forceinline__ void batch_sketch_rows(int K, int D, uint64_t seed, uint32_t iter, double* __restrict__ R) {
+// the one a handle's mmw_sketch returns for that (seed, iteration).  R is K x D, row-major, stride D.  Every row is drawn whole (its
+// norm needs all D columns); only the columns [c0, c1) are written: 0, D for the whole block, a slice for kernels_batch_split.h.
+__device__ __forceinline__ void batch_sketch_rows(int K, int D, uint64_t seed, uint32_t iter, double* __restrict__ R, int c0, int c1) {
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
     const int ngroups = (D + 1) >> 1;
     for (int row = wib; row < K; row += nw) {
@@ -84,14 +85,14 @@ __device__ __forceinline__ void batch_sketch_rows(int K, int D, uint64_t seed, u
             const int p = lane + WAVE * i;
 #pragma unroll
             for (int v = 0; v < 2; ++v)
-                if (p * 2 + v < D) R[(size_t)row * D + p * 2 + v] = n[i][v] * inv;
+                if (p * 2 + v >= c0 && p * 2 + v < c1) R[(size_t)row * D + p * 2 + v] = n[i][v] * inv;
         }
     }
 }
 
 // one sketch block per workgroup (mmw_batch_sketch)
 __global__ __launch_bounds__(BATCH_THREADS) void k_batch_sketch(int K, int D, uint64_t seed, uint32_t iter, double* __restrict__ R) {
-    batch_sketch_rows(K, D, seed, iter, R);
+    batch_sketch_rows(K, D, seed, iter, R, 0, D);
 }
 
 // ---- the duality gap of one iteration (mmw.py:79-117), a phase of the instance's workgroup ----------------------------------------
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_mmw_batch(const BatchDesc* __
             const double* src = randv + d.o_randv + (size_t)it * KD;
             for (size_t i = tid; i < KD; i += NT) R[i] = src[i];
         } else {
-            batch_sketch_rows(K, D, d.seed, (uint32_t)gi, R);
+            batch_sketch_rows(K, D, d.seed, (uint32_t)gi, R, 0, D);
         }
         __syncthreads();
         // ---- exp(A) R by nsub substeps of degree <= mo with a per-column stop (mmw.py:180, 228)

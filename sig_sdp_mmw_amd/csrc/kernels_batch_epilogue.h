@@ -214,7 +214,7 @@ struct FactorRandomDesc {
 };
 __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor_random(const FactorRandomDesc* __restrict__ descs, double* ew) {
     const FactorRandomDesc d = descs[blockIdx.x];
-    batch_sketch_rows(d.K, d.D, d.seed, 0u, ew + d.o_fac);
+    batch_sketch_rows(d.K, d.D, d.seed, 0u, ew + d.o_fac, 0, d.D);
     if ((int)threadIdx.x < EPI_INFO) ew[d.o_info + threadIdx.x] = threadIdx.x == 2 ? (double)d.D : 0.0;
 }
 

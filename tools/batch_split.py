@@ -1,0 +1,103 @@
+"""Developer tool (GPU box): what the batch's split mode (BatchSolver.set_split, csrc/kernels_batch_split.h) buys, fp64, device
+sketches, default expm tolerance (1e-9).
+
+    python tools/batch_split.py [--legs a,b,c,d,e] [--nit 150] [--er-nit 30] [--runs 3] [--limit 240] [--cus 256]
+
+Legs, each `--runs` times under its own time limit (the process ends if a leg overruns it), one JSON line per run:
+  a  the 64-instance journal sweep (tools/batch_small.py's, K 75 ... 675), single-launch kernel
+  b  the same sweep with set_split("auto")
+  c  the same sweep on handles, 8 streams (tools/batch_small.py's leg)
+  d  one K = 675 instance at parts 1, 4, 8, 16: ms per iteration
+  e  er-5pct-2k x 8 (K 2 000, D 64) single launch and at the auto split (report only: D = 64 caps it at 8 slices)
+and a summary line: median(b) against min(a) -- the bar -- and against median(c)."""
+import argparse
+import faulthandler
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from batch_small import run_handles, sweep  # noqa: E402
+from sig_sdp_mmw_amd import _lib  # noqa: E402
+from sig_sdp_mmw_amd.graphs import er_contention_graph  # noqa: E402
+
+
+def run(states, Zs, nit, split, cus, eta=0.04):
+    b = _lib.BatchSolver(Zs, states, nit, eta)
+    if split is not None:
+        b.set_split(split, cus) if split == "auto" else b.set_split(split)
+    parts = b.split_parts
+    t0 = time.perf_counter()
+    b.iterate(nit, None, np.arange(len(states), dtype=np.uint64) + 1)
+    t = time.perf_counter() - t0
+    b.close()
+    return t, parts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="a,b,c,d,e")
+    ap.add_argument("--nit", type=int, default=150)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
+    ap.add_argument("--cus", type=int, default=256)
+    ap.add_argument("--er-nit", type=int, default=30)
+    ap.add_argument("--instances", type=int, default=64)
+    a = ap.parse_args()
+    legs = [x for x in a.legs.split(",") if x]
+    s0, z0 = sweep(2)
+    run(s0, z0, 2, None, a.cus)
+    run(s0, z0, 2, 2, a.cus)  # module load, first launches
+    states, Zs = sweep(a.instances)
+    B = len(states)
+    times = {}
+
+    def leg(name, fn, **extra):
+        faulthandler.dump_traceback_later(a.limit, exit=True)
+        for r in range(a.runs):
+            t, more = fn()
+            times.setdefault(name, []).append(t)
+            print(json.dumps({"leg": name, "run": r, "seconds": round(t, 4), **extra, **more}), flush=True)
+        faulthandler.cancel_dump_traceback_later()
+
+    def batch_leg(split):
+        def fn():
+            t, parts = run(states, Zs, a.nit, split, a.cus)
+            return t, {"instances": B, "nit": a.nit, "instances_per_s": round(B / t, 2),
+                       "workgroups": int(sum(parts)) if parts else B, "max_parts": int(max(parts)) if parts else 1}
+        return fn
+    if "a" in legs:
+        leg("a", batch_leg(None), path="batch")
+    if "b" in legs:
+        leg("b", batch_leg("auto"), path="batch-split-auto")
+    if "c" in legs:
+        leg("c", lambda: (run_handles(states, Zs, a.nit), {"instances": B, "nit": a.nit}), path="handles-8-streams")
+    if "d" in legs:
+        i675 = max(range(B), key=lambda i: states[i][0].shape[0])
+        for parts in (1, 4, 8, 16):
+            def fn(parts=parts):
+                t, _ = run([states[i675]], [Zs[i675]], a.nit, parts, a.cus)
+                return t, {"K": int(states[i675][0].shape[0]), "Z": int(Zs[i675]), "ms_per_iteration": round(t * 1e3 / a.nit, 4)}
+            leg("d%d" % parts, fn, path="one-instance", parts=parts)
+    if "e" in legs:
+        er = [er_contention_graph(2000, 0.05, seed=100 + i) for i in range(8)]
+        for split in (None, "auto"):
+            def fn(split=split):
+                t, parts = run(er, [32] * 8, a.er_nit, split, a.cus)
+                return t, {"instances": 8, "nit": a.er_nit, "instances_per_s": round(8 / t, 2), "max_parts": int(max(parts)) if parts else 1}
+            leg("e-" + ("auto" if split else "single"), fn, path="er-5pct-2k-x8")
+    if "a" in times and "b" in times:
+        out = {"summary": "median(b) against min(a)", "min_a_s": round(min(times["a"]), 4), "median_b_s": round(statistics.median(times["b"]), 4),
+               "bar_met": statistics.median(times["b"]) < min(times["a"])}
+        if "c" in times:
+            out["median_c_s"] = round(statistics.median(times["c"]), 4)
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
