@@ -68,6 +68,9 @@ enum mmw_field {
                              ... with the matrix in one fp16 half} */
     MMW_F_FACTOR_INFO = 20, /* [5]    mmw_batch_factor's record of an instance: {Jacobi sweeps, largest |cos| of a row pair as met in the last sweep (<= 1e-15 when it ended without a rotation),
                              rank, sigma_rank, sigma_rank+1 (0 if rank = K)}; batches only */
+    MMW_F_FACTOR_CALL = 21, /* [4]    the last mmw_batch_factor of a batch, kept on the host, the same for every instance: {path: 0 = one launch
+                             (k_batch_factor), 1 = one launch per round (mmw_batch_set_factor_split); kernel launches enqueued; sweeps
+                             the host loop ran (path 0: 0); workgroups of the largest launch}; zeros before the first call; batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -400,6 +403,25 @@ int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h);
  * Z * rank of the instance's resident factor).
  */
 #define MMW_BATCH_EPILOGUE_MAX_K 1024
+/*
+ * Several workgroups for the factor of a large instance (csrc/kernels_batch_factor_split.h).  mmw_batch_factor lasts as long as the
+ * dense Jacobi of its largest instance runs on its one workgroup; mmw_batch_set_factor_split gives instance b parts[b] workgroups per
+ * tournament round, 1 ... MMW_BATCH_MAX_PARTS (a value outside is refused by instance with MMW_ERR_ARG and leaves the setting as it
+ * was).  While any TAKING instance of a call has parts > 1, mmw_batch_factor enqueues the factors of all taking instances together as
+ * head (Xbar into the dense work matrix: one workgroup per instance), one launch per round of the tournament (one workgroup per item:
+ * a contiguous range of ceil(P / parts) of the instance's P = ceil(K / 2) row pairs, ceil(P / that) <= parts items, none empty; an
+ * instance with parts = 1 has one), one small launch per sweep that sums the items' rotation counts and largest |cos|, and tail (row
+ * norms, the rank cut, X_half, the record) -- on the batch's stream, kernel boundaries being the only synchronisation, with one host
+ * synchronisation per sweep to drop the instances that have ended from the later launches.  A row pair is reduced and rotated by one
+ * wave whichever workgroup takes it, and a sweep's rotation count and largest |cos| are exact in any order: MMW_F_FACTOR,
+ * MMW_F_FACTOR_INFO and everything mmw_batch_round makes of them are bitwise what the single launch gives, whatever the parts, the
+ * batch neighbours and `take`.  Argument checks, parity mode (xavg) and the stderr line at the sweep cap are those of the single
+ * launch.  NULL or all ones selects the single launch (the default).  The setting survives mmw_batch_reset and mmw_batch_set_slots; the
+ * items follow the instances' K at every mmw_batch_factor.  The item table, the slab of per-item sums and the sweep records live in
+ * buffers of their own: the epilogue's work space keeps its layout.  MMW_F_FACTOR_CALL says which path the last call took.
+ * MMW_ERR_STATE on a host-only batch.
+ */
+int mmw_batch_set_factor_split(mmw_batch* b, const int32_t* parts);
 int mmw_batch_factor(mmw_batch* b, const int32_t* take, const int32_t* rank, const double* const* xavg);
 int mmw_batch_round(mmw_batch* b, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out,
                     int32_t* rem_out, int32_t* used_out);

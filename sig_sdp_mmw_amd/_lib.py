@@ -19,7 +19,8 @@ EXPM_LANCZOS, EXPM_TAYLOR = 0, 1
 F_Y, F_E_ACCU, F_E_THIS, F_LVAL, F_XVAL, F_XAVG, F_YAVG, F_XHALF, F_SKETCH = range(9)
 F_S_SUM, F_NORM_H, F_ST_DATA, F_PHASE_US, F_EXPM_INFO, F_FACTOR, F_KERNEL_US, F_BLOCKING, F_SPMM_KIND, F_E_MAX, F_DUAL_INFO = range(9, 20)
 F_FACTOR_INFO = 20
-BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split)
+F_FACTOR_CALL = 21
+BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
@@ -33,7 +34,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
-           "mmw_batch_factor_random", "mmw_batch_set_split"]
+           "mmw_batch_factor_random", "mmw_batch_set_split", "mmw_batch_set_factor_split"]
 
 
 class MMWError(RuntimeError):
@@ -113,6 +114,7 @@ def lib():
     L.mmw_batch_set_gap.argtypes = [C.c_void_p, C.c_int, C.c_int32]
     L.mmw_batch_read_gap.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_int64]
     L.mmw_batch_set_split.argtypes = [C.c_void_p, p_i32]
+    L.mmw_batch_set_factor_split.argtypes = [C.c_void_p, p_i32]
     L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
     L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
@@ -438,6 +440,8 @@ class BatchSolver:
         self.active = [True] * B
         self._auto_split = None
         self.split_parts = None  # workgroups per instance as last accepted by set_split (None: the single-launch kernel)
+        self._auto_factor_split = False
+        self.factor_split_parts = None  # the same for the factor, as last accepted by set_factor_split (None: k_batch_factor's one launch)
         self._load_sizes()
 
     def _load_sizes(self):
@@ -487,6 +491,8 @@ class BatchSolver:
         self._load_sizes()
         if self._auto_split is not None:  # "auto" follows the slot counts
             self._apply_split(self.suggest_split(self._auto_split))
+        if self._auto_factor_split:
+            self._apply_factor_split(self.suggest_factor_split())
 
     def iterate(self, n, randv=None, seeds=None):
         """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the
@@ -602,6 +608,50 @@ class BatchSolver:
                 raise MMWError("set_split: one part count per instance")
             self._apply_split(parts)
             self._auto_split = None
+
+    # ---- several workgroups per instance for the factor (csrc/kernels_batch_factor_split.h)
+    @staticmethod
+    def factor_items(K, parts):
+        """[(first pair, count), ...]: the items `parts` workgroups cut the P = ceil((K + (K & 1)) / 2) row pairs of a tournament round
+        into -- contiguous ranges of ceil(P / parts) pairs, G = ceil(P / that) <= parts of them, none empty."""
+        K, parts = int(K), int(parts)
+        P = (K + (K & 1)) // 2
+        per = -(-P // parts)
+        return [(p0, min(per, P - p0)) for p0 in range(0, P, per)]
+
+    def suggest_factor_split(self):
+        """The rule of set_factor_split("auto"): parts_i = clamp(ceil(P_i / 16), 1, 32) with P_i the row pairs of a round, so each of a
+        workgroup's eight waves holds at most one two-pair step per round.  Instances that sit out get 1."""
+        return [max(1, min(-(-((s["K"] + (s["K"] & 1)) // 2) // 16), BATCH_MAX_PARTS)) if a else 1 for s, a in zip(self.sizes, self.active)]
+
+    def _apply_factor_split(self, parts):
+        p = _i32(np.broadcast_to(np.asarray(parts, dtype=np.int64), (self.B,)))
+        check(lib().mmw_batch_set_factor_split(self._h, _pi(p)))
+        self.factor_split_parts = [int(x) for x in p] if np.any(p > 1) else None
+
+    def set_factor_split(self, parts):
+        """Workgroups per instance and tournament round for the `factor` calls that follow: an int for all, one per instance, "auto"
+        (`suggest_factor_split()`, taken again after every `set_slots`), or None / all ones for the one launch of k_batch_factor.  The
+        factor, its record and every rounding stay bitwise what the single launch gives."""
+        if parts is None:
+            check(lib().mmw_batch_set_factor_split(self._h, None))
+            self._auto_factor_split, self.factor_split_parts = False, None
+        elif isinstance(parts, str):
+            if parts != "auto":
+                raise MMWError("set_factor_split: parts must be an int, one int per instance, \"auto\" or None")
+            self._apply_factor_split(self.suggest_factor_split())
+            self._auto_factor_split = True
+        else:
+            if np.ndim(parts) and len(parts) != self.B:
+                raise MMWError("set_factor_split: one part count per instance")
+            self._apply_factor_split(parts)
+            self._auto_factor_split = False
+
+    def factor_call(self):
+        """The last `factor` of this batch (MMW_F_FACTOR_CALL): {"path": 0 one launch / 1 one launch per round, "launches", "sweeps"
+        (of the host loop; path 0: 0), "widest" (workgroups of the largest launch)}."""
+        v = self.read(0, F_FACTOR_CALL, 4)
+        return {"path": int(v[0]), "launches": int(v[1]), "sweeps": int(v[2]), "widest": int(v[3])}
 
     def export(self, inst, solver):
         """The instance's iterate into `solver` (an fp64 `Solver` of the same state and Z), which then factors / rounds it."""

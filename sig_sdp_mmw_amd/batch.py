@@ -102,6 +102,18 @@ def _split(b, split):
         b.set_split(split)
 
 
+def _factor_split(b, factor_split, in_batch=True):
+    """The `factor_split=` keyword of the workflows: None is k_batch_factor's one launch; an int, one int per instance or "auto" goes
+    to `BatchSolver.set_factor_split` (every result stays bitwise the same; see there).  There is no batch factor to split under
+    epilogue="handle"."""
+    if factor_split is None:
+        return
+    if not in_batch:
+        raise ValueError('factor_split needs epilogue="batch": the handle epilogue has no batch factor to split')
+    if b is not None:
+        b.set_factor_split(factor_split)
+
+
 def _finish(z, rem, used, i, Z, seed):
     """The attempt sdp_solver.rounding returns (sdp_solver.py:21-25: the first with remainder 0, else the last) out of a batch `round`,
     users left over drawn from a generator keyed by the probe seed (:104-105)."""
@@ -113,17 +125,21 @@ def _finish(z, rem, used, i, Z, seed):
     return z_vec, Z, int(rem[i][a])
 
 
-def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle", split=None):
+def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle", split=None,
+                        factor_split=None):
     """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
     X_half per instance through export + mmw_factor on one reused fp64 handle per state, or with epilogue="batch" all of them in one
-    more launch (instances over the epilogue limit still go through a handle).  Returns [(True, X_half), ...]."""
+    more launch (instances over the epilogue limit still go through a handle).  factor_split: workgroups per instance for that
+    factor (`BatchSolver.set_factor_split`; epilogue="batch" only).  Returns [(True, X_half), ...]."""
     del bs_iteration  # the log index of the reference's signature; nothing here depends on it
     in_batch = _check_epilogue(epilogue)
+    _factor_split(None, factor_split, in_batch)
     seeds = np.arange(len(states), dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
     b = _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device)
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
         _split(b, split)
+        _factor_split(b, factor_split, in_batch)
         b.iterate(nit, None, seeds)
         take = [in_batch and _fits(b, i) for i in range(len(states))]
         if any(take):
@@ -159,14 +175,18 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
         b.close()
 
 
-def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None):
+def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None,
+                factor_split=None):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
     Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
     factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
-    one {"probes", "iterate_s", "epilogue_s"} per round (epilogue_s: everything of the round after `iterate`, the bisection's own
-    bookkeeping included).  split: workgroups per instance (`BatchSolver.set_split`: an int, one per instance or "auto", which
-    follows the slot counts of every round; None: one each); the results are bitwise the same."""
+    one {"probes", "iterate_s", "epilogue_s", "factor_call"} per round (epilogue_s: everything of the round after `iterate`, the
+    bisection's own bookkeeping included; factor_call: `BatchSolver.factor_call()` of the round's batch factor, None without one).  split: workgroups per instance (`BatchSolver.set_split`: an int, one per instance or "auto", which
+    follows the slot counts of every round; None: one each); the results are bitwise the same.  factor_split: the same for the
+    factor of epilogue="batch" (`BatchSolver.set_factor_split`; with epilogue="handle" anything but None raises ValueError), bitwise
+    too."""
     in_batch = _check_epilogue(epilogue)
+    _factor_split(None, factor_split, in_batch)
     B = len(states)
     bs = binary_search_relaxation()
     bounds = [bs.set_bounds(st) for st in states]
@@ -180,6 +200,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
         _split(b, split)
+        _factor_split(b, factor_split, in_batch)
         while not all(done):
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
             b.set_slots(mids, nit)
@@ -207,7 +228,8 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
                     done[i] = True
                     out[i] = {"Z": Z, "z_vec": z_vec, "remainder": rem, "probes": probes[i], "bounds": bounds[i]}
             if timings is not None:
-                timings.append({"probes": int(sum(1 for m in mids if m > 0)), "iterate_s": t1 - t0, "epilogue_s": time.perf_counter() - t1})
+                timings.append({"probes": int(sum(1 for m in mids if m > 0)), "iterate_s": t1 - t0, "epilogue_s": time.perf_counter() - t1,
+                                "factor_call": b.factor_call() if any(take) else None})
         return out
     finally:
         hs.close()
@@ -215,7 +237,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
 
 
 def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
-                rank_radio=2, device=0, timings=None, split=None):
+                rank_radio=2, device=0, timings=None, split=None, factor_split=None):
     """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
     many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
     the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
@@ -225,14 +247,16 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     drop walks `step_us` microseconds (one value, or one per instance: the reference passes its own measured search time; 0 is its
     "ideal" variant -- nobody moves, fresh draws per point).  The drops are moved in place.
     Returns per instance {"Z", "probes", "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]}.  timings: a list
-    that receives one {"device_s" (move + round + evaluate), "step_s" (the host's walk)} per point."""
+    that receives one {"device_s" (move + round + evaluate), "step_s" (the host's walk)} per point.  factor_split: workgroups per
+    instance for every factor, the search's and the last solve's (`BatchSolver.set_factor_split`)."""
     B = len(drops)
     for i, d in enumerate(drops):
         if d.K > _lib.BATCH_EPILOGUE_MAX_K:
             raise ValueError("online_many: instance %d has K = %d users, over the batch epilogue's limit %d" % (i, d.K, _lib.BATCH_EPILOGUE_MAX_K))
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
-    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split)
+    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
+                        factor_split=factor_split)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
@@ -240,6 +264,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
     try:
         _split(b, split)
+        _factor_split(b, factor_split)
         b.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
         b.factor()
         for p in range(n_points):
@@ -311,11 +336,12 @@ def _geometry(d):
     return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
 
 
-def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None):
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
     (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
-    "mgain", "masso"}}.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"}."""
+    "mgain", "masso"}}.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"}.  factor_split: workgroups per instance
+    for the search's factors (`BatchSolver.set_factor_split`)."""
     geo = [_geometry(d) for d in drops_or_geometries]
     B = len(geo)
     env = _lib.BatchEnv([g[1] for g in geo], [g[0].shape[0] for g in geo], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
@@ -324,7 +350,8 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         env.move([g[0] for g in geo])
         states = [env.state(i) for i in range(B)]
         t0 = time.perf_counter()
-        found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split)
+        found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
+                            factor_split=factor_split)
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -382,13 +409,15 @@ class single:
     """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
     one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None):
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None):
         self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
         self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
+        _factor_split(None, factor_split, _check_epilogue(epilogue))
         self._in_batch = _check_epilogue(epilogue) and state[0].shape[0] <= _lib.BATCH_EPILOGUE_MAX_K
         self.probes = []
         self._b = None
         self._split = split
+        self._factor_split = factor_split
         self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
 
     def run_with_state(self, bs_iteration, Z, state):
@@ -396,6 +425,7 @@ class single:
         if self._b is None:
             self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
             _split(self._b, self._split)
+            _factor_split(self._b, self._factor_split)
         self._b.set_slots([Z], self.nit)
         self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])
         if self._in_batch:

@@ -5,6 +5,7 @@
 
 #include "kernels_batch.h"
 #include "kernels_batch_epilogue.h"
+#include "kernels_batch_factor_split.h"
 #include "kernels_batch_gm.h"
 #include "kernels_batch_split.h"
 #include "solver.h"
@@ -43,6 +44,13 @@ struct mmw_batch {
     DevBuf<FactorDesc> d_fdesc;
     DevBuf<RoundDesc> d_rdesc;
     DevBuf<FactorRandomDesc> d_frdesc;
+    // the factor's split (mmw_batch_set_factor_split, kernels_batch_factor_split.h): workgroups per instance and round (empty: one
+    // launch, k_batch_factor); the item table, the spans, the slab and the sweep records are buffers of its own, rebuilt per call
+    std::vector<int> fparts;
+    DevBuf<FactorItem> d_fitems;
+    DevBuf<FactorSpan> d_fspans;
+    DevBuf<double> fslab, frec;
+    double fcall[4] = {0.0, 0.0, 0.0, 0.0};  // MMW_F_FACTOR_CALL: the last mmw_batch_factor {path, launches, host sweeps, largest grid}
     struct RoundLists { int64_t soptr, soidx, qptr, qidx, sodata, sohmax, hmax; };
     std::vector<RoundLists> rlists;
     // the greedy baselines (mmw_batch_gm, kernels_batch_gm.h): what the pattern does not keep of Q -- its values, and the clique
@@ -198,6 +206,19 @@ struct mmw_batch {
         else parts.clear();
         return MMW_OK;
     }
+    int set_factor_split(const int32_t* p) {
+        if (host_only) return host_only_batch();
+        bool any = false;
+        for (int b = 0; p && b < B; ++b) {
+            if (p[b] < 1 || p[b] > BATCH_MAX_PARTS)
+                return fail(MMW_ERR_ARG, "mmw_batch_set_factor_split: instance " + std::to_string(b) + ": parts = " + std::to_string(p[b]) + " is outside [1, " +
+                                             std::to_string(BATCH_MAX_PARTS) + "]");
+            any = any || p[b] > 1;
+        }
+        if (any) fparts.assign(p, p + B);
+        else fparts.clear();
+        return MMW_OK;
+    }
     // One iteration as three launches for all instances (kernels_batch_split.h); `dd` is on the device already.
     int iterate_split(const std::vector<BatchDesc>& dd, const double* rv) {
         std::vector<SplitSlice> we;
@@ -333,6 +354,7 @@ struct mmw_batch {
             case MMW_F_S_SUM: return read_host(P.S_sum, out, n);
             case MMW_F_NORM_H: return read_host(P.norm_H, out, n);
             case MMW_F_ST_DATA: return read_host(P.st_data, out, n);
+            case MMW_F_FACTOR_CALL: return read_host(std::vector<double>(fcall, fcall + 4), out, n);
             default: break;
         }
         if (host_only) return host_only_batch();
@@ -437,7 +459,14 @@ struct mmw_batch {
             if (fd[b].src_work) MMW_TRY(copy_h2d(ew.p + fd[b].o_src, xavg[b], (size_t)fd[b].nnzL * sizeof(double), st));
         MMW_TRY(d_fdesc.alloc(launch.size()));
         MMW_TRY(copy_h2d(d_fdesc.p, launch.data(), launch.size() * sizeof(FactorDesc), st));
-        hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, st, d_fdesc.p, ia.p, fa.p, ew.p, ei.p);
+        bool split = false;
+        for (int b : tk) split = split || (!fparts.empty() && fparts[b] > 1);
+        if (split) {
+            MMW_TRY(factor_split(tk, launch));
+        } else {
+            hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, st, d_fdesc.p, ia.p, fa.p, ew.p, ei.p);
+            fcall[0] = 0.0; fcall[1] = 1.0; fcall[2] = 0.0; fcall[3] = (double)launch.size();
+        }
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(st));
         // A factor that used up its sweeps while rows still rotated is handed out (its rows are orthogonal to the |cos| it reports),
@@ -451,6 +480,60 @@ struct mmw_batch {
                         tk[t], desc[tk[t]].K, EPI_SWEEP_CAP, r[1]);
         }
         fdesc = std::move(fd);
+        return MMW_OK;
+    }
+    // The factor as head / one launch per round / tail for all taking instances (kernels_batch_factor_split.h); `launch` is on the
+    // device already (d_fdesc).  One synchronisation per sweep: the host reads the sweep records, ends the instances the device has
+    // ended (no rotation, or the cap) and takes their items out of the table, so the grids shrink with the instances still rotating.
+    int factor_split(const std::vector<int>& tk, const std::vector<FactorDesc>& launch) {
+        const int n = (int)tk.size();
+        std::vector<FactorSpan> spans((size_t)n);
+        std::vector<FactorItem> items;
+        int nslot = 0;
+        for (int t = 0; t < n; ++t) {
+            const int K = launch[t].K, parts = fparts[tk[t]];
+            const int P = factor_pairs(K), per = factor_item_pairs(K, parts), G = factor_item_count(K, parts);
+            spans[t] = FactorSpan{nslot, G};
+            for (int g = 0; g < G; ++g) items.push_back(FactorItem{t, g * per, std::min(per, P - g * per), factor_rounds(K), nslot++});
+        }
+        std::stable_sort(items.begin(), items.end(), [](const FactorItem& a, const FactorItem& b) { return a.rounds > b.rounds; });
+        MMW_TRY(d_fspans.upload(spans, st));
+        MMW_TRY(d_fitems.upload(items, st));
+        MMW_TRY(fslab.alloc((size_t)nslot * FSPLIT_SLOT));
+        MMW_TRY(frec.alloc((size_t)n * FSPLIT_REC));
+        hipLaunchKernelGGL(k_batch_factor_head, dim3((unsigned)n), dim3(BATCH_THREADS), 0, st, d_fdesc.p, d_fspans.p, ia.p, fa.p, ew.p, fslab.p, frec.p);
+        int64_t launches = 1, sweeps = 0;
+        size_t widest = std::max((size_t)n, items.size());
+        std::vector<char> live((size_t)n, 1);
+        std::vector<double> rec((size_t)n * FSPLIT_REC);
+        int nlive = n;
+        while (nlive > 0 && sweeps < EPI_SWEEP_CAP) {
+            size_t cnt = items.size();  // items with more than r rounds: a prefix of the table
+            for (int r = 0;; ++r) {
+                while (cnt > 0 && items[cnt - 1].rounds <= r) --cnt;
+                if (cnt == 0) break;
+                hipLaunchKernelGGL(k_batch_factor_round, dim3((unsigned)cnt), dim3(BATCH_THREADS), 0, st, d_fdesc.p, d_fitems.p, ew.p, fslab.p, frec.p, r);
+                ++launches;
+            }
+            hipLaunchKernelGGL(k_batch_factor_sweep, dim3((unsigned)n), dim3(WAVE), 0, st, d_fdesc.p, d_fspans.p, fslab.p, frec.p);
+            ++launches;
+            ++sweeps;
+            MMW_HIP(hipGetLastError());
+            MMW_TRY(copy_d2h(rec.data(), frec.p, rec.size() * sizeof(double), st));
+            bool ended = false;
+            for (int t = 0; t < n; ++t)
+                if (live[t] && rec[(size_t)t * FSPLIT_REC + 3] != 0.0) { live[t] = 0; --nlive; ended = true; }
+            if (ended && nlive > 0) {
+                std::vector<FactorItem> keep;
+                for (const FactorItem& w : items)
+                    if (live[w.inst]) keep.push_back(w);
+                items = std::move(keep);
+                MMW_TRY(d_fitems.upload(items, st));
+            }
+        }
+        hipLaunchKernelGGL(k_batch_factor_tail, dim3((unsigned)n), dim3(BATCH_THREADS), 0, st, d_fdesc.p, frec.p, ew.p, ei.p);
+        ++launches;
+        fcall[0] = 1.0; fcall[1] = (double)launches; fcall[2] = (double)sweeps; fcall[3] = (double)widest;
         return MMW_OK;
     }
     // the state's rounding lists (S_gain without its diagonal, Q_asso, h_max: csrc/pattern.h), all instances, once

@@ -2,10 +2,12 @@
 epilogue on handles (export + mmw_factor + mmw_round per instance) against the epilogue inside the batch (one mmw_batch_factor and
 one mmw_batch_round per round of probes, csrc/kernels_batch_epilogue.h).
 
-    python tools/batch_search.py [--sizes 64,256] [--nit 150] [--runs 3] [--epilogues handle,batch]
+    python tools/batch_search.py [--sizes 64,256] [--nit 150] [--runs 3] [--epilogues handle,batch] [--factor-split auto|N]
 
 Workload: tools/batch_small.py's `sweep(n)` (journal_graph(cell, 75e-4, seed), cells 5..15, K = 75 ... 675).  One JSON line per run:
-wall seconds of the search and, per round of probes, the instances probing and the seconds in `iterate` and in the epilogue."""
+wall seconds of the search and, per round of probes, the instances probing and the seconds in `iterate` and in the epilogue.
+--factor-split adds runs of epilogue="batch" with that `factor_split` (csrc/kernels_batch_factor_split.h) after the others; every line
+carries its `factor_split` and the `factor_call()` of its first round."""
 import argparse
 import json
 import os
@@ -24,20 +26,24 @@ def main():
     ap.add_argument("--nit", type=int, default=150)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epilogues", default="handle,batch")
+    ap.add_argument("--factor-split", default=None, help="auto or an int: further runs of epilogue=batch with this factor_split")
     a = ap.parse_args()
+    legs = [(ep, None) for ep in a.epilogues.split(",") if ep]
+    if a.factor_split is not None:
+        legs.append(("batch", "auto" if a.factor_split == "auto" else int(a.factor_split)))
     s0, _ = sweep(2)
-    for ep in a.epilogues.split(","):
-        batch.search_many(s0, nit=2, epilogue=ep)  # module load, first launches
+    for ep, fs in legs:
+        batch.search_many(s0, nit=2, epilogue=ep, factor_split=fs)  # module load, first launches
     for B in [int(x) for x in a.sizes.split(",") if x]:
         states, _ = sweep(B)
         K = [st[0].shape[0] for st in states]
-        for ep in a.epilogues.split(","):
+        for ep, fs in legs:
             for run in range(a.runs):
                 rounds = []
                 t0 = time.perf_counter()
-                res = batch.search_many(states, nit=a.nit, eta=0.04, seed=run, epilogue=ep, timings=rounds)
+                res = batch.search_many(states, nit=a.nit, eta=0.04, seed=run, epilogue=ep, timings=rounds, factor_split=fs)
                 t = time.perf_counter() - t0
-                print(json.dumps({"workload": "journal-sweep-75e-4", "epilogue": ep, "instances": B, "nit": a.nit, "run": run,
+                print(json.dumps({"workload": "journal-sweep-75e-4", "epilogue": ep, "factor_split": fs, "factor_call": rounds[0]["factor_call"], "instances": B, "nit": a.nit, "run": run,
                                   "K_range": [int(min(K)), int(max(K))], "seconds": round(t, 4), "rounds": len(rounds),
                                   "iterate_s": round(sum(r["iterate_s"] for r in rounds), 4),
                                   "epilogue_s": round(sum(r["epilogue_s"] for r in rounds), 4),
