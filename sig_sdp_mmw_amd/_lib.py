@@ -157,6 +157,19 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _u64(seeds, B):
+    """One uint64 seed per instance, from one for all or one each."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (B,)))
+
+
+def _pu(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _opt_pi(t):
+    return None if t is None else _pi(t)
+
+
 def _gm_call(fn, handle, B, Ks, who, kind, Zs, nattempt, t, keys):
     """mmw_batch_gm / mmw_batch_env_gm: (z list with None for instances left out, ZZ int32[B], rem int32[B][, keys list])."""
     Z = _i32(np.broadcast_to(np.asarray(Zs, dtype=np.int32), (B,)))
@@ -165,7 +178,7 @@ def _gm_call(fn, handle, B, Ks, who, kind, Zs, nattempt, t, keys):
     kflat = np.empty(n, dtype=np.float64) if keys else None
     zz = np.empty(B, dtype=np.int32)
     rem = np.empty(B, dtype=np.int32)
-    check(fn(handle, int(kind), None if t is None else _pi(t), _pi(Z), int(nattempt), _pi(zflat), _pi(zz), _pi(rem), _pd(kflat) if keys else None))
+    check(fn(handle, int(kind), _opt_pi(t), _pi(Z), int(nattempt), _pi(zflat), _pi(zz), _pi(rem), _pd(kflat) if keys else None))
     z, ks, o = [None] * B, [None] * B, 0
     for i in who:
         z[i] = zflat[o:o + Ks[i]]
@@ -438,9 +451,8 @@ class BatchSolver:
         self.device = int(device)
         self.nits = [int(x) for x in nits]
         self.active = [True] * B
-        self._auto_split = None
+        self._auto = {}  # per setter in _SPLITS: the arguments of its suggest function while "auto" holds
         self.split_parts = None  # workgroups per instance as last accepted by set_split (None: the single-launch kernel)
-        self._auto_factor_split = False
         self.factor_split_parts = None  # the same for the factor, as last accepted by set_factor_split (None: k_batch_factor's one launch)
         self._load_sizes()
 
@@ -489,10 +501,8 @@ class BatchSolver:
         self.nits = [int(nit)] * self.B
         self.active = [int(x) > 0 for x in z]
         self._load_sizes()
-        if self._auto_split is not None:  # "auto" follows the slot counts
-            self._apply_split(self.suggest_split(self._auto_split))
-        if self._auto_factor_split:
-            self._apply_factor_split(self.suggest_factor_split())
+        for who, args in self._auto.items():  # "auto" follows the slot counts
+            self._apply_parts(who, getattr(self, self._SPLITS[who][1])(*args))
 
     def iterate(self, n, randv=None, seeds=None):
         """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the
@@ -501,8 +511,7 @@ class BatchSolver:
         if randv is None:
             if seeds is None:
                 raise MMWError("iterate: give sketches or one seed per instance")
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
-            check(lib().mmw_batch_iterate(self._h, n, None, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+            check(lib().mmw_batch_iterate(self._h, n, None, _pu(_u64(seeds, self.B))))
         else:
             if len(randv) != self.B:
                 raise MMWError("iterate: one block list per instance")
@@ -586,28 +595,40 @@ class BatchSolver:
             return [1] * self.B
         return [max(1, min(int(round(wi * cus / tot)), BATCH_MAX_PARTS, -(-s["D"] // 8))) for wi, s in zip(w, self.sizes)]
 
-    def _apply_split(self, parts):
+    # setter -> (C entry, suggest function, attribute holding the accepted parts)
+    _SPLITS = {"set_split": ("mmw_batch_set_split", "suggest_split", "split_parts"),
+               "set_factor_split": ("mmw_batch_set_factor_split", "suggest_factor_split", "factor_split_parts")}
+
+    def _apply_parts(self, who, parts):
+        entry, _, attr = self._SPLITS[who]
         p = _i32(np.broadcast_to(np.asarray(parts, dtype=np.int64), (self.B,)))
-        check(lib().mmw_batch_set_split(self._h, _pi(p)))
-        self.split_parts = [int(x) for x in p] if np.any(p > 1) else None
+        check(getattr(lib(), entry)(self._h, _pi(p)))
+        setattr(self, attr, [int(x) for x in p] if np.any(p > 1) else None)
+
+    def _set_parts(self, who, parts, *suggest_args):
+        """The protocol of both setters: an int for all, one per instance, "auto" (the suggest function, taken again after every
+        `set_slots`), or None for the unsplit path."""
+        entry, suggest, attr = self._SPLITS[who]
+        if parts is None:
+            check(getattr(lib(), entry)(self._h, None))
+            setattr(self, attr, None)
+            self._auto.pop(who, None)
+        elif isinstance(parts, str):
+            if parts != "auto":
+                raise MMWError("%s: parts must be an int, one int per instance, \"auto\" or None" % who)
+            self._apply_parts(who, getattr(self, suggest)(*suggest_args))
+            self._auto[who] = suggest_args
+        else:
+            if np.ndim(parts) and len(parts) != self.B:
+                raise MMWError("%s: one part count per instance" % who)
+            self._apply_parts(who, parts)
+            self._auto.pop(who, None)
 
     def set_split(self, parts, cus=256):
         """Workgroups per instance for the iterations that follow: an int for all, one per instance, "auto" (`suggest_split(cus)`,
         taken again after every `set_slots`), or None / all ones for the single-launch kernel.  Every field stays bitwise what the
         single launch gives; an instance gains when it is the straggler of its batch."""
-        if parts is None:
-            check(lib().mmw_batch_set_split(self._h, None))
-            self._auto_split = self.split_parts = None
-        elif isinstance(parts, str):
-            if parts != "auto":
-                raise MMWError("set_split: parts must be an int, one int per instance, \"auto\" or None")
-            self._apply_split(self.suggest_split(cus))
-            self._auto_split = int(cus)
-        else:
-            if np.ndim(parts) and len(parts) != self.B:
-                raise MMWError("set_split: one part count per instance")
-            self._apply_split(parts)
-            self._auto_split = None
+        self._set_parts("set_split", parts, int(cus))
 
     # ---- several workgroups per instance for the factor (csrc/kernels_batch_factor_split.h)
     @staticmethod
@@ -624,28 +645,11 @@ class BatchSolver:
         workgroup's eight waves holds at most one two-pair step per round.  Instances that sit out get 1."""
         return [max(1, min(-(-((s["K"] + (s["K"] & 1)) // 2) // 16), BATCH_MAX_PARTS)) if a else 1 for s, a in zip(self.sizes, self.active)]
 
-    def _apply_factor_split(self, parts):
-        p = _i32(np.broadcast_to(np.asarray(parts, dtype=np.int64), (self.B,)))
-        check(lib().mmw_batch_set_factor_split(self._h, _pi(p)))
-        self.factor_split_parts = [int(x) for x in p] if np.any(p > 1) else None
-
     def set_factor_split(self, parts):
         """Workgroups per instance and tournament round for the `factor` calls that follow: an int for all, one per instance, "auto"
         (`suggest_factor_split()`, taken again after every `set_slots`), or None / all ones for the one launch of k_batch_factor.  The
         factor, its record and every rounding stay bitwise what the single launch gives."""
-        if parts is None:
-            check(lib().mmw_batch_set_factor_split(self._h, None))
-            self._auto_factor_split, self.factor_split_parts = False, None
-        elif isinstance(parts, str):
-            if parts != "auto":
-                raise MMWError("set_factor_split: parts must be an int, one int per instance, \"auto\" or None")
-            self._apply_factor_split(self.suggest_factor_split())
-            self._auto_factor_split = True
-        else:
-            if np.ndim(parts) and len(parts) != self.B:
-                raise MMWError("set_factor_split: one part count per instance")
-            self._apply_factor_split(parts)
-            self._auto_factor_split = False
+        self._set_parts("set_factor_split", parts)
 
     def factor_call(self):
         """The last `factor` of this batch (MMW_F_FACTOR_CALL): {"path": 0 one launch / 1 one launch per round, "launches", "sweeps"
@@ -688,7 +692,7 @@ class BatchSolver:
                     raise MMWError("factor: xavg of instance %d must hold nnzL = %d values" % (i, self.sizes[i]["nnzL"]))
                 keep.append(a)
                 xp[i] = _pd(a)
-        check(lib().mmw_batch_factor(self._h, None if t is None else _pi(t), None if r is None else _pi(r), xp))
+        check(lib().mmw_batch_factor(self._h, _opt_pi(t), _opt_pi(r), xp))
 
     def factor_info(self, inst):
         """{"sweeps", "max_cos" (largest |cos| of a row pair as met in the last sweep), "rank", "sigma_rank", "sigma_next"} of the last factor."""
@@ -707,12 +711,11 @@ class BatchSolver:
         rem int32 (B, nattempt) with -1 = not run, used int32 (B,) attempts run.  env: see `round_env`."""
         t, who = self._take(take)
         nattempt = int(nattempt)
-        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
+        sd = _u64(seeds, self.B)
         zflat = np.empty(max(1, nattempt * sum(self.sizes[i]["K"] for i in who)), dtype=np.int32)
         rem = np.empty((self.B, max(1, nattempt)), dtype=np.int32)
         used = np.empty(self.B, dtype=np.int32)
-        args = (None if t is None else _pi(t), nattempt, 1 if stop_at_first else 0, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _pi(zflat), _pi(rem),
-                _pi(used))
+        args = (_opt_pi(t), nattempt, 1 if stop_at_first else 0, _pu(sd), _pi(zflat), _pi(rem), _pi(used))
         check(lib().mmw_batch_round(self._h, *args) if env is None else lib().mmw_batch_round_env(self._h, env._h, *args))
         z, o = [None] * self.B, 0
         for i in who:
@@ -726,8 +729,7 @@ class BatchSolver:
         row-normalised K x D block of normals `sketch(i, seeds[i], 0)`, rank D; `round` / `round_env` / `read_factor` then work on it.
         All its rows have norm 1, so the rounding visits the users of such a block in index order (include/mmw_hip.h)."""
         t, _ = self._take(take)
-        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
-        check(lib().mmw_batch_factor_random(self._h, None if t is None else _pi(t), sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        check(lib().mmw_batch_factor_random(self._h, _opt_pi(t), _pu(_u64(seeds, self.B))))
 
     def gm(self, kind, Zs, nattempt=1, take=None, keys=False):
         """gm.MAX_GAIN.run (kind 0) / gm.MAX_ASSO.run (kind 1) in the stable order for every taking instance's own state, one launch

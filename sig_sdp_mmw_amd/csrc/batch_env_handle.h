@@ -21,7 +21,7 @@ struct mmw_batch_env {
     std::vector<int> K;
     std::vector<BatchEnvDesc> desc;
     std::vector<int> tot;  // [B][BENV_TOTALS] of the last move
-    std::vector<mmw_batch::RoundLists> rlists;
+    std::vector<RoundLists> rlists;
     DevBuf<BatchEnvDesc> d_desc;
     DevBuf<double> fa, zbuf, obuf;
     DevBuf<int> ia, d_tot;
@@ -31,7 +31,6 @@ struct mmw_batch_env {
         (void)hipSetDevice(device);
         (void)hipStreamDestroy(st);
     }
-    static int64_t a32(int64_t x) { return (x + 31) & ~(int64_t)31; }  // 256-byte aligned arrays, as the batch's arenas
     int init(int dev, int32_t B_, const int32_t* K_, const int32_t* A_, const double* const* ap_xy, double fre_Hz, double txp_offset,
              double min_s_n_ratio, double min_sinr_, double noise_dbm) {
         device = dev; B = B_; min_sinr = min_sinr_;
@@ -101,7 +100,7 @@ struct mmw_batch_env {
         MMW_HIP(hipGetLastError());
         MMW_TRY(copy_d2h(tot.data(), d_tot.p, tot.size() * sizeof(int), st));
         int64_t of = f_front, oi = i_front;
-        rlists.assign(B, mmw_batch::RoundLists{});
+        rlists.assign(B, RoundLists{});
         for (int b = 0; b < B; ++b) {
             BatchEnvDesc& d = desc[b];
             const int64_t ns = tot[(size_t)b * BENV_TOTALS], no = tot[(size_t)b * BENV_TOTALS + 1], nq = tot[(size_t)b * BENV_TOTALS + 2];
@@ -178,17 +177,13 @@ struct mmw_batch_env {
         if (!moved) return fail(MMW_ERR_STATE, who + ": no positions yet (mmw_batch_env_move)");
         MMW_TRY(batch_gm_args(who, kind, nattempt));
         std::vector<int> tk;
-        for (int b = 0; b < B; ++b)
-            if (!take || take[b]) tk.push_back(b);
-        if (tk.empty()) return fail(MMW_ERR_ARG, who + ": no instance takes part");
+        MMW_TRY(batch_takers(who.c_str(), B, take, nullptr, tk));
         std::vector<GmDesc> gd;
         for (int b : tk) {
             const BatchEnvDesc& d = desc[b];
-            const mmw_batch::RoundLists& l = rlists[b];
             GmDesc g{};
             g.K = d.K; g.G = d.A; g.kind = kind; g.Zb = Z[b] <= 0 ? d.K : Z[b]; g.nattempt = nattempt;
-            g.s_soptr = l.soptr; g.s_soidx = l.soidx; g.s_qptr = l.qptr;
-            g.s_sodata = l.sodata; g.s_sohmax = l.sohmax; g.s_hmax = l.hmax;
+            set_lists(g, rlists[b]);
             g.g_grp = d.i_asso; g.g_qdata = d.f_qval;
             gd.push_back(g);
         }
@@ -200,10 +195,10 @@ struct mmw_batch_env {
 inline int batch_round_env(mmw_batch* bt, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
                            int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
     const char* who = "mmw_batch_round_env";
-    if (bt->host_only) return mmw_batch::host_only_batch();
-    if (e->device != bt->device) return fail(MMW_ERR_ARG, std::string(who) + ": the environment lives on another device");
-    if (e->B != bt->B) return fail(MMW_ERR_ARG, std::string(who) + ": the batch holds " + std::to_string(bt->B) + " instances, the environment " + std::to_string(e->B));
+    if (bt->core.host_only) return BatchCore::host_only_batch();
+    if (e->device != bt->core.device) return fail(MMW_ERR_ARG, std::string(who) + ": the environment lives on another device");
+    if (e->B != bt->core.B) return fail(MMW_ERR_ARG, std::string(who) + ": the batch holds " + std::to_string(bt->core.B) + " instances, the environment " + std::to_string(e->B));
     if (!e->moved) return fail(MMW_ERR_STATE, std::string(who) + ": no positions yet (mmw_batch_env_move)");
-    const mmw_batch::RoundSource src{who, e->ia.p, e->fa.p, e->rlists.data(), e->K.data()};
+    const BatchEpilogue::RoundSource src{who, e->ia.p, e->fa.p, e->rlists.data(), e->K.data()};
     return bt->round(take, nattempt, stop_at_first, seeds, z_out, rem_out, used_out, &src);
 }

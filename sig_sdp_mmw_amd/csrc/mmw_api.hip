@@ -1,5 +1,5 @@
 // C-ABI of the MI355X MMW hot path (include/mmw_hip.h), the library's one translation unit.  The handles: solver.h (mmw_solver, mmw_env),
-// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch), batch_env_handle.h (mmw_batch_env).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
+// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch: batch_core.h and the parts' headers), batch_env_handle.h (mmw_batch_env).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
 #include "batch_env_handle.h"
 #include "batch_handle.h"
 #include "gm_handle.h"
@@ -169,72 +169,17 @@ int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, c
         if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
         if (!(eta >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
         auto bt = std::make_unique<mmw_batch>();
-        bt->device = device;
-        bt->host_only = device == -1;
-        bt->B = B;
-        bt->rank_radio = rank_radio;
-        bt->eta.assign(B, eta);
-        bt->H.resize(B);
-        bt->gmx.resize(B);
-        bt->nit.assign(nit, nit + B);
-        bt->iter.assign(B, 0);
-        bt->active.assign(B, 1);
-        for (int b = 0; b < B; ++b) {
-            if (nit[b] < 1) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": nit must be >= 1");
-            if (!S_indptr[b] || !S_indices[b] || !S_data[b] || !Q_indptr[b] || !Q_indices[b] || !Q_data[b] || !h_max[b])
-                return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": null pointer");
-            if (K[b] > BATCH_MAX_K) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": K = " + std::to_string(K[b]) +
-                                                    " exceeds the batch limit " + std::to_string(BATCH_MAX_K) + " (run it on a handle)");
-            const std::string err = build_pattern(bt->H[b], K[b], Z[b], S_indptr[b], S_indices[b], S_data[b], Q_indptr[b], Q_indices[b],
-                                                  Q_data[b], h_max[b]);
-            if (!err.empty()) return fail(MMW_ERR_ARG, "mmw_batch_create: instance " + std::to_string(b) + ": " + err);
-            bt->gm_extra(b, Q_indptr[b], Q_data[b]);
-        }
-        if (!bt->host_only) {
-            MMW_TRY(check_device("mmw_batch_create", device, DEV_ID));
-            MMW_HIP(hipSetDevice(device));
-            MMW_HIP(hipStreamCreateWithFlags(&bt->st, hipStreamNonBlocking));
-        }
-        MMW_TRY(bt->layout());
-        if (!bt->host_only)
-            for (int b = 0; b < B; ++b) MMW_TRY(bt->reset_one(b));
+        MMW_TRY(bt->init(device, B, K, Z, rank_radio, eta, nit, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max));
         *out = bt.release();
         return MMW_OK;
     });
 }
 int mmw_batch_destroy(mmw_batch* b) { return guarded("mmw_batch", [&]() -> int { delete b; return MMW_OK; }); }
-int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]) {
-    return guarded("mmw_batch", [&]() -> int {
-        if (!b || !out) return fail(MMW_ERR_ARG, "null pointer");
-        MMW_TRY(b->check_inst(inst));
-        const HostPattern& P = b->H[inst];
-        const BatchDesc& d = b->desc[inst];
-        const int64_t v[10] = {P.K, P.Z, d.D, d.D, P.nnzL(), P.nnzST(), P.E_gain(), P.E_asso(), P.C(), b->iter[inst]};
-        for (int i = 0; i < 10; ++i) out[i] = v[i];
-        return MMW_OK;
-    });
-}
+int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]) { return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->sizes(inst, out); }); }
 int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit); }); }
 int mmw_batch_reset(mmw_batch* b, int32_t nit) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->reset(nit); }); }
-int mmw_batch_set_eta(mmw_batch* b, const double* eta) {
-    return guarded("mmw_batch", [&]() -> int {
-        if (!b || !eta) return fail(MMW_ERR_ARG, "null pointer");
-        for (int i = 0; i < b->B; ++i)
-            if (!(eta[i] >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
-        b->eta.assign(eta, eta + b->B);
-        return MMW_OK;
-    });
-}
-int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) {
-    return guarded("mmw_batch", [&]() -> int {
-        if (!b) return fail(MMW_ERR_ARG, "null batch handle");
-        if (max_order < 1 || max_order > MAX_ORDER) return fail(MMW_ERR_ARG, "max_order must be in [1, 16]");
-        if (!(tol > 0.0)) return fail(MMW_ERR_ARG, "tol must be positive");
-        b->max_order = max_order;
-        b->tol = tol;
-        return MMW_OK;
-    });
-}
+int mmw_batch_set_eta(mmw_batch* b, const double* eta) { return entry("mmw_batch", !b || !eta, "null pointer", [&] { return b->set_eta(eta); }); }
+int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_expm(max_order, tol); }); }
 int mmw_batch_set_gap(mmw_batch* b, int enabled, int32_t m_cap) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_gap(enabled, m_cap); }); }
 int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n) { return entry("mmw_batch", !b || (!out && n), "null pointer", [&] { return b->read_gap(inst, out, n); }); }
 int mmw_batch_set_split(mmw_batch* b, const int32_t* parts) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_split(parts); }); }
@@ -246,7 +191,7 @@ int mmw_batch_sketch(mmw_batch* b, int32_t inst, uint64_t seed, int32_t iteratio
 int mmw_batch_export(mmw_batch* b, int32_t inst, mmw_solver* h) {
     return guarded("mmw_batch", [&]() -> int {
         if (!b || !h) return fail(MMW_ERR_ARG, "null pointer");
-        MMW_TRY(b->check_inst(inst));
+        MMW_TRY(b->core.check_inst(inst));
         auto* s = dynamic_cast<Solver<double>*>(h);
         if (!s) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle is not an fp64 handle");
         return batch_export_into(b, inst, s);

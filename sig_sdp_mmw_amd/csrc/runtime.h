@@ -199,6 +199,8 @@ template <typename V> int export_vec(const std::vector<V>& v, V* out, int64_t ha
     return MMW_OK;
 }
 
+inline int64_t a32(int64_t x) { return (x + 31) & ~(int64_t)31; }  // the batch arenas' arrays start at multiples of 32 elements (fp64: 256 bytes)
+
 template <typename T> struct DevBuf {
     T* p = nullptr;
     size_t n = 0;    // elements in use

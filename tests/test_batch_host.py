@@ -71,7 +71,7 @@ BATCH_MAX_BYTES = 96 << 20  # kernels_batch.h
 
 
 def batch_instance_bytes(p, D):
-    """Arena bytes of one instance as mmw_batch::fp64_words / int_words count them (csrc/batch_handle.h), from the oracle's pattern."""
+    """Arena bytes of one instance as BatchCore::fp64_words / int_words count them (csrc/batch_core.h), from the oracle's pattern."""
     K, nnz, C, EA = p.K, p.nnzL, p.C, p.E_asso
     return (5 * nnz + 6 * K + 4 * C + 4 * K * D + 4 + 64) * 8 + (K + 1 + 3 * nnz + K + EA) * 4
 
