@@ -204,23 +204,65 @@ def canonical_csr(m):
     return _i32(m.indptr), _i32(m.indices), _f64(m.data)
 
 
-class Solver:
+def _state_arrays(state):
+    """(K, (S indptr, indices, data, Q indptr, indices, data, h_max)): a state's seven canonical arrays after its shape check."""
+    S, Q, h = state
+    K = int(S.shape[0])
+    if S.shape != (K, K) or Q.shape != (K, K) or len(h) != K:
+        raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
+    return K, canonical_csr(S) + canonical_csr(Q) + (_f64(h),)
+
+
+def _state_out(K, nnzS, nnzQ, fill):
+    """(S_gain csr, Q_asso csr, h_max) from the seven arrays `fill(sp, si, sx, qp, qi, qx, h)` writes (mmw_env_state / mmw_batch_env_state)."""
+    import scipy.sparse
+    sp = np.empty(K + 1, dtype=np.int32); si = np.empty(nnzS, dtype=np.int32); sx = np.empty(nnzS, dtype=np.float64)
+    qp = np.empty(K + 1, dtype=np.int32); qi = np.empty(nnzQ, dtype=np.int32); qx = np.empty(nnzQ, dtype=np.float64)
+    h = np.empty(K, dtype=np.float64)
+    fill(_pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(h))
+    return scipy.sparse.csr_matrix((sx, si, sp), shape=(K, K)), scipy.sparse.csr_matrix((qx, qi, qp), shape=(K, K)), h
+
+
+# mmw_read_f64 / mmw_read_i32: the size a field's length is (mmw_sizes' names), for the int fields (size, + offset)
+_SIZE_NAMES = ("K", "Z", "D", "Dpad", "nnzL", "nnzST", "E_gain", "E_asso", "C", "iter")
+_LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", F_XAVG: "nnzL", F_YAVG: "C",
+        F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST"}
+_ILEN = {I_L_INDPTR: ("K", 1), I_L_INDICES: ("nnzL", 0), I_ST_INDPTR: ("K", 1), I_ST_INDICES: ("nnzST", 0), I_GAIN_X: ("E_gain", 0),
+         I_GAIN_Y: ("E_gain", 0), I_ASSO_X: ("E_asso", 0), I_ASSO_Y: ("E_asso", 0), I_DIAG_POS: ("K", 0), I_ASSO_POS: ("E_asso", 0)}
+
+
+class _Handle:
+    """What the owning wrappers share: `_h`, the handle; `_destroy`, the name of the C entry that frees it."""
+    _destroy = None
+
+    def _closing(self):
+        """Called by `close` while the handle is still valid."""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            try:
+                self._closing()
+            finally:
+                getattr(lib(), self._destroy)(self._h)
+                self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Solver(_Handle):
     """Owning wrapper of one `mmw_solver*` handle."""
+    _destroy = "mmw_destroy"
 
     def __init__(self, Z, state, nit, eta, rank_radio=2, dtype=F64, device=0):
-        S, Q, h = state
-        self.K = int(S.shape[0])
-        if S.shape != (self.K, self.K) or Q.shape != (self.K, self.K) or len(h) != self.K:
-            raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
-        sp, si, sx = canonical_csr(S)
-        qp, qi, qx = canonical_csr(Q)
-        hm = _f64(h)
+        self.K, (sp, si, sx, qp, qi, qx, hm) = _state_arrays(state)
         self._h = C.c_void_p()
         check(lib().mmw_create(C.byref(self._h), int(device), int(dtype), self.K, int(Z), int(rank_radio), float(eta), int(nit),
                                _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(hm)))
-        sz = (C.c_int64 * 10)()
-        check(lib().mmw_sizes(self._h, sz))
-        (self.K, self.Z, self.D, self.Dpad, self.nnzL, self.nnzST, self.E_gain, self.E_asso, self.C, _) = [int(x) for x in sz]
+        self._load_sizes()
         self.dtype = dtype
         self._timing = False
         self._timed = 0
@@ -231,33 +273,26 @@ class Solver:
         self = cls.__new__(cls)
         self._h = C.c_void_p()
         check(lib().mmw_create_from_env(C.byref(self._h), env._h, int(dtype), int(Z), int(rank_radio), float(eta), int(nit)))
-        sz = (C.c_int64 * 10)()
-        check(lib().mmw_sizes(self._h, sz))
-        (self.K, self.Z, self.D, self.Dpad, self.nnzL, self.nnzST, self.E_gain, self.E_asso, self.C, _) = [int(x) for x in sz]
+        self._load_sizes()
         self.dtype = dtype
         self._timing = False
         self._timed = 0
         return self
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            try:
-                self._keep_resident_factor()
-            finally:
-                lib().mmw_destroy(self._h)
-                self._h = C.c_void_p()
+    def _sizes(self):
+        sz = (C.c_int64 * 10)()
+        check(lib().mmw_sizes(self._h, sz))
+        return [int(x) for x in sz]
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _load_sizes(self):
+        (self.K, self.Z, self.D, self.Dpad, self.nnzL, self.nnzST, self.E_gain, self.E_asso, self.C, _) = self._sizes()
+
+    def _closing(self):
+        self._keep_resident_factor()
 
     @property
     def iterations_done(self):
-        sz = (C.c_int64 * 10)()
-        check(lib().mmw_sizes(self._h, sz))
-        return int(sz[9])
+        return self._sizes()[9]
 
     def set_expm(self, method=EXPM_LANCZOS, max_order=12, tol=1e-9):
         check(lib().mmw_set_expm(self._h, int(method), int(max_order), float(tol)))
@@ -305,9 +340,7 @@ class Solver:
         """Rebind to another slot count on the same state (keeps pattern, blocking and device copies).
         warm=True continues from the previous probe's iterate (mmw_set_slots_warm)."""
         check((lib().mmw_set_slots_warm if warm else lib().mmw_set_slots)(self._h, int(Z), int(nit)))
-        sz = (C.c_int64 * 10)()
-        check(lib().mmw_sizes(self._h, sz))
-        (self.K, self.Z, self.D, self.Dpad, self.nnzL, self.nnzST, self.E_gain, self.E_asso, self.C, _) = [int(x) for x in sz]
+        self._load_sizes()
         self._timed = 0
 
     def iterate(self, n, randv=None, seed=0):
@@ -330,8 +363,7 @@ class Solver:
         check(lib().mmw_sketch(self._h, C.c_uint64(int(seed)), int(iteration), _pd(out), int(out.size)))
         return out
 
-    _LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", F_XAVG: "nnzL", F_YAVG: "C",
-            F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST"}
+    _LEN = _LEN
 
     def read(self, which, n=None):
         if n is None:
@@ -358,13 +390,11 @@ class Solver:
     def _timed_iters(self):
         return self._timed
 
-    _ILEN = {I_L_INDPTR: lambda s: s.K + 1, I_L_INDICES: lambda s: s.nnzL, I_ST_INDPTR: lambda s: s.K + 1,
-             I_ST_INDICES: lambda s: s.nnzST, I_GAIN_X: lambda s: s.E_gain, I_GAIN_Y: lambda s: s.E_gain,
-             I_ASSO_X: lambda s: s.E_asso, I_ASSO_Y: lambda s: s.E_asso, I_DIAG_POS: lambda s: s.K,
-             I_ASSO_POS: lambda s: s.E_asso}
+    _ILEN = _ILEN
 
     def read_i32(self, which):
-        n = self._ILEN[which](self)
+        name, off = self._ILEN[which]
+        n = getattr(self, name) + off
         out = np.empty(int(n), dtype=np.int32)
         check(lib().mmw_read_i32(self._h, int(which), _pi(out), int(n)))
         return out
@@ -414,10 +444,11 @@ class Solver:
         return z, rem
 
 
-class BatchSolver:
+class BatchSolver(_Handle):
     """Owning wrapper of one `mmw_batch*`: B small fp64 instances, one workgroup each, `n` iterations per launch
     (csrc/kernels_batch.h).  Mirrors `Solver` with an instance index on every per-instance call.  `nit` is one count for all
     instances or one per instance; Zs one slot count per instance."""
+    _destroy = "mmw_batch_destroy"
 
     def __init__(self, Zs, states, nit, eta, rank_radio=2, device=0):
         self.B = B = len(states)
@@ -427,14 +458,10 @@ class BatchSolver:
         self._keep = []
         arrays = {k: [] for k in ("sp", "si", "sx", "qp", "qi", "qx", "h")}
         Ks = []
-        for S, Q, h in states:
-            K = int(S.shape[0])
-            if S.shape != (K, K) or Q.shape != (K, K) or len(h) != K:
-                raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
+        for state in states:
+            K, seven = _state_arrays(state)
             Ks.append(K)
-            sp, si, sx = canonical_csr(S)
-            qp, qi, qx = canonical_csr(Q)
-            for k, a in zip(("sp", "si", "sx", "qp", "qi", "qx", "h"), (sp, si, sx, qp, qi, qx, _f64(h))):
+            for k, a in zip(("sp", "si", "sx", "qp", "qi", "qx", "h"), seven):
                 arrays[k].append(a)
         self._keep.append(arrays)
 
@@ -461,18 +488,7 @@ class BatchSolver:
         for b in range(self.B):
             sz = (C.c_int64 * 10)()
             check(lib().mmw_batch_sizes(self._h, b, sz))
-            self.sizes.append(dict(zip(("K", "Z", "D", "Dpad", "nnzL", "nnzST", "E_gain", "E_asso", "C", "iter"), [int(x) for x in sz])))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mmw_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self.sizes.append(dict(zip(_SIZE_NAMES, [int(x) for x in sz])))
 
     def iterations_done(self, inst):
         sz = (C.c_int64 * 10)()
@@ -534,8 +550,7 @@ class BatchSolver:
         check(lib().mmw_batch_sketch(self._h, int(inst), C.c_uint64(int(seed)), int(iteration), _pd(out), int(out.size)))
         return out
 
-    _LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", F_XAVG: "nnzL", F_YAVG: "C",
-            F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST"}
+    _LEN = _LEN
 
     def read(self, inst, which, n=None):
         sz = self.sizes[inst]
@@ -552,13 +567,11 @@ class BatchSolver:
             out = out.reshape(sz["K"], sz["D"])
         return out
 
-    _ILEN = {I_L_INDPTR: lambda s: s["K"] + 1, I_L_INDICES: lambda s: s["nnzL"], I_ST_INDPTR: lambda s: s["K"] + 1,
-             I_ST_INDICES: lambda s: s["nnzST"], I_GAIN_X: lambda s: s["E_gain"], I_GAIN_Y: lambda s: s["E_gain"],
-             I_ASSO_X: lambda s: s["E_asso"], I_ASSO_Y: lambda s: s["E_asso"], I_DIAG_POS: lambda s: s["K"],
-             I_ASSO_POS: lambda s: s["E_asso"]}
+    _ILEN = _ILEN
 
     def read_i32(self, inst, which):
-        n = self._ILEN[which](self.sizes[inst])
+        name, off = self._ILEN[which]
+        n = self.sizes[inst][name] + off
         out = np.empty(int(n), dtype=np.int32)
         check(lib().mmw_batch_read_i32(self._h, int(inst), int(which), _pi(out), int(n)))
         return out
@@ -790,8 +803,9 @@ class DeviceFactor(np.lib.mixins.NDArrayOperatorsMixin):
         return getattr(np.asarray(self), name)
 
 
-class DeviceEnv:
+class DeviceEnv(_Handle):
     """Owning wrapper of one `mmw_env*`: the reference's problem generator and scorer on the device (env.py:136-233)."""
+    _destroy = "mmw_env_destroy"
 
     def __init__(self, sta_locs, ap_locs, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1, min_sinr=1.0, noise_floor_dbm=-94.0, device=0):
         sta = _f64(sta_locs)
@@ -808,14 +822,7 @@ class DeviceEnv:
 
     def state(self):
         """(S_gain csr, Q_asso csr, h_max) as env.generate_S_Q_hmax returns them."""
-        import scipy.sparse
-        sp = np.empty(self.K + 1, dtype=np.int32); si = np.empty(self.nnzS, dtype=np.int32); sx = np.empty(self.nnzS, dtype=np.float64)
-        qp = np.empty(self.K + 1, dtype=np.int32); qi = np.empty(self.nnzQ, dtype=np.int32); qx = np.empty(self.nnzQ, dtype=np.float64)
-        h = np.empty(self.K, dtype=np.float64)
-        check(lib().mmw_env_state(self._h, _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(h)))
-        S = scipy.sparse.csr_matrix((sx, si, sp), shape=(self.K, self.K))
-        Q = scipy.sparse.csr_matrix((qx, qi, qp), shape=(self.K, self.K))
-        return S, Q, h
+        return _state_out(self.K, self.nnzS, self.nnzQ, lambda *a: check(lib().mmw_env_state(self._h, *a)))
 
     def bounds(self):
         """(lower, upper) slot-count bounds of binary_search_relaxation.py:13-29 for this state, from the device's count pass."""
@@ -839,22 +846,12 @@ class DeviceEnv:
                                      _pd(bl) if bler else None))
         return sinr, bl
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mmw_env_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchEnv:
+class BatchEnv(_Handle):
     """Owning wrapper of one `mmw_batch_env*`: the generator and the scorer (env.py:136-233) for B small instances, one workgroup
     each (csrc/kernels_batch_env.h).  ap_locs: one (A, 2) array per instance; Ks: stations per instance.  `move` takes the
     stations' positions, one (K, 2) array per instance, and regenerates every state; until the first move nothing else answers."""
+    _destroy = "mmw_batch_env_destroy"
 
     def __init__(self, ap_locs, Ks, fre_Hz=4e9, txp_offset=2.0, min_s_n_ratio=0.1, min_sinr=1.0, noise_floor_dbm=-94.0, device=0):
         aps = [_f64(a) for a in ap_locs]
@@ -883,14 +880,8 @@ class BatchEnv:
 
     def state(self, inst):
         """(S_gain csr, Q_asso csr, h_max) of instance `inst` at its last positions, as env.generate_S_Q_hmax returns them."""
-        import scipy.sparse
         sz = self.sizes(inst)
-        K, ns, nq = sz["K"], sz["nnzS"], sz["nnzQ"]
-        sp = np.empty(K + 1, dtype=np.int32); si = np.empty(ns, dtype=np.int32); sx = np.empty(ns, dtype=np.float64)
-        qp = np.empty(K + 1, dtype=np.int32); qi = np.empty(nq, dtype=np.int32); qx = np.empty(nq, dtype=np.float64)
-        h = np.empty(K, dtype=np.float64)
-        check(lib().mmw_batch_env_state(self._h, int(inst), _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(h)))
-        return scipy.sparse.csr_matrix((sx, si, sp), shape=(K, K)), scipy.sparse.csr_matrix((qx, qi, qp), shape=(K, K)), h
+        return _state_out(sz["K"], sz["nnzS"], sz["nnzQ"], lambda *a: check(lib().mmw_batch_env_state(self._h, int(inst), *a)))
 
     def evaluate(self, zs, Zs, packet_bit=800, bandwidth=5e6, slot_time=1.25e-4, bler=True):
         """env.evaluate_sinr / evaluate_bler of one colouring per instance in one launch: zs[i] (K_i,) slot numbers, Zs[i] slots.
@@ -911,17 +902,6 @@ class BatchEnv:
             raise MMWError("take: one flag per instance")
         who = [i for i in range(self.B) if t is None or t[i]]
         return _gm_call(lib().mmw_batch_env_gm, self._h, self.B, self.Ks, who, kind, Zs, nattempt, t, keys)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mmw_batch_env_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceState:
@@ -947,17 +927,12 @@ class DeviceState:
         return 3
 
 
-class GreedyHandle:
+class GreedyHandle(_Handle):
     """Owning wrapper of one `mmw_gm*`: the state of the greedy baselines of gm.py (mmw_gm_create), device = -1 for host C++."""
+    _destroy = "mmw_gm_destroy"
 
     def __init__(self, state, device=0):
-        S, Q, h = state
-        self.K = int(S.shape[0])
-        if S.shape != (self.K, self.K) or Q.shape != (self.K, self.K) or len(h) != self.K:
-            raise MMWError("state must be (S_gain KxK, Q_asso KxK, h_max[K])")
-        sp, si, sx = canonical_csr(S)
-        qp, qi, qx = canonical_csr(Q)
-        hm = _f64(h)
+        self.K, (sp, si, sx, qp, qi, qx, hm) = _state_arrays(state)
         self.device = int(device)
         self._h = C.c_void_p()
         check(lib().mmw_gm_create(C.byref(self._h), self.device, self.K, _pi(sp), _pi(si), _pd(sx), _pi(qp), _pi(qi), _pd(qx), _pd(hm)))
@@ -993,17 +968,6 @@ class GreedyHandle:
         rem = C.c_int32(0)
         check(lib().mmw_gm_assign(self._h, int(p.shape[1]), _pi(o), _pi(p), _pi(z), C.byref(rem)))
         return z, rem.value
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mmw_gm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def sym_eig(G, rel_tol=1e-13, max_sweeps=30, device=0):

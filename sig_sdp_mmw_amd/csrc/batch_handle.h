@@ -215,39 +215,39 @@ struct mmw_batch {
 inline int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {
     const BatchDesc& d = bt->core.desc[b];
     const HostPattern& P = bt->core.H[b];
-    if (s->host_only || bt->core.host_only) return fail(MMW_ERR_STATE, "mmw_batch_export: host-only batch or handle");
-    if (s->device != bt->core.device) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle lives on another device");
-    if (s->K != d.K || s->Z != d.Z || s->D != d.D || s->H.nnzL() != (int64_t)d.nnzL || s->H.C() != (int64_t)d.C)
+    if (s->core.host_only || bt->core.host_only) return fail(MMW_ERR_STATE, "mmw_batch_export: host-only batch or handle");
+    if (s->core.device != bt->core.device) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle lives on another device");
+    if (s->core.K != d.K || s->core.Z != d.Z || s->core.D != d.D || s->core.H.nnzL() != (int64_t)d.nnzL || s->core.H.C() != (int64_t)d.C)
         return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's K / Z / nnzL do not match the instance's");
-    if (s->H.l_indices != P.l_indices || s->H.l_indptr != P.l_indptr) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's pattern is not the instance's");
-    MMW_HIP(hipSetDevice(s->device));
+    if (s->core.H.l_indices != P.l_indices || s->core.H.l_indptr != P.l_indptr) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's pattern is not the instance's");
+    MMW_HIP(hipSetDevice(s->core.device));
     MMW_TRY(s->settle());
     MMW_HIP(hipStreamSynchronize(bt->core.st));
-    MMW_HIP(hipStreamSynchronize(s->st));
+    MMW_HIP(hipStreamSynchronize(s->core.st));
     // the state a reset leaves (plans, lagged history, chains, timers), then the iterate on top
     MMW_TRY(s->reset(std::max(1, bt->core.nit[b])));
     const size_t nnz = (size_t)d.nnzL, C = (size_t)d.C;
     const double* f = bt->core.fa.p;
-    const struct { double* dst; int64_t off; size_t n; } parts[7] = {{s->lval.p, d.o_lval, nnz}, {s->xval.p, d.o_xval, nnz}, {s->xavg.p, d.o_xavg, nnz}, {s->Y.p, d.o_Y, C},
-                                                                     {s->yavg.p, d.o_yavg, C}, {s->e_accu.p, d.o_eaccu, C}, {s->e_this.p, d.o_ethis, C}};
-    for (const auto& p : parts) MMW_HIP(hipMemcpyAsync(p.dst, f + p.off, p.n * sizeof(double), hipMemcpyDeviceToDevice, s->st));
+    const struct { double* dst; int64_t off; size_t n; } parts[7] = {{s->core.lval.p, d.o_lval, nnz}, {s->core.xval.p, d.o_xval, nnz}, {s->core.xavg.p, d.o_xavg, nnz}, {s->core.Y.p, d.o_Y, C},
+                                                                     {s->core.yavg.p, d.o_yavg, C}, {s->core.e_accu.p, d.o_eaccu, C}, {s->core.e_this.p, d.o_ethis, C}};
+    for (const auto& p : parts) MMW_HIP(hipMemcpyAsync(p.dst, f + p.off, p.n * sizeof(double), hipMemcpyDeviceToDevice, s->core.st));
     // The batch adds X_i / Y_i to the running sums when iteration i starts; a handle adds them as soon as they are made while
     // iterations remain (mmw_gap reads iter + 1 terms then).  Before the last iteration the handle's sums hold the current X / Y too.
     if (bt->core.iter[b] < bt->core.nit[b]) {
         const unsigned gx = (unsigned)std::min<size_t>((nnz + BLOCK - 1) / BLOCK, 4096), gy = (unsigned)std::min<size_t>((C + BLOCK - 1) / BLOCK, 4096);
-        hipLaunchKernelGGL((k_accumulate<double>), dim3(gx), dim3(BLOCK), 0, s->st, nnz, s->xval.p, s->xavg.p);
-        hipLaunchKernelGGL((k_accumulate<double>), dim3(gy), dim3(BLOCK), 0, s->st, C, s->Y.p, s->yavg.p);
+        hipLaunchKernelGGL((k_accumulate<double>), dim3(gx), dim3(BLOCK), 0, s->core.st, nnz, s->core.xval.p, s->core.xavg.p);
+        hipLaunchKernelGGL((k_accumulate<double>), dim3(gy), dim3(BLOCK), 0, s->core.st, C, s->core.Y.p, s->core.yavg.p);
         MMW_HIP(hipGetLastError());
     }
     // derived copies: L in the LDS-staged SpMM's traversal order (when the handle's blocking is attached; a later attach gathers it
     // from lval itself)
-    if (s->bt.lval_blk.p && s->bt.HB.nent > 0) {
-        hipLaunchKernelGGL((k_gather_blocked<double>), dim3(grid_elems((size_t)s->bt.HB.nent)), dim3(BLOCK), 0, s->st, (size_t)s->bt.HB.nent,
-                           s->bt.b_bepos.p, s->lval.p, s->bt.lval_blk.p);
+    if (s->core.bt.lval_blk.p && s->core.bt.HB.nent > 0) {
+        hipLaunchKernelGGL((k_gather_blocked<double>), dim3(grid_elems((size_t)s->core.bt.HB.nent)), dim3(BLOCK), 0, s->core.st, (size_t)s->core.bt.HB.nent,
+                           s->core.bt.b_bepos.p, s->core.lval.p, s->core.bt.lval_blk.p);
         MMW_HIP(hipGetLastError());
     }
-    s->lblk_stale = false;
-    s->iter = bt->core.iter[b];
-    MMW_HIP(hipStreamSynchronize(s->st));
+    s->core.lblk_stale = false;
+    s->core.iter = bt->core.iter[b];
+    MMW_HIP(hipStreamSynchronize(s->core.st));
     return MMW_OK;
 }

@@ -1,4 +1,4 @@
-// The device tables of a handle's two locality blockings (blocking.h): host build threads, upload, kernel argument structs (the iterate's buffers stay in solver.h).
+// The device tables of a handle's two locality blockings (blocking.h): host build threads, upload, kernel argument structs (the iterate's buffers are the core's, solver_core.h).
 #pragma once
 #include <queue>
 #include <thread>

@@ -22,7 +22,7 @@ int mmw_create(mmw_solver** out, int device, int dtype, int32_t K, int32_t Z, in
         const bool host_only = device == -1;
         if (!host_only) MMW_TRY(check_device("mmw_create", device, DEV_ID_VISIBLE));
         return create_solver(out, dtype, host_only, [&](auto& s) {
-            return s.init(device, K, Z, rank_radio, eta, nit, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
+            return std::decay_t<decltype(s)>::Create::init(s, device, K, Z, rank_radio, eta, nit, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
         });
     });
 }
@@ -32,7 +32,7 @@ int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, in
         *out = nullptr;
         if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
         if (nit < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
-        return create_solver(out, dtype, false, [&](auto& s) { return s.init_env(env->e.device, env->e, Z, rank_radio, eta, nit); });
+        return create_solver(out, dtype, false, [&](auto& s) { return std::decay_t<decltype(s)>::Create::init_env(s, env->e.device, env->e, Z, rank_radio, eta, nit); });
     });
 }
 int mmw_env_bounds(mmw_env* e, int32_t out[2]) { return entry("mmw_env_bounds", !e || !out, "null pointer", [&] { return e->e.bounds(out); }); }

@@ -30,7 +30,7 @@ struct Switches {
     bool factor_no_ns = false;     // MMW_FACTOR_NO_NS: the second orthonormalisation pass is a Cholesky-QR too
     bool factor_no_mfma = false;   // MMW_FACTOR_NO_MFMA: the Chebyshev filter stays on the fp32 SpMM
     bool factor_full_rr = false;   // MMW_FACTOR_FULL_RR: a Rayleigh-Ritz step after every filter pass
-    // ---- the loop (solver.h, chunk_policy.h)
+    // ---- the loop (solver.h, solver_loop.h, chunk_policy.h)
     bool no_fused_dual = false;    // MMW_NO_FUSED_DUAL: the softmax in its two passes in every iteration
     double dual_gap = NAN;         // MMW_DUAL_GAP: how far e_accu's maximum may run ahead of the fused pass's shift (NaN: 60 / 600 by dtype)
     bool no_lagged_plan = false;   // MMW_NO_LAGGED_PLAN: an exact plan in front of every exponential
