@@ -71,6 +71,11 @@ enum mmw_field {
     MMW_F_FACTOR_CALL = 21, /* [4]    the last mmw_batch_factor of a batch, kept on the host, the same for every instance: {path: 0 = one launch
                              (k_batch_factor), 1 = one launch per round (mmw_batch_set_factor_split); kernel launches enqueued; sweeps
                              the host loop ran (path 0: 0); workgroups of the largest launch}; zeros before the first call; batches only */
+    MMW_F_SPLIT_CALL = 22,  /* [4]    the last mmw_batch_iterate of a batch, kept on the host, the same for every instance: {path: 0 = one launch
+                             (k_mmw_batch), 1 = three launches per iteration (mmw_batch_set_split), 2 = one launch per Taylor term
+                             (mmw_batch_set_row_split); kernel launches enqueued; of which idle: every workgroup past its instance's
+                             schedule or with all its columns stopped (path 2 only); workgroups of the largest launch}; zeros before
+                             the first call; batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -356,6 +361,26 @@ int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n);
  */
 #define MMW_BATCH_MAX_PARTS 32
 int mmw_batch_set_split(mmw_batch* b, const int32_t* parts);
+/*
+ * The rows of a Taylor term over workgroups (csrc/kernels_batch_rows.h).  mmw_batch_set_split cuts exp(L/2)R by sketch column only, at
+ * most ceil(D / 8) workgroups per instance; mmw_batch_set_row_split gives instance b rows[b] row parts, 1 ... MMW_BATCH_MAX_ROW_PARTS (a
+ * value outside is refused by instance with MMW_ERR_ARG and leaves the setting as it was), multiplied with its column slices.  While
+ * any instance that runs has rows > 1, mmw_batch_iterate enqueues every iteration for all instances together as: the head of the
+ * column split; a plan launch whose records (mu, rho, substeps, order per instance) the host reads -- one synchronisation per
+ * iteration, after which the host knows the length nsub (1 + order) of every schedule; per launch of the longest schedule one
+ * workgroup per (instance, column slice, row part), which starts a substep or adds one Taylor term on its own rows and columns and
+ * returns at once when it is past its instance's schedule or all its columns have stopped; X on the pattern with slices x rows entry
+ * ranges.  Kernel boundaries are the only synchronisation.  The row ranges are contiguous, cover [0, K) and are balanced by stored
+ * entries of L: boundary p is the first row at which the prefix of L's indptr reaches p nnzL / rows, so a range may be empty
+ * (mmw_batch_row_ranges writes the rows + 1 boundaries of instance `inst`; it also answers on a host-only batch).  A row's sum runs
+ * over its entries in CSR order whichever workgroup owns it and the stop rule is built from maxima only: all fields, the gap log and
+ * EXPM_INFO are bitwise what the single launch gives.  NULL or all ones selects what runs without it (the default).  The setting
+ * survives mmw_batch_reset and mmw_batch_set_slots.  Tables, records and slabs live in buffers of their own: the arenas do not move.
+ * MMW_F_SPLIT_CALL says which path the last mmw_batch_iterate took.  MMW_ERR_STATE on a host-only batch.
+ */
+#define MMW_BATCH_MAX_ROW_PARTS 64
+int mmw_batch_set_row_split(mmw_batch* b, const int32_t* rows);
+int mmw_batch_row_ranges(mmw_batch* b, int32_t inst, int32_t rows, int32_t* out);
 /* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
  * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);

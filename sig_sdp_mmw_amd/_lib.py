@@ -20,7 +20,9 @@ F_Y, F_E_ACCU, F_E_THIS, F_LVAL, F_XVAL, F_XAVG, F_YAVG, F_XHALF, F_SKETCH = ran
 F_S_SUM, F_NORM_H, F_ST_DATA, F_PHASE_US, F_EXPM_INFO, F_FACTOR, F_KERNEL_US, F_BLOCKING, F_SPMM_KIND, F_E_MAX, F_DUAL_INFO = range(9, 20)
 F_FACTOR_INFO = 20
 F_FACTOR_CALL = 21
+F_SPLIT_CALL = 22
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
+BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
@@ -34,7 +36,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
-           "mmw_batch_factor_random", "mmw_batch_set_split", "mmw_batch_set_factor_split"]
+           "mmw_batch_factor_random", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
+           "mmw_batch_row_ranges"]
 
 
 class MMWError(RuntimeError):
@@ -115,6 +118,8 @@ def lib():
     L.mmw_batch_read_gap.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_int64]
     L.mmw_batch_set_split.argtypes = [C.c_void_p, p_i32]
     L.mmw_batch_set_factor_split.argtypes = [C.c_void_p, p_i32]
+    L.mmw_batch_set_row_split.argtypes = [C.c_void_p, p_i32]
+    L.mmw_batch_row_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_i32]
     L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
     L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
@@ -480,6 +485,7 @@ class BatchSolver(_Handle):
         self.active = [True] * B
         self._auto = {}  # per setter in _SPLITS: the arguments of its suggest function while "auto" holds
         self.split_parts = None  # workgroups per instance as last accepted by set_split (None: the single-launch kernel)
+        self.row_split_parts = None  # row parts per instance as last accepted by set_row_split (None: no row split)
         self.factor_split_parts = None  # the same for the factor, as last accepted by set_factor_split (None: k_batch_factor's one launch)
         self._load_sizes()
 
@@ -517,8 +523,9 @@ class BatchSolver(_Handle):
         self.nits = [int(nit)] * self.B
         self.active = [int(x) > 0 for x in z]
         self._load_sizes()
-        for who, args in self._auto.items():  # "auto" follows the slot counts
-            self._apply_parts(who, getattr(self, self._SPLITS[who][1])(*args))
+        for who in self._SPLITS:  # "auto" follows the slot counts (in _SPLITS' order: the row parts follow the column slices)
+            if who in self._auto:
+                self._apply_parts(who, getattr(self, self._SPLITS[who][1])(*self._auto[who]))
 
     def iterate(self, n, randv=None, seeds=None):
         """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the
@@ -610,6 +617,7 @@ class BatchSolver(_Handle):
 
     # setter -> (C entry, suggest function, attribute holding the accepted parts)
     _SPLITS = {"set_split": ("mmw_batch_set_split", "suggest_split", "split_parts"),
+               "set_row_split": ("mmw_batch_set_row_split", "suggest_row_split", "row_split_parts"),
                "set_factor_split": ("mmw_batch_set_factor_split", "suggest_factor_split", "factor_split_parts")}
 
     def _apply_parts(self, who, parts):
@@ -642,6 +650,58 @@ class BatchSolver(_Handle):
         taken again after every `set_slots`), or None / all ones for the single-launch kernel.  Every field stays bitwise what the
         single launch gives; an instance gains when it is the straggler of its batch."""
         self._set_parts("set_split", parts, int(cus))
+
+    # ---- the rows of a Taylor term over workgroups (csrc/kernels_batch_rows.h)
+    @staticmethod
+    def row_bounds(indptr, rows):
+        """The rows + 1 boundaries the library cuts a pattern's K rows at: boundary p is the first row at which the prefix of `indptr`
+        reaches p nnzL / rows (compared in integers), the last one is K.  Contiguous ranges that cover [0, K), balanced by stored
+        entries: every range holds at most ceil(nnzL / rows) entries plus its last row's, and a range may be empty."""
+        ip = [int(x) for x in indptr]
+        K, rows = len(ip) - 1, int(rows)
+        nnz, out, r = ip[K], [], 0
+        for p in range(rows):
+            while r < K and ip[r] * rows < p * nnz:
+                r += 1
+            out.append(r)
+        return out + [K]
+
+    def row_ranges(self, inst, rows):
+        """The boundaries the library uses for instance `inst` at `rows` row parts (mmw_batch_row_ranges): part p owns the rows
+        [out[p], out[p + 1]).  Answers on a host-only batch too."""
+        out = np.empty(int(rows) + 1, dtype=np.int32)
+        check(lib().mmw_batch_row_ranges(self._h, int(inst), int(rows), _pi(out)))
+        return [int(x) for x in out]
+
+    def suggest_row_split(self, cus=256):
+        """The rule of set_row_split("auto"): with w_i = nnzL_i D_i (the work of one Taylor term) and G_i the instance's current
+        column slices, rows_i = clamp(ceil(round(w_i cus / sum w) / G_i), 1, min(64, ceil(K_i / 64))): the instance's share of `cus`
+        compute units, divided by the workgroups its column slices already give it, at least 64 rows per part.  The rule is a
+        choice, not a measurement (DESIGN section 12 has what was measured).  Instances that sit out get 1 and do not weigh."""
+        w = [float(s["nnzL"]) * s["D"] if a else 0.0 for s, a in zip(self.sizes, self.active)]
+        tot = sum(w)
+        if tot <= 0.0:
+            return [1] * self.B
+        cols = self.split_parts or [1] * self.B
+        out = []
+        for wi, s, cp in zip(w, self.sizes, cols):
+            G = self.split_slices(s["D"], cp)[1]
+            out.append(max(1, min(-(-int(round(wi * cus / tot)) // G), BATCH_MAX_ROW_PARTS, -(-s["K"] // 64))))
+        return out
+
+    def set_row_split(self, rows, cus=256):
+        """Row parts per instance for the iterations that follow, multiplied with the column slices of `set_split`: an int for all,
+        one per instance, "auto" (`suggest_row_split(cus)`, taken again after every `set_slots`), or None / all ones for no row split.
+        One launch per Taylor term and one host synchronisation per iteration; every field stays bitwise what the single launch gives
+        (DESIGN section 12)."""
+        self._set_parts("set_row_split", rows, int(cus))
+
+    def split_call(self):
+        """The last `iterate` of this batch (MMW_F_SPLIT_CALL): {"path": 0 one launch / 1 the column split's three per iteration / 2 the
+        row split's one per Taylor term, "launches", "idle" (launches in which every workgroup was past its schedule or had all its
+        columns stopped; path 2 only), "widest" (workgroups of the largest launch)}."""
+        v = self.read(0, F_SPLIT_CALL, 4)
+        return {"path": int(v[0]), "launches": int(v[1]), "idle": int(v[2]), "widest": int(v[3])}
 
     # ---- several workgroups per instance for the factor (csrc/kernels_batch_factor_split.h)
     @staticmethod

@@ -102,6 +102,13 @@ def _split(b, split):
         b.set_split(split)
 
 
+def _row_split(b, row_split):
+    """The `row_split=` keyword of the workflows, beside `split=`: None is no row split; an int, one int per instance or "auto" goes to
+    `BatchSolver.set_row_split` after the column split is set (every result stays bitwise the same; see there)."""
+    if row_split is not None:
+        b.set_row_split(row_split)
+
+
 def _factor_split(b, factor_split, in_batch=True):
     """The `factor_split=` keyword of the workflows: None is k_batch_factor's one launch; an int, one int per instance or "auto" goes
     to `BatchSolver.set_factor_split` (every result stays bitwise the same; see there).  There is no batch factor to split under
@@ -126,11 +133,12 @@ def _finish(z, rem, used, i, Z, seed):
 
 
 def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle", split=None,
-                        factor_split=None):
+                        factor_split=None, row_split=None):
     """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
     X_half per instance through export + mmw_factor on one reused fp64 handle per state, or with epilogue="batch" all of them in one
     more launch (instances over the epilogue limit still go through a handle).  factor_split: workgroups per instance for that
-    factor (`BatchSolver.set_factor_split`; epilogue="batch" only).  Returns [(True, X_half), ...]."""
+    factor (`BatchSolver.set_factor_split`; epilogue="batch" only).  row_split: row parts per instance beside `split`
+    (`BatchSolver.set_row_split`).  Returns [(True, X_half), ...]."""
     del bs_iteration  # the log index of the reference's signature; nothing here depends on it
     in_batch = _check_epilogue(epilogue)
     _factor_split(None, factor_split, in_batch)
@@ -139,6 +147,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
         _split(b, split)
+        _row_split(b, row_split)
         _factor_split(b, factor_split, in_batch)
         b.iterate(nit, None, seeds)
         take = [in_batch and _fits(b, i) for i in range(len(states))]
@@ -151,7 +160,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
         b.close()
 
 
-def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, split=None):
+def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, split=None, row_split=None):
     """The reference's convergence sweeps (sim_convergence_rho.py, sim_all_mmw.py: LOG_GAP = True, one run per instance) as one
     batch: `nit` and `eta` are one value for all or one per instance, the gap is logged inside the launch (mmw.py:79-117) and all
     iterations of all instances run in ONE `iterate`.  Returns per instance {"gap": [nit, 3], "lanczos_steps": [nit]}; the three
@@ -165,6 +174,7 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
         b.set_eta(etas)
         b.set_gap(True)
         _split(b, split)
+        _row_split(b, row_split)
         b.iterate(max(nits), None, seeds)
         out = []
         for i in range(B):
@@ -176,14 +186,15 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
 
 
 def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None,
-                factor_split=None):
+                factor_split=None, row_split=None):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
     Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
     factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
     one {"probes", "iterate_s", "epilogue_s", "factor_call"} per round (epilogue_s: everything of the round after `iterate`, the
     bisection's own bookkeeping included; factor_call: `BatchSolver.factor_call()` of the round's batch factor, None without one).  split: workgroups per instance (`BatchSolver.set_split`: an int, one per instance or "auto", which
     follows the slot counts of every round; None: one each); the results are bitwise the same.  factor_split: the same for the
-    factor of epilogue="batch" (`BatchSolver.set_factor_split`; with epilogue="handle" anything but None raises ValueError), bitwise
+    factor of epilogue="batch" (`BatchSolver.set_factor_split`; with epilogue="handle" anything but None raises ValueError), row_split: row parts
+    per instance multiplied with `split`'s column slices (`BatchSolver.set_row_split`: an int, one per instance or "auto"), bitwise
     too."""
     in_batch = _check_epilogue(epilogue)
     _factor_split(None, factor_split, in_batch)
@@ -200,6 +211,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     hs = _Handles(states, nit, eta, rank_radio, device)
     try:
         _split(b, split)
+        _row_split(b, row_split)
         _factor_split(b, factor_split, in_batch)
         while not all(done):
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
@@ -237,7 +249,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
 
 
 def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
-                rank_radio=2, device=0, timings=None, split=None, factor_split=None):
+                rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None):
     """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
     many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
     the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
@@ -256,7 +268,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
     found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                        factor_split=factor_split)
+                        factor_split=factor_split, row_split=row_split)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
@@ -264,6 +276,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
     try:
         _split(b, split)
+        _row_split(b, row_split)
         _factor_split(b, factor_split)
         b.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
         b.factor()
@@ -336,7 +349,7 @@ def _geometry(d):
     return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
 
 
-def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None):
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
     (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
@@ -351,7 +364,7 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         states = [env.state(i) for i in range(B)]
         t0 = time.perf_counter()
         found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                            factor_split=factor_split)
+                            factor_split=factor_split, row_split=row_split)
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -409,7 +422,7 @@ class single:
     """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
     one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None):
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None, row_split=None):
         self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
         self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
         _factor_split(None, factor_split, _check_epilogue(epilogue))
@@ -417,6 +430,7 @@ class single:
         self.probes = []
         self._b = None
         self._split = split
+        self._row_split = row_split
         self._factor_split = factor_split
         self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
 
@@ -425,6 +439,7 @@ class single:
         if self._b is None:
             self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
             _split(self._b, self._split)
+            _row_split(self._b, self._row_split)
             _factor_split(self._b, self._factor_split)
         self._b.set_slots([Z], self.nit)
         self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])

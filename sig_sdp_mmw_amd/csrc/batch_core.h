@@ -18,13 +18,13 @@ inline int batch_takers(const char* who, int B, const int32_t* take, const char*
     if (tk.empty()) return fail(MMW_ERR_ARG, std::string(who) + ": no instance takes part");
     return MMW_OK;
 }
-// workgroups per instance as the entry `who` takes them (null or all ones: `dst` empty, the unsplit path)
-inline int check_parts(const char* who, const int32_t* p, int B, std::vector<int>& dst) {
+// workgroups per instance as the entry `who` takes them, 1 ... maxp each (null or all ones: `dst` empty, the unsplit path)
+inline int check_parts(const char* who, const int32_t* p, int B, std::vector<int>& dst, int maxp = MMW_BATCH_MAX_PARTS) {
     bool any = false;
     for (int b = 0; p && b < B; ++b) {
-        if (p[b] < 1 || p[b] > MMW_BATCH_MAX_PARTS)
+        if (p[b] < 1 || p[b] > maxp)
             return fail(MMW_ERR_ARG, std::string(who) + ": instance " + std::to_string(b) + ": parts = " + std::to_string(p[b]) + " is outside [1, " +
-                                         std::to_string(MMW_BATCH_MAX_PARTS) + "]");
+                                         std::to_string(maxp) + "]");
         any = any || p[b] > 1;
     }
     if (any) dst.assign(p, p + B);

@@ -1,16 +1,18 @@
 // Batched solver (mmw_batch_*): many small fp64 instances, one workgroup each (csrc/kernels_batch.h).  The handle holds a core
 // (batch_core.h: patterns, counters, the two arenas) and four parts by value, each with the state and the device buffers of one feature:
-// gap and split (batch_iterate.h), epi (batch_epilogue.h), greedy (batch_gm.h), and sequences them.  Whatever a part holds that a new
+// gap and split (batch_iterate.h), rows (batch_rows.h), epi (batch_epilogue.h), greedy (batch_gm.h), and sequences them.  Whatever a part holds that a new
 // run invalidates, it drops in its on_restart: reset and set_slots call those and name no field of a part.
 #pragma once
 #include "batch_epilogue.h"
 #include "batch_gm.h"
 #include "batch_iterate.h"
+#include "batch_rows.h"
 
 struct mmw_batch {
     BatchCore core;
     BatchGap gap;
     BatchSplit split;
+    BatchRows rows;
     BatchEpilogue epi;
     BatchGm greedy;
     DevBuf<double> rbuf, skbuf;  // the call's sketches (iterate), the block handed out (sketch)
@@ -128,12 +130,19 @@ struct mmw_batch {
         MMW_TRY(copy_h2d(core.d_desc.p, dd.data(), dd.size() * sizeof(BatchDesc), st));
         const double* rv = randv ? rbuf.p : (const double*)nullptr;
         MMW_TRY(gap.stage(core));
-        if (split.wanted(dd)) {
+        int nmax = 0;
+        for (int b = 0; b < B; ++b) nmax = std::max(nmax, dd[b].nrun);
+        if (rows.wanted(dd)) {
+            MMW_TRY(rows.run(core, gap, split.parts, dd, rv));
+        } else if (split.wanted(dd)) {
             MMW_TRY(split.run(core, gap, dd, rv));
-        } else if (gap.on) {
-            hipLaunchKernelGGL(k_mmw_batch<true>, dim3(B), dim3(BATCH_THREADS), 0, st, core.d_desc.p, core.ia.p, core.fa.p, rv, gap.d_gdesc.p, gap.ga.p);
+            rows.record(1, 3 * (int64_t)nmax, 0, std::max<int64_t>(split.d_wexpm.n, std::max<int64_t>(split.d_wx.n, B)));
         } else {
-            hipLaunchKernelGGL(k_mmw_batch<false>, dim3(B), dim3(BATCH_THREADS), 0, st, core.d_desc.p, core.ia.p, core.fa.p, rv, (const GapDesc*)nullptr, (double*)nullptr);
+            if (gap.on)
+                hipLaunchKernelGGL(k_mmw_batch<true>, dim3(B), dim3(BATCH_THREADS), 0, st, core.d_desc.p, core.ia.p, core.fa.p, rv, gap.d_gdesc.p, gap.ga.p);
+            else
+                hipLaunchKernelGGL(k_mmw_batch<false>, dim3(B), dim3(BATCH_THREADS), 0, st, core.d_desc.p, core.ia.p, core.fa.p, rv, (const GapDesc*)nullptr, (double*)nullptr);
+            rows.record(0, 1, 0, B);
         }
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(st));
@@ -154,6 +163,7 @@ struct mmw_batch {
             case MMW_F_NORM_H: return read_host(P.norm_H, out, n);
             case MMW_F_ST_DATA: return read_host(P.st_data, out, n);
             case MMW_F_FACTOR_CALL: return read_host(std::vector<double>(epi.fs.call, epi.fs.call + 4), out, n);
+            case MMW_F_SPLIT_CALL: return read_host(std::vector<double>(rows.call, rows.call + 4), out, n);
             default: break;
         }
         if (core.host_only) return BatchCore::host_only_batch();
@@ -199,6 +209,14 @@ struct mmw_batch {
     int set_gap(int enabled, int32_t m_cap) { return gap.set(core, enabled, m_cap); }
     int read_gap(int b, double* out, int64_t n) { return gap.read(core, b, out, n); }
     int set_split(const int32_t* p) { return split.set(core, p); }
+    int set_row_split(const int32_t* p) { return rows.set(core, p); }
+    int row_ranges(int b, int32_t nrows, int32_t* out) const {
+        MMW_TRY(core.check_inst(b));
+        if (nrows < 1 || nrows > MMW_BATCH_MAX_ROW_PARTS)
+            return fail(MMW_ERR_ARG, "mmw_batch_row_ranges: rows = " + std::to_string(nrows) + " is outside [1, " + std::to_string(MMW_BATCH_MAX_ROW_PARTS) + "]");
+        batch_row_bounds(core.H[b].l_indptr.data(), core.H[b].K, nrows, out);
+        return MMW_OK;
+    }
     int set_factor_split(const int32_t* p) { return epi.set_split(core, p); }
     int factor(const int32_t* take, const int32_t* rank, const double* const* xavg) { return epi.factor(core, take, rank, xavg); }
     int factor_random(const int32_t* take, const uint64_t* seeds) { return epi.factor_random(core, take, seeds); }

@@ -1,15 +1,21 @@
-"""Developer tool (GPU box): what the batch's split mode (BatchSolver.set_split, csrc/kernels_batch_split.h) buys, fp64, device
-sketches, default expm tolerance (1e-9).
+"""Developer tool (GPU box): what the batch's split modes (BatchSolver.set_split, csrc/kernels_batch_split.h; BatchSolver.set_row_split,
+csrc/kernels_batch_rows.h) buy, fp64, device sketches, default expm tolerance (1e-9).
 
-    python tools/batch_split.py [--legs a,b,c,d,e] [--nit 150] [--er-nit 30] [--runs 3] [--limit 240] [--cus 256]
+    python tools/batch_split.py [--legs a,b,c,d,e] [--row-split] [--nit 150] [--er-nit 30] [--runs 3] [--limit 240] [--cus 256]
 
-Legs, each `--runs` times under its own time limit (the process ends if a leg overruns it), one JSON line per run:
+Legs, `--runs` rounds with the legs alternating inside a round, every run under its own time limit (the process ends if a run
+overruns it), one JSON line per run (with MMW_F_SPLIT_CALL's launches and idle launches of the run's one iterate call):
   a  the 64-instance journal sweep (tools/batch_small.py's, K 75 ... 675), single-launch kernel
   b  the same sweep with set_split("auto")
   c  the same sweep on handles, 8 streams (tools/batch_small.py's leg)
   d  one K = 675 instance at parts 1, 4, 8, 16: ms per iteration
   e  er-5pct-2k x 8 (K 2 000, D 64) single launch and at the auto split (report only: D = 64 caps it at 8 slices)
-and a summary line: median(b) against min(a) -- the bar -- and against median(c)."""
+--row-split adds
+  r  the sweep with set_split("auto") and set_row_split("auto")
+  s  the K = 675 instance at rows 1, 2, 4, 8 x parts "auto"
+  f  er-5pct-2k x 8 at rows 8, 16, 32 x parts 8
+  h  er-5pct-2k x 8 on handles, 8 streams: f's comparator
+and summary lines: median(b) and median(r) against min(a) -- the bar -- and against median(c); median(f*) against min(h)."""
 import argparse
 import faulthandler
 import json
@@ -27,14 +33,21 @@ from sig_sdp_mmw_amd import _lib  # noqa: E402
 from sig_sdp_mmw_amd.graphs import er_contention_graph  # noqa: E402
 
 
-def run(states, Zs, nit, split, cus, eta=0.04):
+def run(states, Zs, nit, split, cus, eta=0.04, rows=None, info=None):
     b = _lib.BatchSolver(Zs, states, nit, eta)
     if split is not None:
         b.set_split(split, cus) if split == "auto" else b.set_split(split)
+    if rows is not None:
+        b.set_row_split(rows, cus) if rows == "auto" else b.set_row_split(rows)
     parts = b.split_parts
     t0 = time.perf_counter()
     b.iterate(nit, None, np.arange(len(states), dtype=np.uint64) + 1)
     t = time.perf_counter() - t0
+    if info is not None:
+        call = b.split_call()
+        rp = b.row_split_parts
+        info.update(launches_per_iteration=round(call["launches"] / nit, 2), idle_share=round(call["idle"] / max(1, call["launches"]), 4),
+                    widest=call["widest"], max_rows=int(max(rp)) if rp else 1)
     b.close()
     return t, parts
 
@@ -48,8 +61,9 @@ def main():
     ap.add_argument("--cus", type=int, default=256)
     ap.add_argument("--er-nit", type=int, default=30)
     ap.add_argument("--instances", type=int, default=64)
+    ap.add_argument("--row-split", action="store_true", help="add the row-split legs r, s, f, h")
     a = ap.parse_args()
-    legs = [x for x in a.legs.split(",") if x]
+    legs = [x for x in a.legs.split(",") if x] + (["r", "s", "f", "h"] if a.row_split else [])
     s0, z0 = sweep(2)
     run(s0, z0, 2, None, a.cus)
     run(s0, z0, 2, 2, a.cus)  # module load, first launches
@@ -57,13 +71,10 @@ def main():
     B = len(states)
     times = {}
 
+    todo = []
+
     def leg(name, fn, **extra):
-        faulthandler.dump_traceback_later(a.limit, exit=True)
-        for r in range(a.runs):
-            t, more = fn()
-            times.setdefault(name, []).append(t)
-            print(json.dumps({"leg": name, "run": r, "seconds": round(t, 4), **extra, **more}), flush=True)
-        faulthandler.cancel_dump_traceback_later()
+        todo.append((name, fn, extra))
 
     def batch_leg(split):
         def fn():
@@ -91,12 +102,57 @@ def main():
                 t, parts = run(er, [32] * 8, a.er_nit, split, a.cus)
                 return t, {"instances": 8, "nit": a.er_nit, "instances_per_s": round(8 / t, 2), "max_parts": int(max(parts)) if parts else 1}
             leg("e-" + ("auto" if split else "single"), fn, path="er-5pct-2k-x8")
-    if "a" in times and "b" in times:
-        out = {"summary": "median(b) against min(a)", "min_a_s": round(min(times["a"]), 4), "median_b_s": round(statistics.median(times["b"]), 4),
-               "bar_met": statistics.median(times["b"]) < min(times["a"])}
-        if "c" in times:
-            out["median_c_s"] = round(statistics.median(times["c"]), 4)
-        print(json.dumps(out), flush=True)
+    rows_of = {}
+    if "r" in legs:
+        def fn_r():
+            more = {}
+            t, parts = run(states, Zs, a.nit, "auto", a.cus, rows="auto", info=more)
+            return t, {"instances": B, "nit": a.nit, "instances_per_s": round(B / t, 2), "max_parts": int(max(parts)) if parts else 1, **more}
+        leg("r", fn_r, path="batch-split-auto-rows-auto")
+    if "s" in legs:
+        i675 = max(range(B), key=lambda i: states[i][0].shape[0])
+        for rows in (1, 2, 4, 8):
+            def fn(rows=rows):
+                more = {}
+                t, parts = run([states[i675]], [Zs[i675]], a.nit, "auto", a.cus, rows=rows, info=more)
+                return t, {"K": int(states[i675][0].shape[0]), "Z": int(Zs[i675]), "ms_per_iteration": round(t * 1e3 / a.nit, 4),
+                           "parts": int(max(parts)) if parts else 1, **more}
+            leg("s%d" % rows, fn, path="one-instance-rows", rows=rows)
+    if "f" in legs or "h" in legs or any(x[:1] == "f" and x[1:].isdigit() for x in legs):
+        er = [er_contention_graph(2000, 0.05, seed=100 + i) for i in range(8)]
+        for rows in (8, 16, 32):
+            if "f" not in legs and "f%d" % rows not in legs:
+                continue
+
+            def fn(rows=rows):
+                more = {}
+                t, _ = run(er, [32] * 8, a.er_nit, 8, a.cus, rows=rows, info=more)
+                return t, {"instances": 8, "nit": a.er_nit, "instances_per_s": round(8 / t, 2), **more}
+            leg("f%d" % rows, fn, path="er-5pct-2k-x8-rows", rows=rows, parts=8)
+        if "h" in legs:
+            def fn_h():
+                t = run_handles(er, [32] * 8, a.er_nit)
+                return t, {"instances": 8, "nit": a.er_nit, "instances_per_s": round(8 / t, 2)}
+            leg("h", fn_h, path="er-5pct-2k-x8-handles-8-streams")
+    for r in range(a.runs):  # the legs alternate inside a round
+        for name, fn, extra in todo:
+            faulthandler.dump_traceback_later(a.limit, exit=True)
+            t, more = fn()
+            faulthandler.cancel_dump_traceback_later()
+            times.setdefault(name, []).append(t)
+            print(json.dumps({"leg": name, "run": r, "seconds": round(t, 4), **extra, **more}), flush=True)
+    med = statistics.median
+    for x in ("b", "r"):
+        if "a" in times and x in times:
+            out = {"summary": "median(%s) against min(a)" % x, "min_a_s": round(min(times["a"]), 4), "median_%s_s" % x: round(med(times[x]), 4),
+                   "bar_met": med(times[x]) < min(times["a"])}
+            if "c" in times:
+                out["median_c_s"] = round(med(times["c"]), 4)
+            print(json.dumps(out), flush=True)
+    for x in sorted(times):
+        if x[:1] == "f" and "h" in times:
+            print(json.dumps({"summary": "median(%s) against min(h)" % x, "min_h_s": round(min(times["h"]), 4), "median_%s_s" % x: round(med(times[x]), 4),
+                              "bar_met": med(times[x]) < min(times["h"])}), flush=True)
 
 
 if __name__ == "__main__":
