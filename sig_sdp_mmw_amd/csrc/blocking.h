@@ -677,7 +677,11 @@ inline std::string verify_blocking(const HostBlocking& B, int K, const std::vect
             if (real != indptr[r + 1] - indptr[r]) return "row lost entries";
             if (local[r] >= 0 && B.self_li[q] != (uint16_t)local[r]) return "self index mismatch";
         }
-        // SDDMM slots
+        // SDDMM slots (build_sd_tables leaves them unbuilt for a blocking that is not usable: no kernel reads them then)
+        if (!B.sd_ready) {
+            for (int u = u0; u < u1; ++u) local[B.un_cols[u]] = -1;
+            continue;
+        }
         const int s0 = B.sd2_ptr[b], s1 = B.sd2_ptr[b + 1];
         if ((s1 - s0) % SD2_THREADS || s1 - s0 < SD2_THREADS) return "slot range is not whole rounds";
         for (int sidx = s0; sidx < s1; ++sidx) {
@@ -712,7 +716,7 @@ inline std::string verify_blocking(const HostBlocking& B, int K, const std::vect
     }
     for (int64_t e = 0; e < nnz; ++e)
         if (!ent_seen[e]) return "a CSR entry is missing from the blocked arrays";
-    if (slots_used != nupper) return "the SDDMM slots do not hold every upper-triangular entry exactly once";
+    if (B.sd_ready && slots_used != nupper) return "the SDDMM slots do not hold every upper-triangular entry exactly once";
     return "";
 }
 

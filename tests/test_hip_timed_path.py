@@ -53,14 +53,15 @@ def compare_calls(snaps, o, nit, bars=(1e-5, 1e-4)):
         compare(got, o, j, j == len(snaps) - 1, nit, bars)
 
 
-def follow(state, Z, nit, n1, eta, seed, dtype=_lib.F32):
-    """Device run in two calls (each chunked by the library), then the oracle on the regenerated sketches."""
-    s = _lib.Solver(Z, state, nit, eta, dtype=dtype)
+def follow(state, Z, nit, n1, eta, seed, dtype=_lib.F32, rank_radio=2, oracle=oracle_for):
+    """Device run in two calls (each chunked by the library), then the oracle on the regenerated sketches (`oracle`: oracle_for, or a
+    caller's cache in front of it)."""
+    s = _lib.Solver(Z, state, nit, eta, rank_radio=rank_radio, dtype=dtype)
     s.set_expm(_lib.EXPM_LANCZOS, 12, 1e-6 if dtype == _lib.F32 else 1e-12)  # bench.py's settings (fp32) / tight for the fp64 bars
     mid, end = run_calls(s, [n1, nit - n1], seed)
     info = s.read(_lib.F_DUAL_INFO)
     replays = s.read(_lib.F_BLOCKING)[3]
-    o = oracle_for(s.sketch, state, Z, nit, eta, seed, [n1, nit - n1])
+    o = oracle(s.sketch, state, Z, nit, eta, seed, [n1, nit - n1])
     s.close()
     return mid, end, o, info, replays
 
