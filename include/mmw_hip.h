@@ -314,6 +314,18 @@ int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]);
 /* per-instance slot counts for the next probes (norm_H and D rebuilt, every instance reset to the initial point with `nit`);
  * Z[b] <= 0 takes instance b out of the runs until a later call gives it a slot count */
 int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit);
+/*
+ * mmw_batch_set_slots_warm: the same rebinding, but every instance that has iterated CONTINUES from its previous probe's iterate
+ * instead of the reference's initial point (opt-in warm start of the bisection as mmw_set_slots_warm: binary_search_relaxation.py:44-72
+ * calls the solver once per probed Z and the reference restarts each time, mmw.py:62-68): e_accu, L_accu and the last X / Y are
+ * kept, the running sums of X and Y restart (the batch adds X_i / Y_i when iteration i starts, so after n iterations they hold the
+ * kept X / Y and n - 1 new terms), the iterations done read 0 and `nit` more are announced.  An instance that has not iterated
+ * falls back to mmw_batch_set_slots.  Z[b] <= 0 takes instance b out of the runs WITH its iterate and its counters carried over,
+ * so a later warm call with a slot count picks it up where it stopped.  Both entries move the arena on the device
+ * (csrc/kernels_batch_relayout.h: one small upload and one launch, into a second arena that then trades places with the first).
+ * MMW_ERR_STATE on a host-only batch.
+ */
+int mmw_batch_set_slots_warm(mmw_batch* b, const int32_t* Z, int32_t nit);
 int mmw_batch_reset(mmw_batch* b, int32_t nit);
 /* one step size per instance (eta[B]) for the iterations that follow */
 int mmw_batch_set_eta(mmw_batch* b, const double* eta);

@@ -32,7 +32,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_factor", "mmw_expm_apply", "mmw_sym_eig", "mmw_round", "mmw_env_create", "mmw_env_destroy", "mmw_env_sizes", "mmw_env_state",
            "mmw_env_evaluate", "mmw_create_from_env", "mmw_env_bounds", "mmw_gm_create", "mmw_gm_destroy", "mmw_gm_sizes", "mmw_gm_pass",
            "mmw_gm_run", "mmw_gm_assign", "mmw_batch_create", "mmw_batch_destroy", "mmw_batch_sizes", "mmw_batch_set_slots",
-           "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
+           "mmw_batch_set_slots_warm", "mmw_batch_reset", "mmw_batch_set_eta", "mmw_batch_set_expm", "mmw_batch_iterate", "mmw_batch_read_f64", "mmw_batch_read_i32",
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
@@ -106,6 +106,7 @@ def lib():
     L.mmw_batch_destroy.argtypes = [C.c_void_p]
     L.mmw_batch_sizes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
     L.mmw_batch_set_slots.argtypes = [C.c_void_p, p_i32, C.c_int32]
+    L.mmw_batch_set_slots_warm.argtypes = [C.c_void_p, p_i32, C.c_int32]
     L.mmw_batch_reset.argtypes = [C.c_void_p, C.c_int32]
     L.mmw_batch_set_eta.argtypes = [C.c_void_p, p_f64]
     L.mmw_batch_set_expm.argtypes = [C.c_void_p, C.c_int, C.c_double]
@@ -514,13 +515,16 @@ class BatchSolver(_Handle):
         self.nits = [int(nit)] * self.B
         self._load_sizes()
 
-    def set_slots(self, Zs, nit):
-        """Per-instance slot counts (0: the instance sits out until a later call gives it one); every instance restarts."""
+    def set_slots(self, Zs, nit, warm=False):
+        """Per-instance slot counts (0: the instance sits out until a later call gives it one); every instance restarts.
+        warm=True (mmw_batch_set_slots_warm): an instance that has iterated continues from its previous probe's iterate with its
+        sums restarted and `nit` more iterations announced, one that has not restarts cold, and one that sits out keeps its
+        iterate and its counters, so a later warm call picks it up."""
         z = _i32(Zs)
         if z.size != self.B:
             raise MMWError("set_slots: one slot count per instance")
-        check(lib().mmw_batch_set_slots(self._h, _pi(z), int(nit)))
-        self.nits = [int(nit)] * self.B
+        check((lib().mmw_batch_set_slots_warm if warm else lib().mmw_batch_set_slots)(self._h, _pi(z), int(nit)))
+        self.nits = [self.nits[b] if warm and int(z[b]) <= 0 else int(nit) for b in range(self.B)]
         self.active = [int(x) > 0 for x in z]
         self._load_sizes()
         for who in self._SPLITS:  # "auto" follows the slot counts (in _SPLITS' order: the row parts follow the column slices)

@@ -185,8 +185,18 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
         b.close()
 
 
+def warm_iterations(nit, warm_fraction):
+    """Iterations of a warm-started probe: max(1, ceil(nit * warm_fraction)), the rule of `mmw._run`."""
+    return max(1, int(math.ceil(int(nit) * float(warm_fraction))))
+
+
+def _check_warm(warm_fraction):
+    if not 0.0 < float(warm_fraction) <= 1.0:
+        raise ValueError("warm_fraction must be in (0, 1], got %r" % (warm_fraction,))
+
+
 def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None,
-                factor_split=None, row_split=None):
+                factor_split=None, row_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
     Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
     factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
@@ -195,9 +205,13 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     follows the slot counts of every round; None: one each); the results are bitwise the same.  factor_split: the same for the
     factor of epilogue="batch" (`BatchSolver.set_factor_split`; with epilogue="handle" anything but None raises ValueError), row_split: row parts
     per instance multiplied with `split`'s column slices (`BatchSolver.set_row_split`: an int, one per instance or "auto"), bitwise
-    too."""
+    too.  warm_start (opt-in; NOT the reference's search, which restarts every probe at mmw.py:62-68): the first probe of every
+    instance runs cold with `nit`, every later round continues from the previous probe's iterate (`set_slots(..., warm=True)`) with
+    `warm_iterations(nit, warm_fraction)` iterations; the probe seeds are unchanged.  Every result also holds "iters", the
+    iterations of every probe in order, and every timings row "set_slots_s", the round's slot change."""
     in_batch = _check_epilogue(epilogue)
     _factor_split(None, factor_split, in_batch)
+    _check_warm(warm_fraction)
     B = len(states)
     bs = binary_search_relaxation()
     bounds = [bs.set_bounds(st) for st in states]
@@ -205,6 +219,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     right = [ub for _, ub in bounds]
     done = [False] * B
     probes = [[] for _ in range(B)]
+    iters = [[] for _ in range(B)]
     out = [None] * B
     mids = [max(2, math.floor(float(l + r) / 2.)) for l, r in zip(left, right)]
     b = _lib.BatchSolver(mids, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -215,10 +230,13 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
         _factor_split(b, factor_split, in_batch)
         while not all(done):
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
-            b.set_slots(mids, nit)
+            warm = bool(warm_start) and any(probes)  # the instances run in lockstep: after the first round every one has iterated
+            n_round = warm_iterations(nit, warm_fraction) if warm else nit
+            ts = time.perf_counter()
+            b.set_slots(mids, n_round, warm=warm)
             seeds = np.array([probe_seed(seed, i, len(probes[i])) for i in range(B)], dtype=np.uint64)
             t0 = time.perf_counter()
-            b.iterate(nit, None, seeds)
+            b.iterate(n_round, None, seeds)
             t1 = time.perf_counter()
             take = [in_batch and not done[i] and _fits(b, i) for i in range(B)]
             if any(take):
@@ -235,13 +253,14 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
                     Xh = _factor(b, i, h, Z, rank_radio, 0)
                     z_vec, Z, rem = _round(h, Z, Xh, states[i], probe_seed(seed, i, len(probes[i])), nattempt)
                 probes[i].append(Z)
+                iters[i].append(n_round)
                 left[i], right[i], fin = binary_search_relaxation._step(left[i], right[i], Z, rem)
                 if fin:
                     done[i] = True
-                    out[i] = {"Z": Z, "z_vec": z_vec, "remainder": rem, "probes": probes[i], "bounds": bounds[i]}
+                    out[i] = {"Z": Z, "z_vec": z_vec, "remainder": rem, "probes": probes[i], "bounds": bounds[i], "iters": iters[i]}
             if timings is not None:
                 timings.append({"probes": int(sum(1 for m in mids if m > 0)), "iterate_s": t1 - t0, "epilogue_s": time.perf_counter() - t1,
-                                "factor_call": b.factor_call() if any(take) else None})
+                                "factor_call": b.factor_call() if any(take) else None, "set_slots_s": t0 - ts})
         return out
     finally:
         hs.close()
@@ -249,7 +268,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
 
 
 def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
-                rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None):
+                rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
     """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
     many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
     the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
@@ -260,7 +279,8 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     "ideal" variant -- nobody moves, fresh draws per point).  The drops are moved in place.
     Returns per instance {"Z", "probes", "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]}.  timings: a list
     that receives one {"device_s" (move + round + evaluate), "step_s" (the host's walk)} per point.  factor_split: workgroups per
-    instance for every factor, the search's and the last solve's (`BatchSolver.set_factor_split`)."""
+    instance for every factor, the search's and the last solve's (`BatchSolver.set_factor_split`).  warm_start / warm_fraction go to
+    the search and nowhere else (`search_many`)."""
     B = len(drops)
     for i, d in enumerate(drops):
         if d.K > _lib.BATCH_EPILOGUE_MAX_K:
@@ -268,7 +288,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
     found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                        factor_split=factor_split, row_split=row_split)
+                        factor_split=factor_split, row_split=row_split, warm_start=warm_start, warm_fraction=warm_fraction)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
@@ -349,12 +369,13 @@ def _geometry(d):
     return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
 
 
-def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None):
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None,
+                 warm_start=False, warm_fraction=1.0 / 3.0):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
     (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
     "mgain", "masso"}}.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"}.  factor_split: workgroups per instance
-    for the search's factors (`BatchSolver.set_factor_split`)."""
+    for the search's factors (`BatchSolver.set_factor_split`).  warm_start / warm_fraction go to the search and nowhere else."""
     geo = [_geometry(d) for d in drops_or_geometries]
     B = len(geo)
     env = _lib.BatchEnv([g[1] for g in geo], [g[0].shape[0] for g in geo], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
@@ -364,7 +385,7 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         states = [env.state(i) for i in range(B)]
         t0 = time.perf_counter()
         found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                            factor_split=factor_split, row_split=row_split)
+                            factor_split=factor_split, row_split=row_split, warm_start=warm_start, warm_fraction=warm_fraction)
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -420,9 +441,14 @@ def online_greedy_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, res
 
 class single:
     """The reference's solver protocol (run_with_state / rounding, binary_search_relaxation.py:50-53) for ONE state on a batch of
-    one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`."""
+    one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`
+    (with the same warm_start / warm_fraction too)."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None, row_split=None):
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None, row_split=None,
+                 warm_start=False, warm_fraction=1.0 / 3.0):
+        _check_warm(warm_fraction)
+        self.warm_start, self.warm_fraction = bool(warm_start), float(warm_fraction)
+        self.iters = []  # the iterations of every probe, in order
         self.state, self.index, self.nit, self.eta, self.seed = state, int(index), int(nit), float(eta), int(seed)
         self.nattempt, self.rank_radio, self.device = int(nattempt), int(rank_radio), int(device)
         _factor_split(None, factor_split, _check_epilogue(epilogue))
@@ -441,8 +467,11 @@ class single:
             _split(self._b, self._split)
             _row_split(self._b, self._row_split)
             _factor_split(self._b, self._factor_split)
-        self._b.set_slots([Z], self.nit)
-        self._b.iterate(self.nit, None, [probe_seed(self.seed, self.index, len(self.probes))])
+        warm = self.warm_start and len(self.probes) > 0  # as search_many: the first probe cold, every later one from its predecessor
+        n = warm_iterations(self.nit, self.warm_fraction) if warm else self.nit
+        self._b.set_slots([Z], n, warm=warm)
+        self._b.iterate(n, None, [probe_seed(self.seed, self.index, len(self.probes))])
+        self.iters.append(n)
         if self._in_batch:
             self._b.factor()
             return True, self._b.read_factor(0)

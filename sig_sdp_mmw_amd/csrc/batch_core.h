@@ -1,9 +1,11 @@
 // What every part of the batched solver reads (batch_handle.h): the instances' host patterns (built by the host code mmw_create uses,
 // build_pattern / update_slots), their run counters, and the int32 and the fp64 arena all of them are packed into.
 #pragma once
+#include <cstring>
 #include <limits>
 
 #include "kernels_batch.h"
+#include "kernels_batch_relayout.h"
 #include "solver.h"
 
 // the instances of a call: those `take` flags, or every active one (take null).  `active` null: every instance is active.
@@ -44,6 +46,7 @@ struct BatchCore {
     std::vector<BatchDesc> desc;  // offsets and sizes; nrun / iter0 / seed / o_randv are set per call
     DevBuf<int> ia;
     DevBuf<double> fa;
+    DevBuf<double> fb, rl;  // a slot change writes the fp64 arena anew into fb and swaps (relayout); rl is that call's upload
     DevBuf<BatchDesc> d_desc;
     static int host_only_batch() { return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)"); }
     int check_inst(int b) const {
@@ -64,13 +67,14 @@ struct BatchCore {
         const int64_t K = P.K, nnz = P.nnzL(), C = P.C();
         return 5 * nnz + 6 * K + 4 * C + 4 * K * D + 4 + 64;
     }
-    // offsets of every instance; the int32 arena never changes, the fp64 one follows the slot counts
-    int layout() {
-        desc.assign(B, BatchDesc{});
-        int64_t oi = 0, of = 0;
+    // Offsets of every instance for the slot counts the patterns hold now, used by creation and by every slot change: the int32 arena
+    // never changes, the fp64 one follows the slot counts.  `out` is only written when every instance fits.
+    int offsets(std::vector<BatchDesc>& out, int64_t& oi, int64_t& of) const {
+        std::vector<BatchDesc> nd((size_t)B, BatchDesc{});
+        oi = of = 0;
         for (int b = 0; b < B; ++b) {
             const HostPattern& P = H[b];
-            BatchDesc& d = desc[b];
+            BatchDesc& d = nd[b];
             const int64_t K = P.K, nnz = P.nnzL(), C = P.C();
             d.K = P.K; d.Z = P.Z; d.D = P.Z * rank_radio; d.E_asso = (int)P.E_asso(); d.C = (int)C; d.nnzL = (int)nnz;
             d.max_order = max_order; d.eta = eta[b]; d.tol = tol; d.o_randv = -1;
@@ -105,6 +109,13 @@ struct BatchCore {
             d.o_info = of = a32(of); of += 4;
             of = a32(of);
         }
+        out = std::move(nd);
+        return MMW_OK;
+    }
+    // creation only: both arenas filled on the host (the fp64 one zero but for the pattern data) and uploaded whole
+    int layout() {
+        int64_t oi = 0, of = 0;
+        MMW_TRY(offsets(desc, oi, of));
         if (host_only) return MMW_OK;
         std::vector<int> hi((size_t)oi, 0);
         std::vector<double> hf((size_t)of, 0.0);
@@ -142,5 +153,41 @@ struct BatchCore {
         // the running sums start empty: iteration i adds X_i and Y_i when it starts, so after n iterations they hold X_0 + ... + X_{n-1}
         for (int c = 0; c < d.C; ++c) init[d.o_Y - d.o_lval + c] = 1.0 / (double)d.C;
         return copy_h2d(fa.p + d.o_lval, init.data(), init.size() * sizeof(double), st);
+    }
+    // A slot change on the device (kernels_batch_relayout.h).  The patterns hold the new slot counts already; mode[b] says what
+    // instance b starts from.  One upload -- both descriptor tables, the per-instance items and the host-computed 1 / norm_H and cH --
+    // one launch from `fa` into the second arena `fb` (made on the first slot change, grown only when the new layout needs more),
+    // then the two trade places.  Every kernel takes fa.p as an argument of its launch, so nothing else has to be re-bound.
+    int relayout(const std::vector<int>& mode) {
+        std::vector<BatchDesc> nd;
+        int64_t oi = 0, of = 0;
+        MMW_TRY(offsets(nd, oi, of));
+        constexpr size_t DW = sizeof(BatchDesc) / sizeof(double), IW = sizeof(RelayoutItem) / sizeof(double);
+        static_assert(sizeof(BatchDesc) % sizeof(double) == 0 && sizeof(RelayoutItem) % sizeof(double) == 0, "the staging buffer is one array of doubles");
+        int64_t Ksum = 0;
+        for (int b = 0; b < B; ++b) Ksum += H[b].K;
+        const size_t w_old = 0, w_new = w_old + DW * B, w_item = w_new + DW * B, w_invn = w_item + IW * B, w_cH = w_invn + (size_t)Ksum;
+        std::vector<double> stage(w_cH + (size_t)Ksum);
+        std::memcpy(stage.data() + w_old, desc.data(), sizeof(BatchDesc) * B);
+        std::memcpy(stage.data() + w_new, nd.data(), sizeof(BatchDesc) * B);
+        int64_t os = 0;
+        for (int b = 0; b < B; ++b) {
+            const HostPattern& P = H[b];
+            const RelayoutItem t{mode[b], 0, os, 1.0 / (double)nd[b].C};
+            std::memcpy(stage.data() + w_item + IW * b, &t, sizeof t);
+            for (int k = 0; k < P.K; ++k) stage[w_invn + os + k] = 1.0 / P.norm_H[k];
+            std::copy(P.cH.begin(), P.cH.end(), stage.begin() + w_cH + os);
+            os += P.K;
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(fb.alloc((size_t)of));
+        MMW_TRY(rl.upload(stage, st));
+        hipLaunchKernelGGL(k_batch_relayout, dim3(B), dim3(BATCH_THREADS), 0, st, (const BatchDesc*)(rl.p + w_old), (const BatchDesc*)(rl.p + w_new),
+                           (const RelayoutItem*)(rl.p + w_item), rl.p + w_invn, rl.p + w_cH, ia.p, fa.p, fb.p);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        fa.swap(fb);
+        desc = std::move(nd);
+        return MMW_OK;
     }
 };

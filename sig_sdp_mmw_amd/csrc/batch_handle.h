@@ -85,23 +85,32 @@ struct mmw_batch {
         }
         return on_restart();
     }
-    int set_slots(const int32_t* Z, int32_t nit_) {
+    // Same states, new slot counts: the Z-dependent scalars on the host (update_slots), the arena on the device (BatchCore::relayout).
+    // Cold, every instance restarts at the initial point.  Warm (mmw_batch_set_slots_warm), an instance that has iterated keeps
+    // (e_accu, L, X, Y) and restarts its sums; one that has not falls back to cold, as Solver::set_slots does; one with Z[b] <= 0 sits
+    // out with its iterate and its counters carried over, so a later warm call can pick it up.
+    int set_slots(const int32_t* Z, int32_t nit_, bool warm) {
         if (core.host_only) return BatchCore::host_only_batch();
         if (nit_ < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
+        const std::string who = warm ? "mmw_batch_set_slots_warm" : "mmw_batch_set_slots";
         std::vector<HostPattern>& H = core.H;
         std::vector<HostPattern> keep = H;  // a refused slot count leaves the batch as it was
         for (int b = 0; b < core.B; ++b) {
             if (Z[b] <= 0) continue;
             const std::string err = update_slots(H[b], Z[b]);
-            if (!err.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, "mmw_batch_set_slots: instance " + std::to_string(b) + ": " + err); }
+            if (!err.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, who + ": instance " + std::to_string(b) + ": " + err); }
             const std::string lerr = BatchCore::check_limits(H[b], Z[b] * core.rank_radio);
-            if (!lerr.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, "mmw_batch_set_slots: instance " + std::to_string(b) + ": " + lerr + " (run it on a handle)"); }
+            if (!lerr.empty()) { H = std::move(keep); return fail(MMW_ERR_ARG, who + ": instance " + std::to_string(b) + ": " + lerr + " (run it on a handle)"); }
         }
-        MMW_TRY(core.layout());
+        std::vector<int> mode((size_t)core.B);
+        for (int b = 0; b < core.B; ++b) mode[b] = !warm ? RELAYOUT_COLD : Z[b] <= 0 ? RELAYOUT_OUT : core.iter[b] == 0 ? RELAYOUT_COLD : RELAYOUT_WARM;
+        const int rc = core.relayout(mode);
+        if (rc != MMW_OK) { H = std::move(keep); return rc; }
         for (int b = 0; b < core.B; ++b) {
             core.active[b] = Z[b] > 0;
+            if (mode[b] == RELAYOUT_OUT) continue;
             core.nit[b] = nit_;
-            MMW_TRY(core.reset_one(b));
+            core.iter[b] = 0;
         }
         return on_restart();
     }

@@ -176,7 +176,8 @@ int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, c
 }
 int mmw_batch_destroy(mmw_batch* b) { return guarded("mmw_batch", [&]() -> int { delete b; return MMW_OK; }); }
 int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]) { return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->sizes(inst, out); }); }
-int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit); }); }
+int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit, false); }); }
+int mmw_batch_set_slots_warm(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit, true); }); }
 int mmw_batch_reset(mmw_batch* b, int32_t nit) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->reset(nit); }); }
 int mmw_batch_set_eta(mmw_batch* b, const double* eta) { return entry("mmw_batch", !b || !eta, "null pointer", [&] { return b->set_eta(eta); }); }
 int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_expm(max_order, tol); }); }
