@@ -326,6 +326,27 @@ int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit);
  * MMW_ERR_STATE on a host-only batch.
  */
 int mmw_batch_set_slots_warm(mmw_batch* b, const int32_t* Z, int32_t nit);
+/*
+ * mmw_batch_carry: the warm start ACROSS states (the stations have moved; a re-solve per time point of the online sweeps).  `src` is
+ * a batch on the old states that has iterated, `dst` a batch on the new states as mmw_batch_create made it, at any slot counts, that
+ * has not.  For every instance `take` flags (NULL: all) the iterate (e_accu, L_accu, X, Y) of `src` is re-indexed onto `dst`'s
+ * pattern and constraints: entry (row, col) of L and X receives src's value at (row, col) where src's pattern stores it, else 0 (the
+ * diagonal is in both, so X's diagonal always carries); e_accu and Y, laid out [D-part K | F-part E_asso | H-part K], carry the D-
+ * and the H-part by user index and the F-part by pair (asso_x, asso_y), 0 for a pair src does not have.  Y is NOT renormalised: the
+ * first iteration's softmax rewrites it, and before that only the first term of the running sum of Y and the first row of the gap
+ * log read it.  Everything else of `dst` stays as creation left it: sums, e_this, the K x D blocks and the info record zero, the
+ * iterations done 0 and `nit` unchanged -- so a later mmw_batch_set_slots_warm on `dst`, whose rule is unchanged, still treats a
+ * carried instance that has not iterated as cold.  A taking instance whose `src` counterpart has run no iteration is left cold (not
+ * an error: mmw_batch_set_slots_warm's fallback).  The index maps are merged on the host from the two batches' patterns and go up in
+ * one copy; one launch (csrc/kernels_batch_carry.h) on dst's stream does the rest, after src's stream has been synchronised.
+ * Refused before anything is written, both batches untouched: dst == src, a host-only batch (MMW_ERR_STATE), different devices,
+ * different B, K[b] of a taking instance different in the two, a taking dst instance that has iterated (MMW_ERR_STATE).
+ * mmw_batch_carry_map: the two maps of instance `inst` as mmw_batch_carry computes them -- lmap[nl = nnzL of dst] the position in
+ * src's L / X values, cmap[nc = C of dst] the position in src's constraint vector, -1 where src has none.  Host patterns only:
+ * device == -1 batches answer too.
+ */
+int mmw_batch_carry(mmw_batch* dst, mmw_batch* src, const int32_t* take);
+int mmw_batch_carry_map(mmw_batch* dst, mmw_batch* src, int32_t inst, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc);
 int mmw_batch_reset(mmw_batch* b, int32_t nit);
 /* one step size per instance (eta[B]) for the iterations that follow */
 int mmw_batch_set_eta(mmw_batch* b, const double* eta);

@@ -37,7 +37,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
            "mmw_batch_factor_random", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
-           "mmw_batch_row_ranges"]
+           "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map"]
 
 
 class MMWError(RuntimeError):
@@ -107,6 +107,8 @@ def lib():
     L.mmw_batch_sizes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
     L.mmw_batch_set_slots.argtypes = [C.c_void_p, p_i32, C.c_int32]
     L.mmw_batch_set_slots_warm.argtypes = [C.c_void_p, p_i32, C.c_int32]
+    L.mmw_batch_carry.argtypes = [C.c_void_p, C.c_void_p, p_i32]
+    L.mmw_batch_carry_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, p_i32, C.c_int64, p_i32, C.c_int64]
     L.mmw_batch_reset.argtypes = [C.c_void_p, C.c_int32]
     L.mmw_batch_set_eta.argtypes = [C.c_void_p, p_f64]
     L.mmw_batch_set_expm.argtypes = [C.c_void_p, C.c_int, C.c_double]
@@ -530,6 +532,26 @@ class BatchSolver(_Handle):
         for who in self._SPLITS:  # "auto" follows the slot counts (in _SPLITS' order: the row parts follow the column slices)
             if who in self._auto:
                 self._apply_parts(who, getattr(self, self._SPLITS[who][1])(*self._auto[who]))
+
+    def carry_from(self, src, take=None):
+        """mmw_batch_carry: take the iterate (e_accu, L, X, Y) of `src`, a batch of the same users on the states they were in before
+        they moved, over into this batch, which has not iterated: L and X by (row, col), e_accu and Y by user and by association
+        pair, 0 for what `src` does not hold; Y is not renormalised (the first iteration rewrites it).  take: one flag per instance
+        (None: all).  An instance whose source never iterated stays cold.  `iterations_done` stays 0 and `nit` is unchanged, so
+        `set_slots(..., warm=True)` still treats a carried instance that has not iterated as cold."""
+        t = None if take is None else _i32([1 if x else 0 for x in take])
+        if t is not None and t.size != self.B:
+            raise MMWError("carry_from: one flag per instance")
+        check(lib().mmw_batch_carry(self._h, src._h, _opt_pi(t)))
+
+    def carry_map(self, src, inst):
+        """mmw_batch_carry_map: (lmap int32[nnzL], cmap int32[C]) of instance `inst` -- for every entry of this batch's L pattern and
+        of its constraint vector the position in `src`'s, -1 where `src` holds none.  Works on device=-1 batches."""
+        sz = self.sizes[inst]
+        lmap = np.empty(sz["nnzL"], dtype=np.int32)
+        cmap = np.empty(sz["C"], dtype=np.int32)
+        check(lib().mmw_batch_carry_map(self._h, src._h, int(inst), _pi(lmap), int(lmap.size), _pi(cmap), int(cmap.size)))
+        return lmap, cmap
 
     def iterate(self, n, randv=None, seeds=None):
         """randv: None (device Philox, `seeds` one per instance) or a list with, per instance, the (n_b, K, D) sketches of the

@@ -8,6 +8,7 @@ sweep loops (sim_script/journal_version/*: seeds x cell sizes, one `binary_searc
     online   = online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1)       # [{"Z", "probes", "z_vec", "remainder", "bler"}, ...]
     base     = baselines_many(batch_solver, Zs)                                        # [{"rand" / "mgain" / "masso": (z_vec, Z, remainder)}, ...]
     cmp      = compare_many(drops, nit=150, eta=0.04)                                  # [{"Z", "probes", "bler": {"mmw", "rand", "mgain", "masso"}}, ...]
+    resolved = online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=1.0)  # online_many's results plus "iters"; a re-solve per point
     greedy   = online_greedy_many(drops, n_points=11, step_us=1e6)                     # [{"Z", "z_vec", "remainder", "bler"}, ...]
 
 The iterations of every instance run in one launch per call.  The epilogue of a probe (X_half and the rounding) is chosen by
@@ -318,6 +319,97 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     finally:
         env.close()
         b.close()
+
+
+def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
+                        rank_radio=2, device=0, resolve_nit=None, carry=False, warm_fraction=1.0 / 3.0, timings=None, split=None, factor_split=None,
+                        row_split=None):
+    """`online_many` with a re-solve at every time point (NOT one of the reference's scripts, which solve once and re-round that
+    factor while the stations walk).  The start is `online_many`'s: the bisection on the drops' states, one more solve at the Z it
+    ends at with the same sketch seed, and point 0 is that factor rounded on the unmoved state.  Z stays at that Z throughout.
+    Every later point p, for all instances together: `BatchEnv.move`, the states fetched (`BatchEnv.state`), a new `BatchSolver` on
+    them at the Zs with the splits applied, `carry_from` the previous point's batch (carry=True; at p = 1 that is the first
+    solve's), `iterate` with sketches keyed by probe_seed(seed, i, 0xC0000 | p), `factor`, `round` with draws keyed by
+    probe_seed(seed, i, 0x80000 | p) (users left over drawn as in the search), `BatchEnv.evaluate`; the previous batch is closed
+    and every drop walks `step_us` microseconds.  Iterations per re-solve: `resolve_nit`, or when that is None
+    `warm_iterations(nit, warm_fraction)` with carry=True and `nit` with carry=False (a cold re-solve from the initial point).
+    carry=False is the default: measured on the sweep's mix, the carried re-solve's colourings were not better than a cold
+    re-solve's at the same iterations.
+    The drops are moved in place.  Returns `online_many`'s dictionaries plus "iters", the iterations behind every point's factor.
+    timings: a list that receives per point {"create_s" (move, states, the new batch), "carry_s", "iterate_s", "epilogue_s" (factor
+    and round), "evaluate_s", "step_s"}."""
+    B = len(drops)
+    for i, d in enumerate(drops):
+        if d.K > _lib.BATCH_EPILOGUE_MAX_K:
+            raise ValueError("online_resolve_many: instance %d has K = %d users, over the batch epilogue's limit %d" % (i, d.K, _lib.BATCH_EPILOGUE_MAX_K))
+    _check_warm(warm_fraction)
+    if resolve_nit is not None and int(resolve_nit) < 1:
+        raise ValueError("resolve_nit must be >= 1, got %r" % (resolve_nit,))
+    n_p = int(resolve_nit) if resolve_nit is not None else warm_iterations(nit, warm_fraction) if carry else int(nit)
+    steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
+    states = [d.state() for d in drops]
+    found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
+                        factor_split=factor_split, row_split=row_split)
+    Zs = [int(r["Z"]) for r in found]
+    out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
+            "bler": np.empty((n_points, drops[i].K)), "iters": [int(nit)] + [n_p] * (n_points - 1)} for i in range(B)]
+
+    def solver(sts, n):
+        b = _lib.BatchSolver(Zs, sts, n, eta, rank_radio=rank_radio, device=device)
+        try:
+            _split(b, split)
+            _row_split(b, row_split)
+            _factor_split(b, factor_split)
+        except Exception:
+            b.close()
+            raise
+        return b
+
+    prev = solver(states, nit)
+    env = None
+    try:
+        env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
+        prev.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
+        prev.factor()
+        for p in range(n_points):
+            t0 = time.perf_counter()
+            env.move([d.sta_locs for d in drops])
+            seeds = np.array([probe_seed(seed, i, 0x80000 | p) for i in range(B)], dtype=np.uint64)
+            if p == 0:
+                t1 = t2 = t3 = time.perf_counter()
+                z, rem, used = prev.round_env(env, nattempt, seeds)
+            else:
+                b = solver([env.state(i) for i in range(B)], n_p)
+                try:
+                    t1 = time.perf_counter()
+                    if carry:
+                        b.carry_from(prev)
+                    t2 = time.perf_counter()
+                    b.iterate(n_p, None, np.array([probe_seed(seed, i, 0xC0000 | p) for i in range(B)], dtype=np.uint64))
+                    t3 = time.perf_counter()
+                    b.factor()
+                    z, rem, used = b.round(nattempt, seeds)
+                except Exception:
+                    b.close()
+                    raise
+                prev.close()
+                prev = b
+            fin = [_finish(z, rem, used, i, Zs[i], int(seeds[i])) for i in range(B)]
+            t4 = time.perf_counter()
+            _, bler = env.evaluate([f[0] for f in fin], Zs)
+            for i in range(B):
+                out[i]["z_vec"][p], out[i]["remainder"][p], out[i]["bler"][p] = fin[i][0], fin[i][2], bler[i]
+            t5 = time.perf_counter()
+            for d, t in zip(drops, steps):
+                d.step_time(t, mob_spd_meter_s, resolution_us)
+            if timings is not None:
+                timings.append({"create_s": t1 - t0, "carry_s": t2 - t1, "iterate_s": t3 - t2, "epilogue_s": t4 - t3, "evaluate_s": t5 - t4,
+                                "step_s": time.perf_counter() - t5})
+        return out
+    finally:
+        if env is not None:
+            env.close()
+        prev.close()
 
 
 METHODS = ("rand", "mgain", "masso")  # the baselines of sim_all_bler.py:42-72 that run inside the batch, in its order

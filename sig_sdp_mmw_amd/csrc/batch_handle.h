@@ -1,7 +1,8 @@
 // Batched solver (mmw_batch_*): many small fp64 instances, one workgroup each (csrc/kernels_batch.h).  The handle holds a core
 // (batch_core.h: patterns, counters, the two arenas) and four parts by value, each with the state and the device buffers of one feature:
 // gap and split (batch_iterate.h), rows (batch_rows.h), epi (batch_epilogue.h), greedy (batch_gm.h), and sequences them.  Whatever a part holds that a new
-// run invalidates, it drops in its on_restart: reset and set_slots call those and name no field of a part.
+// run invalidates, it drops in its on_restart: reset and set_slots call those and name no field of a part.  Two entries work on a
+// pair of batches and stand below the handle: batch_export_into (an fp64 handle) and batch_carry (another batch, on moved states).
 #pragma once
 #include "batch_epilogue.h"
 #include "batch_gm.h"
@@ -276,5 +277,75 @@ inline int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {
     s->core.lblk_stale = false;
     s->core.iter = bt->core.iter[b];
     MMW_HIP(hipStreamSynchronize(s->core.st));
+    return MMW_OK;
+}
+// what mmw_batch_carry and mmw_batch_carry_map ask of one instance of the pair before either looks at its patterns
+inline int batch_carry_pair(const char* who, const mmw_batch* dst, const mmw_batch* src, int b) {
+    if (dst->core.H[b].K != src->core.H[b].K)
+        return fail(MMW_ERR_ARG, std::string(who) + ": instance " + std::to_string(b) + ": K = " + std::to_string(dst->core.H[b].K) + " here, K = " +
+                                     std::to_string(src->core.H[b].K) + " in the source (a carry keeps the users and moves them)");
+    return MMW_OK;
+}
+// mmw_batch_carry_map: the two index maps of one instance (BatchCore::carry_maps); host patterns only, so device -1 batches answer too
+inline int batch_carry_map(mmw_batch* dst, mmw_batch* src, int b, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc) {
+    MMW_TRY(dst->core.check_inst(b));
+    MMW_TRY(src->core.check_inst(b));
+    MMW_TRY(batch_carry_pair("mmw_batch_carry_map", dst, src, b));
+    const HostPattern& N = dst->core.H[b];
+    if (nl != N.nnzL() || nc != N.C())
+        return fail(MMW_ERR_ARG, "mmw_batch_carry_map: instance " + std::to_string(b) + ": wrong lengths " + std::to_string(nl) + ", " + std::to_string(nc) +
+                                     ", expected nnzL = " + std::to_string(N.nnzL()) + " and C = " + std::to_string(N.C()));
+    BatchCore::carry_maps(N, src->core.H[b], lmap, cmap);
+    return MMW_OK;
+}
+// mmw_batch_carry: (e_accu, L, X, Y) of `src`, a batch on the old states that has iterated, re-indexed onto `dst`, a batch on the new
+// states that has not (kernels_batch_carry.h).  Every refusal comes before anything is written.  An instance whose source has run
+// no iteration is left as creation made it (cold), as mmw_batch_set_slots_warm leaves one.  dst's counters do not change: its
+// iterations done stay 0, so a later mmw_batch_set_slots_warm still treats a carried instance that has not iterated as cold.
+inline int batch_carry(mmw_batch* dst, mmw_batch* src, const int32_t* take) {
+    const char* who = "mmw_batch_carry";
+    BatchCore& D = dst->core;
+    BatchCore& S = src->core;
+    if (dst == src) return fail(MMW_ERR_ARG, "mmw_batch_carry: the batch cannot carry from itself");
+    if (D.host_only || S.host_only) return fail(MMW_ERR_STATE, "mmw_batch_carry: host-only batch (created with device -1)");
+    if (D.device != S.device) return fail(MMW_ERR_ARG, "mmw_batch_carry: the source lives on device " + std::to_string(S.device) + ", this batch on device " + std::to_string(D.device));
+    if (D.B != S.B) return fail(MMW_ERR_ARG, "mmw_batch_carry: the source holds " + std::to_string(S.B) + " instances, this batch " + std::to_string(D.B));
+    std::vector<int> tk;
+    MMW_TRY(D.takers(who, take, tk));
+    for (int b : tk) {
+        MMW_TRY(batch_carry_pair(who, dst, src, b));
+        if (D.iter[b] != 0)
+            return fail(MMW_ERR_STATE, std::string(who) + ": instance " + std::to_string(b) + " has run " + std::to_string(D.iter[b]) + " iterations (carry into a batch that has not iterated)");
+    }
+    std::vector<int> go;
+    for (int b : tk)
+        if (S.iter[b] > 0) go.push_back(b);
+    if (go.empty()) return MMW_OK;
+    constexpr size_t DW = sizeof(BatchDesc) / sizeof(double), IW = sizeof(CarryItem) / sizeof(double);
+    static_assert(sizeof(CarryItem) % sizeof(double) == 0, "the staging buffer is one array of doubles");
+    const size_t n = go.size();
+    int64_t words = 0;  // int32 map entries of the call
+    for (int b : go) words += D.H[b].nnzL() + D.H[b].C();
+    const size_t w_src = 0, w_dst = w_src + DW * n, w_item = w_dst + DW * n, w_map = w_item + IW * n;
+    std::vector<double> stage(w_map + (size_t)((words + 1) / 2), 0.0);
+    int32_t* maps = reinterpret_cast<int32_t*>(stage.data() + w_map);
+    int64_t om = 0;
+    for (size_t t = 0; t < n; ++t) {
+        const int b = go[t];
+        const HostPattern& N = D.H[b];
+        std::memcpy(stage.data() + w_src + DW * t, &S.desc[b], sizeof(BatchDesc));
+        std::memcpy(stage.data() + w_dst + DW * t, &D.desc[b], sizeof(BatchDesc));
+        const CarryItem it{om, om + N.nnzL()};
+        std::memcpy(stage.data() + w_item + IW * t, &it, sizeof it);
+        BatchCore::carry_maps(N, S.H[b], maps + it.o_lmap, maps + it.o_cmap);
+        om += N.nnzL() + N.C();
+    }
+    MMW_HIP(hipSetDevice(D.device));
+    MMW_HIP(hipStreamSynchronize(S.st));  // the source's iterations have landed
+    MMW_TRY(D.rl.upload(stage, D.st));
+    hipLaunchKernelGGL(k_batch_carry, dim3((unsigned)n), dim3(BATCH_THREADS), 0, D.st, (const BatchDesc*)(D.rl.p + w_src), (const BatchDesc*)(D.rl.p + w_dst),
+                       (const CarryItem*)(D.rl.p + w_item), (const int*)(D.rl.p + w_map), (const double*)S.fa.p, D.fa.p);
+    MMW_HIP(hipGetLastError());
+    MMW_HIP(hipStreamSynchronize(D.st));
     return MMW_OK;
 }

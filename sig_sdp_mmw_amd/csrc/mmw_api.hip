@@ -178,6 +178,10 @@ int mmw_batch_destroy(mmw_batch* b) { return guarded("mmw_batch", [&]() -> int {
 int mmw_batch_sizes(mmw_batch* b, int32_t inst, int64_t out[10]) { return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->sizes(inst, out); }); }
 int mmw_batch_set_slots(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit, false); }); }
 int mmw_batch_set_slots_warm(mmw_batch* b, const int32_t* Z, int32_t nit) { return entry("mmw_batch", !b || !Z, "null pointer", [&] { return b->set_slots(Z, nit, true); }); }
+int mmw_batch_carry(mmw_batch* dst, mmw_batch* src, const int32_t* take) { return entry("mmw_batch", !dst || !src, "null batch handle", [&] { return batch_carry(dst, src, take); }); }
+int mmw_batch_carry_map(mmw_batch* dst, mmw_batch* src, int32_t inst, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc) {
+    return entry("mmw_batch", !dst || !src || (!lmap && nl) || (!cmap && nc), "null pointer", [&] { return batch_carry_map(dst, src, inst, lmap, nl, cmap, nc); });
+}
 int mmw_batch_reset(mmw_batch* b, int32_t nit) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->reset(nit); }); }
 int mmw_batch_set_eta(mmw_batch* b, const double* eta) { return entry("mmw_batch", !b || !eta, "null pointer", [&] { return b->set_eta(eta); }); }
 int mmw_batch_set_expm(mmw_batch* b, int max_order, double tol) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_expm(max_order, tol); }); }
