@@ -76,6 +76,10 @@ enum mmw_field {
                              (mmw_batch_set_row_split); kernel launches enqueued; of which idle: every workgroup past its instance's
                              schedule or with all its columns stopped (path 2 only); workgroups of the largest launch}; zeros before
                              the first call; batches only */
+    MMW_F_FACTOR_ROWNORM = 23, /* [K] after mmw_batch_factor_spectral: every user's row norm of the K x Z eigenvector block BEFORE its rows
+                             were normalised (0: the row is exactly zero and stayed so).  The top eigenvectors are localised: a user with
+                             a tiny norm here has a row of amplified rounding noise in MMW_F_FACTOR.  MMW_ERR_STATE on any other factor;
+                             batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -521,10 +525,33 @@ int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t att
  * with one rule of its own: every row has norm 1, so the rounding's visiting order (descending norm, sdp_solver.py:51) is one tie
  * over all users, and the rounding visits such a block in index order (ties to the lower index) without forming the norms, whose
  * last bits would decide the order otherwise.  A factor of mmw_batch_factor is rounded exactly as before.
+ *
+ * mmw_batch_factor_spectral: spectral_sdp_solver.run_with_state (sim_src/alg/sdp_solver.py:165-185) as the RESIDENT FACTOR of every
+ * taking instance (csrc/kernels_batch_spectral.h): the Laplacian L = D - W of the state the batch was built from, W = S_gain +
+ * S_gain^T with the diagonal zeroed (the state's CSR is taken as canonical: no entry stored twice) and D_ii = sum_j W_ij, its Z[b]
+ * eigenvectors of largest eigenvalue as a K x Z block, columns in ascending eigenvalue (eigsh's order), every row of the block divided
+ * by its norm (:182).  The reference takes eigsh(k = Z, which = 'LM', tol = 1e-5); here the eigenvectors come from mmw_batch_factor's
+ * dense one-sided Jacobi on the rows of L, to rounding error: L is positive semidefinite, so the row norms at convergence are the
+ * eigenvalues.  L is built without atomics and exactly symmetric, every sum in a fixed order: an instance's block is bitwise
+ * independent of its batch neighbours and of `take`, and the single launch and the chain of mmw_batch_set_factor_split give the same
+ * bits.  The sign of a column is arbitrary but deterministic (comparisons belong on the projector V V^T).  take[B]: as in mmw_batch_factor.  Z[B]: NULL = each instance's own slot count; otherwise
+ * 1 <= Z[b] <= K (eigsh itself refuses k >= K; the Jacobi does not, and the one-AP shape K = 2, Z = 2 rounds).  The eigenvector of
+ * eigenvalue 0 is the one a row norm cannot carry: its row ends as rounding noise or as exact zeros (a zero-norm row gives a zero
+ * column); it ranks last and enters the block only at Z = K.  A user whose row of the K x Z block is exactly zero keeps a zero row
+ * -- an isolated user is one; the reference divides by zero there.  Users whose row is tiny before the division (the top eigenvectors
+ * of these Laplacians are localised: norms down to 1e-14) carry amplified rounding noise, here as in the reference.  No iteration
+ * needs to have run.  As with mmw_batch_factor_random the work buffers are laid out anew (earlier factors are gone).  Refused by name
+ * with MMW_ERR_ARG before anything runs: a taking instance with K > MMW_BATCH_EPILOGUE_MAX_K, or Z[b] outside [1, K]; a host-only
+ * batch answers MMW_ERR_STATE.  An instance still rotating at the cap of 30 sweeps keeps its block and is named on stderr as by
+ * mmw_batch_factor.  mmw_batch_round, mmw_batch_round_env, mmw_batch_round_randv, MMW_F_FACTOR ([K * Z], row-major),
+ * MMW_F_FACTOR_INFO ({sweeps, largest |cos| of a row pair met in the last sweep, Z, lambda_Z, lambda_Z+1 (0 at Z = K)}) and
+ * MMW_F_FACTOR_CALL then work on it, and MMW_F_FACTOR_ROWNORM hands out the users' row norms before the division; the rows being unit (or zero), the rounding visits the users in index order as for
+ * mmw_batch_factor_random.
  */
 int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
                  int32_t* rem_out, double* key_out);
 int mmw_batch_factor_random(mmw_batch* b, const int32_t* take, const uint64_t* seeds);
+int mmw_batch_factor_spectral(mmw_batch* b, const int32_t* take, const int32_t* Z);
 
 /*
  * The generator and the scorer for many small instances (csrc/kernels_batch_env.h), one workgroup per instance: the state of

@@ -20,6 +20,7 @@ F_Y, F_E_ACCU, F_E_THIS, F_LVAL, F_XVAL, F_XAVG, F_YAVG, F_XHALF, F_SKETCH = ran
 F_S_SUM, F_NORM_H, F_ST_DATA, F_PHASE_US, F_EXPM_INFO, F_FACTOR, F_KERNEL_US, F_BLOCKING, F_SPMM_KIND, F_E_MAX, F_DUAL_INFO = range(9, 20)
 F_FACTOR_INFO = 20
 F_FACTOR_CALL = 21
+F_FACTOR_ROWNORM = 23
 F_SPLIT_CALL = 22
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
@@ -36,7 +37,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_sketch", "mmw_batch_export", "mmw_batch_set_gap", "mmw_batch_read_gap", "mmw_batch_factor", "mmw_batch_round",
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
-           "mmw_batch_factor_random", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
+           "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map"]
 
 
@@ -137,6 +138,7 @@ def lib():
     L.mmw_batch_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
     L.mmw_batch_env_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
     L.mmw_batch_factor_random.argtypes = [C.c_void_p, p_i32, C.POINTER(C.c_uint64)]
+    L.mmw_batch_factor_spectral.argtypes = [C.c_void_p, p_i32, p_i32]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -798,6 +800,11 @@ class BatchSolver(_Handle):
         v = self.read(inst, F_FACTOR_INFO, 5)
         return {"sweeps": int(v[0]), "max_cos": float(v[1]), "rank": int(v[2]), "sigma_rank": float(v[3]), "sigma_next": float(v[4])}
 
+    def factor_row_norms(self, inst):
+        """After `factor_spectral`: every user's row norm of the eigenvector block before its rows were normalised (MMW_F_FACTOR_ROWNORM).
+        The top eigenvectors are localised: users with a tiny norm here carry amplified rounding noise in `read_factor`."""
+        return self.read(inst, F_FACTOR_ROWNORM, self.sizes[inst]["K"])
+
     def read_factor(self, inst):
         """X_half (K, rank) of the instance's last `factor`, columns in ascending singular value."""
         rank = self.factor_info(inst)["rank"]
@@ -829,6 +836,19 @@ class BatchSolver(_Handle):
         All its rows have norm 1, so the rounding visits the users of such a block in index order (include/mmw_hip.h)."""
         t, _ = self._take(take)
         check(lib().mmw_batch_factor_random(self._h, _opt_pi(t), _pu(_u64(seeds, self.B))))
+
+    def factor_spectral(self, Zs=None, take=None):
+        """spectral_sdp_solver.run_with_state (sdp_solver.py:165-185) of every taking instance on the state the batch was built from:
+        its resident factor becomes the K x Z block of the Laplacian's Z eigenvectors of largest eigenvalue (columns in ascending
+        eigenvalue, signs arbitrary but deterministic), every row divided by its norm; a row that is exactly zero (an isolated user)
+        stays zero.  Zs: one per instance (None: each instance's own slot count), 1 <= Z <= K.  `round` / `round_env` / `read_factor` /
+        `factor_info` ({sweeps, max_cos, rank = Z, sigma_rank = lambda_Z, sigma_next = lambda_Z+1}) then work on it; the rounding visits
+        the users in index order, as for `factor_random` (include/mmw_hip.h)."""
+        t, _ = self._take(take)
+        z = None if Zs is None else _i32(Zs)
+        if z is not None and z.size != self.B:
+            raise MMWError("factor_spectral: one Z per instance")
+        check(lib().mmw_batch_factor_spectral(self._h, _opt_pi(t), _opt_pi(z)))
 
     def gm(self, kind, Zs, nattempt=1, take=None, keys=False):
         """gm.MAX_GAIN.run (kind 0) / gm.MAX_ASSO.run (kind 1) in the stable order for every taking instance's own state, one launch

@@ -413,6 +413,7 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
 
 
 METHODS = ("rand", "mgain", "masso")  # the baselines of sim_all_bler.py:42-72 that run inside the batch, in its order
+OPT_IN_METHODS = ("spectral",)  # what baselines_many also takes when it is named: spectral_sdp_solver (sdp_solver.py:165-185)
 
 
 def _fill(slot, rem, high, seed):
@@ -431,6 +432,9 @@ def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, natte
     states it was built from) or a `(BatchSolver, BatchEnv)` pair (the states the environment holds: `round_env`, `BatchEnv.gm`).
     Zs: one slot count per instance; the solver's slot counts must be these for "rand" (its embedding is K x Z rank_radio).  Users
     left over are drawn from a generator keyed by the same seed.  The resident factors are replaced by "rand".
+    methods may also name "spectral" (OPT_IN_METHODS; spectral_sdp_solver: `factor_spectral(Zs)` then `round`, keyed by
+    probe_seed(seed, i, 0x40000 | 3)): the embedding is that of the states the batch was built from, also when the rounding goes
+    against an environment; it replaces the resident factors too.
     Returns per instance {method: (z_vec float64[K], Z, remainder)}."""
     b, env = source if isinstance(source, tuple) else (source, None)
     B = b.B
@@ -439,14 +443,17 @@ def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, natte
         raise ValueError("baselines_many: one slot count per instance")
     out = [{} for _ in range(B)]
     for name in methods:
-        if name not in METHODS:
-            raise ValueError("baselines_many: method must be one of %s, got %r" % (METHODS, name))
-        m = METHODS.index(name)
+        if name not in METHODS + OPT_IN_METHODS:
+            raise ValueError("baselines_many: method must be one of %s, got %r" % (METHODS + OPT_IN_METHODS, name))
+        m = (METHODS + OPT_IN_METHODS).index(name)
         seeds = np.array([probe_seed(seed, i, 0x40000 | m) for i in range(B)], dtype=np.uint64)
-        if name == "rand":
+        if name in ("rand", "spectral"):
             if any(b.sizes[i]["Z"] != Zs[i] for i in range(B)):
                 raise ValueError("baselines_many: the batch's slot counts are not Zs (set_slots first)")
-            b.factor_random(seeds)
+            if name == "rand":
+                b.factor_random(seeds)
+            else:
+                b.factor_spectral(Zs)
             z, rem, used = b.round(nattempt_round, seeds) if env is None else b.round_env(env, nattempt_round, seeds)
             for i in range(B):
                 out[i][name] = _finish(z, rem, used, i, Zs[i], int(seeds[i]))

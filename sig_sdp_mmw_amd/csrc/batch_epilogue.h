@@ -74,12 +74,18 @@ struct BatchEpilogue {
             f.o_ord = oi; oi = a32(oi + K);
             launch.push_back(f);
         }
+        return run_factor(c, tk, fd, launch, of, oi, xavg);
+    }
+    // The Jacobi of a call for the descriptors laid out by mmw_batch_factor or mmw_batch_factor_spectral: the work buffers, the single
+    // launch or the split chain, the records and the stderr line at the sweep cap.
+    int run_factor(const BatchCore& c, const std::vector<int>& tk, std::vector<FactorDesc>& fd, const std::vector<FactorDesc>& launch, int64_t of,
+                   int64_t oi, const double* const* xavg) {
         on_restart();  // the buffers are laid out anew: earlier factors are gone whatever happens below
         MMW_HIP(hipSetDevice(c.device));
         MMW_TRY(ew.alloc((size_t)of));
         MMW_TRY(ei.alloc((size_t)oi));
         for (int b : tk)
-            if (fd[b].src_work) MMW_TRY(copy_h2d(ew.p + fd[b].o_src, xavg[b], (size_t)fd[b].nnzL * sizeof(double), c.st));
+            if (xavg && fd[b].src_work) MMW_TRY(copy_h2d(ew.p + fd[b].o_src, xavg[b], (size_t)fd[b].nnzL * sizeof(double), c.st));
         MMW_TRY(d_fdesc.alloc(launch.size()));
         MMW_TRY(copy_h2d(d_fdesc.p, launch.data(), launch.size() * sizeof(FactorDesc), c.st));
         bool split = false;
@@ -87,7 +93,7 @@ struct BatchEpilogue {
         if (split) {
             MMW_TRY(factor_split(c, tk, launch));
         } else {
-            hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, c.ia.p, c.fa.p, ew.p, ei.p);
+            hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, c.ia.p, c.fa.p, ew.p, ei.p, rs_i.p, rs_f.p);
             fs.call[0] = 0.0; fs.call[1] = 1.0; fs.call[2] = 0.0; fs.call[3] = (double)launch.size();
         }
         MMW_HIP(hipGetLastError());
@@ -124,7 +130,8 @@ struct BatchEpilogue {
         MMW_TRY(fs.d_items.upload(items, c.st));
         MMW_TRY(fs.slab.alloc((size_t)nslot * FSPLIT_SLOT));
         MMW_TRY(fs.rec.alloc((size_t)n * FSPLIT_REC));
-        hipLaunchKernelGGL(k_batch_factor_head, dim3((unsigned)n), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, fs.d_spans.p, c.ia.p, c.fa.p, ew.p, fs.slab.p, fs.rec.p);
+        hipLaunchKernelGGL(k_batch_factor_head, dim3((unsigned)n), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, fs.d_spans.p, c.ia.p, c.fa.p, ew.p, fs.slab.p, fs.rec.p,
+                           rs_i.p, rs_f.p);
         int64_t launches = 1, sweeps = 0;
         size_t widest = std::max((size_t)n, items.size());
         std::vector<char> live((size_t)n, 1);
@@ -159,6 +166,40 @@ struct BatchEpilogue {
         fs.call[0] = 1.0; fs.call[1] = (double)launches; fs.call[2] = (double)sweeps; fs.call[3] = (double)widest;
         return MMW_OK;
     }
+    // spectral_sdp_solver.run_with_state (sdp_solver.py:165-185): the row-normalised top-Z eigenvector block of the state's Laplacian as
+    // the resident factor, rank Z (kernels_batch_spectral.h); the Jacobi, its split and its records are mmw_batch_factor's
+    int factor_spectral(const BatchCore& c, const int32_t* take, const int32_t* Z) {
+        if (c.host_only) return BatchCore::host_only_batch();
+        std::vector<int> tk;
+        MMW_TRY(c.takers("mmw_batch_factor_spectral", take, tk));
+        for (int b : tk) {
+            const BatchDesc& d = c.desc[b];
+            const std::string who = "mmw_batch_factor_spectral: instance " + std::to_string(b);
+            if (d.K > EPI_MAX_K) return fail(MMW_ERR_ARG, who + ": K = " + std::to_string(d.K) + " exceeds the epilogue limit " + std::to_string(EPI_MAX_K) + " (spectral_sdp_solver takes it on the host)");
+            const int z = Z ? Z[b] : d.Z;
+            if (z < 1 || z > d.K) return fail(MMW_ERR_ARG, who + ": Z = " + std::to_string(z) + " must be in [1, K = " + std::to_string(d.K) + "]");
+        }
+        MMW_HIP(hipSetDevice(c.device));
+        MMW_TRY(round_lists(c));
+        std::vector<FactorDesc> fd(c.B, FactorDesc{});
+        std::vector<FactorDesc> launch;
+        int64_t of = a32((int64_t)tk.size() * EPI_INFO_STRIDE), oi = 0, ninfo = 0;
+        for (int b : tk) {
+            FactorDesc& f = fd[b];
+            const int64_t K = c.desc[b].K;
+            f.kind = 1; f.unit_rows = 1; f.div = 1.0;
+            f.K = (int)K; f.rank = Z ? Z[b] : c.desc[b].Z; f.cap = EPI_SWEEP_CAP;
+            f.s_soptr = rlists[b].soptr; f.s_soidx = rlists[b].soidx; f.s_sodata = rlists[b].sodata;
+            f.o_info = EPI_INFO_STRIDE * ninfo++;
+            f.o_A = of; of = a32(of + K * K);
+            f.o_fac = of; of = a32(of + K * f.rank);
+            f.o_nrm = of; of = a32(of + K);
+            f.o_rown = of; of = a32(of + K);
+            f.o_ord = oi; oi = a32(oi + K);
+            launch.push_back(f);
+        }
+        return run_factor(c, tk, fd, launch, of, oi, nullptr);
+    }
     // rand_sdp_solver.run_with_state (sdp_solver.py:109-114): the instance's sketch of (seed, iteration 0) as its resident factor, rank D
     int factor_random(const BatchCore& c, const int32_t* take, const uint64_t* seeds) {
         if (c.host_only) return BatchCore::host_only_batch();
@@ -188,14 +229,17 @@ struct BatchEpilogue {
         fdesc = std::move(fd);
         return MMW_OK;
     }
-    // MMW_F_FACTOR / MMW_F_FACTOR_INFO of the instance's resident factor
+    // MMW_F_FACTOR / MMW_F_FACTOR_INFO / MMW_F_FACTOR_ROWNORM of the instance's resident factor
     int read(const BatchCore& c, int b, int which, double* out, int64_t n) {
         if (!has_factor(b)) return no_factor("mmw_batch_read_f64", b);
         const FactorDesc& f = fdesc[b];
-        const int64_t len = which == MMW_F_FACTOR ? (int64_t)f.K * f.rank : EPI_INFO;
+        if (which == MMW_F_FACTOR_ROWNORM && f.kind != 1)
+            return fail(MMW_ERR_STATE, "mmw_batch_read_f64: instance " + std::to_string(b) + ": its factor is not a spectral one (mmw_batch_factor_spectral)");
+        const int64_t len = which == MMW_F_FACTOR ? (int64_t)f.K * f.rank : which == MMW_F_FACTOR_ROWNORM ? (int64_t)f.K : EPI_INFO;
         if (n != len) return fail(MMW_ERR_ARG, "mmw_batch_read_f64: wrong length " + std::to_string(n) + ", expected " + std::to_string(len));
         MMW_HIP(hipSetDevice(c.device));
-        return copy_d2h(out, ew.p + (which == MMW_F_FACTOR ? f.o_fac : f.o_info), (size_t)len * sizeof(double), c.st);
+        const int64_t o = which == MMW_F_FACTOR ? f.o_fac : which == MMW_F_FACTOR_ROWNORM ? f.o_rown : f.o_info;
+        return copy_d2h(out, ew.p + o, (size_t)len * sizeof(double), c.st);
     }
     // the rounding lists of the state the batch was built from, all instances, once
     int round_lists(const BatchCore& c) {

@@ -193,6 +193,7 @@ struct mmw_batch {
                 return read_dev(d.o_R, KD, out, n);
             case MMW_F_EXPM_INFO: return read_dev(d.o_info, 4, out, n);
             case MMW_F_FACTOR:
+            case MMW_F_FACTOR_ROWNORM:
             case MMW_F_FACTOR_INFO: return epi.read(core, b, which, out, n);
             default: return fail(MMW_ERR_ARG, "mmw_batch_read_f64: field not held by a batch");
         }
@@ -230,6 +231,7 @@ struct mmw_batch {
     int set_factor_split(const int32_t* p) { return epi.set_split(core, p); }
     int factor(const int32_t* take, const int32_t* rank, const double* const* xavg) { return epi.factor(core, take, rank, xavg); }
     int factor_random(const int32_t* take, const uint64_t* seeds) { return epi.factor_random(core, take, seeds); }
+    int factor_spectral(const int32_t* take, const int32_t* Z) { return epi.factor_spectral(core, take, Z); }
     int round(const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out,
               const BatchEpilogue::RoundSource* src = nullptr) {
         return epi.round(core, take, nattempt, stop_at_first, seeds, z_out, rem_out, used_out, src);

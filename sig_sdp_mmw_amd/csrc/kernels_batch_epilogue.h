@@ -25,6 +25,7 @@
 #pragma once
 #include "../../include/mmw_hip.h"
 #include "kernels_batch.h"
+#include "kernels_batch_spectral.h"
 
 namespace mmw {
 
@@ -44,6 +45,9 @@ struct FactorDesc {
     int64_t o_src;          // [nnzL] values on the pattern
     int64_t o_A, o_fac, o_nrm, o_info;  // fp64 work: K x K, K x rank, K, EPI_INFO
     int64_t o_ord;                      // int32 work: rows by descending norm
+    int kind;                           // 0: X_half of Xbar; 1: the spectral block of the state's Laplacian (kernels_batch_spectral.h)
+    int64_t s_soptr, s_soidx, s_sodata;  // kind 1: the state's rounding lists (S_gain without its diagonal), int32 / fp64
+    int64_t o_rown;                      // kind 1, fp64 work: K, the users' row norms of the block before the division
 };
 
 // All sweeps of the one-sided Jacobi on the rows of A (K x K, row-major), NE = elements of a row per lane.
@@ -137,7 +141,8 @@ __device__ __forceinline__ void epi_jacobi(double* A, int K, int cap, int* s_rot
 }
 
 __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor(const FactorDesc* __restrict__ descs, const int* __restrict__ ia,
-                                                                const double* __restrict__ fa, double* ew, int* __restrict__ ei) {
+                                                                const double* __restrict__ fa, double* ew, int* __restrict__ ei,
+                                                                const int* __restrict__ si, const double* __restrict__ sf) {
     const FactorDesc d = descs[blockIdx.x];
     __shared__ int s_rot[BATCH_WAVES];
     __shared__ double s_cos[BATCH_WAVES];
@@ -150,12 +155,16 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor(const FactorDesc
     double* fac = ew + d.o_fac;
     double* nrm = ew + d.o_nrm;
     int* ord = ei + d.o_ord;
-    // ---- Xbar, dense (mmw.py:201, 213)
-    const size_t KK = (size_t)K * K;
-    for (size_t i = tid; i < KK; i += NT) A[i] = 0.0;
-    __syncthreads();
-    for (int e = tid; e < d.nnzL; e += NT) A[(size_t)lrow[e] * K + col[e]] = src[e] / d.div;
-    __syncthreads();
+    if (d.kind == 1) {  // (workgroup-uniform) the Laplacian of the state instead of Xbar
+        spectral_head(K, si + d.s_soptr, si + d.s_soidx, sf + d.s_sodata, A);
+    } else {
+        // ---- Xbar, dense (mmw.py:201, 213)
+        const size_t KK = (size_t)K * K;
+        for (size_t i = tid; i < KK; i += NT) A[i] = 0.0;
+        __syncthreads();
+        for (int e = tid; e < d.nnzL; e += NT) A[(size_t)lrow[e] * K + col[e]] = src[e] / d.div;
+        __syncthreads();
+    }
     // ---- rows made orthogonal
     int sweeps = 0;
     double lastcos = 0.0;
@@ -185,12 +194,16 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor(const FactorDesc
     }
     __syncthreads();
     // ---- X_half[K, rank] = U sqrt(S) (mmw.py:215-216), columns in ascending sigma as svds returns them; a row of norm 0 gives a zero column
-    const size_t KR = (size_t)K * rank;
-    for (size_t idx = tid; idx < KR; idx += NT) {
-        const int i = (int)(idx / rank), j = (int)(idx % rank);
-        const int row = ord[rank - 1 - j];
-        const double nv = nrm[row];
-        fac[idx] = nv > 0.0 ? A[(size_t)row * K + i] / sqrt(nv) : 0.0;
+    if (d.kind == 1) {  // the eigenvector block, rows normalised, instead of U sqrt(S)
+        spectral_tail(K, rank, A, nrm, ord, fac, ew + d.o_rown);
+    } else {
+        const size_t KR = (size_t)K * rank;
+        for (size_t idx = tid; idx < KR; idx += NT) {
+            const int i = (int)(idx / rank), j = (int)(idx % rank);
+            const int row = ord[rank - 1 - j];
+            const double nv = nrm[row];
+            fac[idx] = nv > 0.0 ? A[(size_t)row * K + i] / sqrt(nv) : 0.0;
+        }
     }
     if (tid == 0) {
         double* info = ew + d.o_info;

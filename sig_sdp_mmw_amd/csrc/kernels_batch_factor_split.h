@@ -6,6 +6,8 @@
 //   k_batch_factor_round   one launch per tournament round r, one workgroup per item {instance, first pair, pair count}
 //   k_batch_factor_sweep   one workgroup per instance after the last round of a sweep: the items' {rotations, |cos|} into the record
 //   k_batch_factor_tail    one workgroup per instance: row norms, the rank cut by counting, X_half, MMW_F_FACTOR_INFO's record
+// (FactorDesc::kind == 1, mmw_batch_factor_spectral: the head builds the state's Laplacian and the tail the row-normalised eigenvector
+// block instead, kernels_batch_spectral.h; the rounds and the sweep records do not know the difference)
 //
 // Why the bits do not change.  A round of the tournament is ceil(K / 2) disjoint row pairs; a pair is reduced and rotated by one
 // wave -- per-lane sums in ascending column order, the fixed-order wave reduction -- so what it computes does not depend on the wave
@@ -47,7 +49,8 @@ inline int factor_item_count(int K, int parts) {
 // ---- Xbar, dense (k_batch_factor, same statements); the instance's slab slots and its sweep record start at zero
 __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor_head(const FactorDesc* __restrict__ descs, const FactorSpan* __restrict__ spans,
                                                                      const int* __restrict__ ia, const double* __restrict__ fa, double* ew,
-                                                                     double* __restrict__ slab, double* __restrict__ rec) {
+                                                                     double* __restrict__ slab, double* __restrict__ rec,
+                                                                     const int* __restrict__ si, const double* __restrict__ sf) {
     const FactorDesc d = descs[blockIdx.x];
     const FactorSpan sp = spans[blockIdx.x];
     const int tid = (int)threadIdx.x, NT = (int)blockDim.x;
@@ -56,10 +59,14 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor_head(const Facto
     const int* __restrict__ col = ia + d.o_col;
     const double* src = (d.src_work ? ew : fa) + d.o_src;
     double* A = ew + d.o_A;
-    const size_t KK = (size_t)K * K;
-    for (size_t i = tid; i < KK; i += NT) A[i] = 0.0;
-    __syncthreads();
-    for (int e = tid; e < d.nnzL; e += NT) A[(size_t)lrow[e] * K + col[e]] = src[e] / d.div;
+    if (d.kind == 1) {  // (workgroup-uniform) the Laplacian of the state instead of Xbar
+        spectral_head(K, si + d.s_soptr, si + d.s_soidx, sf + d.s_sodata, A);
+    } else {
+        const size_t KK = (size_t)K * K;
+        for (size_t i = tid; i < KK; i += NT) A[i] = 0.0;
+        __syncthreads();
+        for (int e = tid; e < d.nnzL; e += NT) A[(size_t)lrow[e] * K + col[e]] = src[e] / d.div;
+    }
     for (int i = tid; i < sp.nitems * FSPLIT_SLOT; i += NT) slab[(size_t)sp.slot0 * FSPLIT_SLOT + i] = 0.0;
     if (tid < FSPLIT_REC) rec[(size_t)blockIdx.x * FSPLIT_REC + tid] = 0.0;
 }
@@ -226,12 +233,16 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_factor_tail(const Facto
         ord[r] = k;
     }
     __syncthreads();
-    const size_t KR = (size_t)K * rank;
-    for (size_t idx = tid; idx < KR; idx += NT) {
-        const int i = (int)(idx / rank), j = (int)(idx % rank);
-        const int row = ord[rank - 1 - j];
-        const double nv = nrm[row];
-        fac[idx] = nv > 0.0 ? A[(size_t)row * K + i] / sqrt(nv) : 0.0;
+    if (d.kind == 1) {  // the eigenvector block, rows normalised, instead of U sqrt(S)
+        spectral_tail(K, rank, A, nrm, ord, fac, ew + d.o_rown);
+    } else {
+        const size_t KR = (size_t)K * rank;
+        for (size_t idx = tid; idx < KR; idx += NT) {
+            const int i = (int)(idx / rank), j = (int)(idx % rank);
+            const int row = ord[rank - 1 - j];
+            const double nv = nrm[row];
+            fac[idx] = nv > 0.0 ? A[(size_t)row * K + i] / sqrt(nv) : 0.0;
+        }
     }
     if (tid == 0) {
         double* info = ew + d.o_info;

@@ -218,6 +218,9 @@ int mmw_batch_round_randv(mmw_batch* b, int32_t inst, uint64_t seed, int32_t att
 int mmw_batch_factor_random(mmw_batch* b, const int32_t* take, const uint64_t* seeds) {
     return entry("mmw_batch", !b || !seeds, "null pointer", [&] { return b->factor_random(take, seeds); });
 }
+int mmw_batch_factor_spectral(mmw_batch* b, const int32_t* take, const int32_t* Z) {
+    return entry("mmw_batch", !b, "null batch handle", [&] { return b->factor_spectral(take, Z); });
+}
 int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
                  int32_t* rem_out, double* key_out) {
     return entry("mmw_batch", !b || !Z || !z_out || !zz_out || !rem_out, "null pointer",

@@ -11,6 +11,7 @@ of users left unassigned from the global NumPy stream, in the reference's order
 import numpy as np
 
 from . import _lib
+from .stats import STATS_OBJECT
 
 
 class sdp_solver:
@@ -155,3 +156,60 @@ class rand_sdp_solver(sdp_solver):
         randv = np.random.randn(K, Z * self.rank_radio)
         randv = randv / np.linalg.norm(randv, axis=1, keepdims=True)
         return True, randv
+
+
+def spectral_laplacian(S_gain):
+    """The reference's Laplacian (sdp_solver.py:173-176): D - W of W = S_gain + S_gain^T with the diagonal zeroed, sparse."""
+    import scipy.sparse
+    import scipy.sparse.csgraph
+    W = scipy.sparse.csr_matrix(S_gain + S_gain.transpose())
+    W.setdiag(0)
+    W.eliminate_zeros()
+    return scipy.sparse.csgraph.laplacian(W, normed=False)
+
+
+class spectral_sdp_solver(STATS_OBJECT, rand_sdp_solver):
+    """The reference's spectral embedding (sdp_solver.py:165-185): the Z eigenvectors of largest eigenvalue of the Laplacian of
+    S_gain + S_gain^T (diagonal zeroed) as a K x Z block, rows normalised, handed to the shared rounding.  Same positional
+    constructor; `run_with_state` logs `spectral_problem_setup` and `spectral_solve` rows [Z, K, microseconds] like the reference.
+
+    K <= 1024 and device >= 0: a batch of one on the device (`BatchSolver.factor_spectral`: a dense Jacobi instead of the reference's
+    `eigsh(tol=1e-5)`, eigenvectors to rounding error).  device = -1 or K > 1024: SciPy's `eigsh` on the host, the reference's own
+    expression.  Column signs are arbitrary in both.  A user whose row of the block is exactly zero (an isolated user) keeps a zero
+    row on the device; the host path divides by zero there, like the reference.
+
+    The rows are unit, so the rounding visits the users in index order through `rand_sdp_solver.index_ordered`, as for the random
+    embedding (and as `BatchSolver.round` does on a spectral factor).  A `DeviceState` is read through its host copy."""
+
+    def __init__(self, nit=100, rank_radio=2, alpha=1., *, device=0):
+        sdp_solver.__init__(self, nit=nit, rank_radio=rank_radio, alpha=alpha)
+        self.device = int(device)
+        if self.device >= 0:
+            self._device_index = self.device
+
+    def run_with_state(self, bs_iteration, Z, state):
+        ps_tic = self._get_tic()
+        Z = int(Z)
+        if isinstance(state, _lib.DeviceState):
+            state = state.host()
+        K = state[0].shape[0]
+        on_device = self.device >= 0 and K <= _lib.BATCH_EPILOGUE_MAX_K
+        if on_device:
+            b = _lib.BatchSolver([2], [state], 1, 0.1, rank_radio=1, device=self.device)  # (its own slot count plays no part: Z goes to the factor)
+        else:
+            Laplacian = spectral_laplacian(state[0])
+        self._add_np_log("spectral_problem_setup", bs_iteration, np.array([Z, K, self._get_tim(ps_tic)]))
+
+        solving_tic = self._get_tic()
+        if on_device:
+            try:
+                b.factor_spectral([Z])
+                normed_eigvecs = b.read_factor(0)
+            finally:
+                b.close()
+        else:
+            import scipy.sparse.linalg
+            _, eigvecs = scipy.sparse.linalg.eigsh(Laplacian, k=Z, which='LM', return_eigenvectors=True, tol=1e-5)
+            normed_eigvecs = eigvecs / np.linalg.norm(eigvecs, axis=1, keepdims=True)
+        self._add_np_log("spectral_solve", bs_iteration, np.array([Z, K, self._get_tim(solving_tic)]))
+        return True, normed_eigvecs
