@@ -80,6 +80,10 @@ enum mmw_field {
                              were normalised (0: the row is exactly zero and stayed so).  The top eigenvectors are localised: a user with
                              a tiny norm here has a row of amplified rounding noise in MMW_F_FACTOR.  MMW_ERR_STATE on any other factor;
                              batches only */
+    MMW_F_HEAD_CALL = 24,   /* [4]    the last mmw_batch_iterate of a batch, kept on the host, the same for every instance: {on: 1 while the
+                             head split ran (mmw_batch_set_head_split), else 0; launches of the head path's own kernels (k_batch_head_*)
+                             enqueued; workgroups of the widest of them; 0}; zeros before the first call and with the head split off;
+                             batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -418,6 +422,29 @@ int mmw_batch_set_split(mmw_batch* b, const int32_t* parts);
 #define MMW_BATCH_MAX_ROW_PARTS 64
 int mmw_batch_set_row_split(mmw_batch* b, const int32_t* rows);
 int mmw_batch_row_ranges(mmw_batch* b, int32_t inst, int32_t rows, int32_t* out);
+/*
+ * The head and the plan over workgroups (csrc/kernels_batch_head.h).  Both splits above leave everything in front of the exponential --
+ * averaging, both DUAL passes, the softmax, the LOSS update and the plan's pass over L, all O(nnzL) -- on one workgroup per instance,
+ * and let every entry range of X recompute all K row sums of X_half X_half^T.  mmw_batch_set_head_split gives instance b parts[b] row
+ * parts for that work, 1 ... MMW_BATCH_MAX_HEAD_PARTS (a value outside is refused by instance with MMW_ERR_ARG and leaves the setting
+ * as it was).  While any instance that runs has parts > 1, every iteration goes through the split paths -- with neither
+ * mmw_batch_set_split nor mmw_batch_set_row_split that is the column split's path with one slice per instance -- and its head is the
+ * launches [gap row] averaging, DUAL, fold, LOSS: one workgroup per (instance, row part), except the gap row and the fold (e_accu,
+ * softmax, the LOSS constant: O(C)), which stay on one workgroup per instance.  On the row split's path the plan becomes an O(K)
+ * launch over per-row values the LOSS launch left; the host's one synchronisation per iteration stays where it is.  Behind the
+ * exponential a launch forms the row sums of X_half X_half^T once, by row part, and X on the pattern reads them.  Kernel boundaries
+ * are the only synchronisation.  The row ranges are those of mmw_batch_row_ranges' rule (mmw_batch_head_ranges writes the parts + 1
+ * boundaries of instance `inst`; it also answers on a host-only batch); part p also owns the pairs [p E_asso / parts, (p + 1) E_asso
+ * / parts).  Per-entry and per-row statements do not depend on their owner, a row's sum runs over its entries in CSR order, and every
+ * sum across threads stays on one workgroup with the single launch's thread map: all fields, the gap log and EXPM_INFO are bitwise
+ * what the single launch gives.  NULL or all ones turns it off (the default): every launch is then what it is without this entry.
+ * The setting survives mmw_batch_reset and mmw_batch_set_slots.  Tables, records and scratch live in buffers of their own: the arenas
+ * do not move.  MMW_F_HEAD_CALL says whether the last mmw_batch_iterate took the head path; MMW_F_SPLIT_CALL keeps its meaning and
+ * counts the head path's launches among its own.  MMW_ERR_STATE on a host-only batch.
+ */
+#define MMW_BATCH_MAX_HEAD_PARTS 64
+int mmw_batch_set_head_split(mmw_batch* b, const int32_t* parts);
+int mmw_batch_head_ranges(mmw_batch* b, int32_t inst, int32_t parts, int32_t* out);
 /* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
  * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);

@@ -22,8 +22,10 @@ F_FACTOR_INFO = 20
 F_FACTOR_CALL = 21
 F_FACTOR_ROWNORM = 23
 F_SPLIT_CALL = 22
+F_HEAD_CALL = 24
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
+BATCH_MAX_HEAD_PARTS = 64  # MMW_BATCH_MAX_HEAD_PARTS: head parts per instance at most (mmw_batch_set_head_split)
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
@@ -38,7 +40,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
-           "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map"]
+           "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges"]
 
 
 class MMWError(RuntimeError):
@@ -124,6 +126,8 @@ def lib():
     L.mmw_batch_set_factor_split.argtypes = [C.c_void_p, p_i32]
     L.mmw_batch_set_row_split.argtypes = [C.c_void_p, p_i32]
     L.mmw_batch_row_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_i32]
+    L.mmw_batch_set_head_split.argtypes = [C.c_void_p, p_i32]
+    L.mmw_batch_head_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_i32]
     L.mmw_batch_factor.argtypes = [C.c_void_p, p_i32, p_i32, pp_f64]
     L.mmw_batch_round.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
@@ -491,6 +495,7 @@ class BatchSolver(_Handle):
         self._auto = {}  # per setter in _SPLITS: the arguments of its suggest function while "auto" holds
         self.split_parts = None  # workgroups per instance as last accepted by set_split (None: the single-launch kernel)
         self.row_split_parts = None  # row parts per instance as last accepted by set_row_split (None: no row split)
+        self.head_split_parts = None  # head parts per instance as last accepted by set_head_split (None: the head on one workgroup)
         self.factor_split_parts = None  # the same for the factor, as last accepted by set_factor_split (None: k_batch_factor's one launch)
         self._load_sizes()
 
@@ -646,6 +651,7 @@ class BatchSolver(_Handle):
     # setter -> (C entry, suggest function, attribute holding the accepted parts)
     _SPLITS = {"set_split": ("mmw_batch_set_split", "suggest_split", "split_parts"),
                "set_row_split": ("mmw_batch_set_row_split", "suggest_row_split", "row_split_parts"),
+               "set_head_split": ("mmw_batch_set_head_split", "suggest_head_split", "head_split_parts"),
                "set_factor_split": ("mmw_batch_set_factor_split", "suggest_factor_split", "factor_split_parts")}
 
     def _apply_parts(self, who, parts):
@@ -730,6 +736,38 @@ class BatchSolver(_Handle):
         columns stopped; path 2 only), "widest" (workgroups of the largest launch)}."""
         v = self.read(0, F_SPLIT_CALL, 4)
         return {"path": int(v[0]), "launches": int(v[1]), "idle": int(v[2]), "widest": int(v[3])}
+
+    # ---- the head and the plan over workgroups (csrc/kernels_batch_head.h)
+    def head_ranges(self, inst, parts):
+        """The row boundaries the library uses for instance `inst` at `parts` head parts (mmw_batch_head_ranges): the rule of
+        `row_bounds`; part p owns the rows [out[p], out[p + 1]).  Answers on a host-only batch too."""
+        out = np.empty(int(parts) + 1, dtype=np.int32)
+        check(lib().mmw_batch_head_ranges(self._h, int(inst), int(parts), _pi(out)))
+        return [int(x) for x in out]
+
+    def suggest_head_split(self, cus=256):
+        """The rule of set_head_split("auto"): the head's work is O(nnzL), so instance i gets its share of `cus` compute units by stored
+        entries, parts_i = clamp(round(nnzL_i cus / sum nnzL), 1, min(64, ceil(K_i / 64))): at least 64 rows per part.  The rule is a
+        choice, not a measurement (DESIGN section 12 has what was measured).  Instances that sit out get 1 and do not weigh."""
+        w = [float(s["nnzL"]) if a else 0.0 for s, a in zip(self.sizes, self.active)]
+        tot = sum(w)
+        if tot <= 0.0:
+            return [1] * self.B
+        return [max(1, min(int(round(wi * cus / tot)), BATCH_MAX_HEAD_PARTS, -(-s["K"] // 64))) for wi, s in zip(w, self.sizes)]
+
+    def set_head_split(self, parts, cus=256):
+        """Row parts per instance for everything in front of the exponential (averaging, DUAL, LOSS, the plan's pass over L) and for the
+        row sums of X behind it, in the iterations that follow: an int for all, one per instance, "auto" (`suggest_head_split(cus)`,
+        taken again after every `set_slots`), or None / all ones for the head on one workgroup.  With it on an iteration runs through
+        the split paths even when `set_split` and `set_row_split` are off; every field stays bitwise what the single launch gives
+        (DESIGN section 12)."""
+        self._set_parts("set_head_split", parts, int(cus))
+
+    def head_call(self):
+        """The last `iterate` of this batch (MMW_F_HEAD_CALL): {"on": the head split ran, "launches" (of the head path's own kernels),
+        "widest" (workgroups of the largest of them)}."""
+        v = self.read(0, F_HEAD_CALL, 4)
+        return {"on": bool(v[0]), "launches": int(v[1]), "widest": int(v[2])}
 
     # ---- several workgroups per instance for the factor (csrc/kernels_batch_factor_split.h)
     @staticmethod

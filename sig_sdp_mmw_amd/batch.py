@@ -110,6 +110,13 @@ def _row_split(b, row_split):
         b.set_row_split(row_split)
 
 
+def _head_split(b, head_split):
+    """The `head_split=` keyword of the workflows, beside `split=` and `row_split=`: None leaves the head on one workgroup per instance; an
+    int, one int per instance or "auto" goes to `BatchSolver.set_head_split` after both (every result stays bitwise the same; see there)."""
+    if head_split is not None:
+        b.set_head_split(head_split)
+
+
 def _factor_split(b, factor_split, in_batch=True):
     """The `factor_split=` keyword of the workflows: None is k_batch_factor's one launch; an int, one int per instance or "auto" goes
     to `BatchSolver.set_factor_split` (every result stays bitwise the same; see there).  There is no batch factor to split under
@@ -134,12 +141,13 @@ def _finish(z, rem, used, i, Z, seed):
 
 
 def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None, rank_radio=2, device=0, factor_seed=0, epilogue="handle", split=None,
-                        factor_split=None, row_split=None):
+                        factor_split=None, row_split=None, head_split=None):
     """mmw.run_with_state (mmw.py:44-222) for every (Z, state) pair at once: one batch, `nit` iterations in one launch, then
     X_half per instance through export + mmw_factor on one reused fp64 handle per state, or with epilogue="batch" all of them in one
     more launch (instances over the epilogue limit still go through a handle).  factor_split: workgroups per instance for that
     factor (`BatchSolver.set_factor_split`; epilogue="batch" only).  row_split: row parts per instance beside `split`
-    (`BatchSolver.set_row_split`).  Returns [(True, X_half), ...]."""
+    (`BatchSolver.set_row_split`).  head_split: row parts per instance for the head of an iteration (`BatchSolver.set_head_split`).
+    Returns [(True, X_half), ...]."""
     del bs_iteration  # the log index of the reference's signature; nothing here depends on it
     in_batch = _check_epilogue(epilogue)
     _factor_split(None, factor_split, in_batch)
@@ -149,6 +157,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
     try:
         _split(b, split)
         _row_split(b, row_split)
+        _head_split(b, head_split)
         _factor_split(b, factor_split, in_batch)
         b.iterate(nit, None, seeds)
         take = [in_batch and _fits(b, i) for i in range(len(states))]
@@ -161,7 +170,7 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
         b.close()
 
 
-def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, split=None, row_split=None):
+def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, split=None, row_split=None, head_split=None):
     """The reference's convergence sweeps (sim_convergence_rho.py, sim_all_mmw.py: LOG_GAP = True, one run per instance) as one
     batch: `nit` and `eta` are one value for all or one per instance, the gap is logged inside the launch (mmw.py:79-117) and all
     iterations of all instances run in ONE `iterate`.  Returns per instance {"gap": [nit, 3], "lanczos_steps": [nit]}; the three
@@ -176,6 +185,7 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
         b.set_gap(True)
         _split(b, split)
         _row_split(b, row_split)
+        _head_split(b, head_split)
         b.iterate(max(nits), None, seeds)
         out = []
         for i in range(B):
@@ -197,7 +207,7 @@ def _check_warm(warm_fraction):
 
 
 def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", timings=None, split=None,
-                factor_split=None, row_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
+                factor_split=None, row_split=None, head_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
     """The bisection of binary_search_relaxation.py:44-72 for every state, in lockstep (one batch launch per round of probes).
     Returns per state {"Z", "z_vec", "remainder", "probes" (the slot counts probed, in order), "bounds"}.  epilogue="batch": the
     factors and the roundings of a round are one launch each (the rounding seed is the probe seed).  timings: a list that receives
@@ -206,7 +216,8 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     follows the slot counts of every round; None: one each); the results are bitwise the same.  factor_split: the same for the
     factor of epilogue="batch" (`BatchSolver.set_factor_split`; with epilogue="handle" anything but None raises ValueError), row_split: row parts
     per instance multiplied with `split`'s column slices (`BatchSolver.set_row_split`: an int, one per instance or "auto"), bitwise
-    too.  warm_start (opt-in; NOT the reference's search, which restarts every probe at mmw.py:62-68): the first probe of every
+    too; head_split: row parts per instance for the head of an iteration and the plan (`BatchSolver.set_head_split`: the same values),
+    bitwise too.  warm_start (opt-in; NOT the reference's search, which restarts every probe at mmw.py:62-68): the first probe of every
     instance runs cold with `nit`, every later round continues from the previous probe's iterate (`set_slots(..., warm=True)`) with
     `warm_iterations(nit, warm_fraction)` iterations; the probe seeds are unchanged.  Every result also holds "iters", the
     iterations of every probe in order, and every timings row "set_slots_s", the round's slot change."""
@@ -228,6 +239,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     try:
         _split(b, split)
         _row_split(b, row_split)
+        _head_split(b, head_split)
         _factor_split(b, factor_split, in_batch)
         while not all(done):
             mids = [0 if done[i] else math.floor(float(left[i] + right[i]) / 2.) for i in range(B)]
@@ -269,7 +281,7 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
 
 
 def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
-                rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
+                rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None, head_split=None, warm_start=False, warm_fraction=1.0 / 3.0):
     """The reference's online sweeps (sim_script/journal_version/sim_mmw_online.py:34-78, ton_major_rv/sim_mmw_online_cmp_*.py) for
     many `graphs.mobile_drop`s at once: the bisection on the drops' states (`search_many(..., epilogue="batch")`), one more solve at
     the Z it ends at for gX (:40) -- a batch of the (Z, state) pairs, iterated and factored once, the sketches keyed by the probe
@@ -289,7 +301,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
     found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                        factor_split=factor_split, row_split=row_split, warm_start=warm_start, warm_fraction=warm_fraction)
+                        factor_split=factor_split, row_split=row_split, head_split=head_split, warm_start=warm_start, warm_fraction=warm_fraction)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
@@ -298,6 +310,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     try:
         _split(b, split)
         _row_split(b, row_split)
+        _head_split(b, head_split)
         _factor_split(b, factor_split)
         b.iterate(nit, None, np.array([probe_seed(seed, i, len(found[i]["probes"])) for i in range(B)], dtype=np.uint64))
         b.factor()
@@ -323,7 +336,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
 
 def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
                         rank_radio=2, device=0, resolve_nit=None, carry=False, warm_fraction=1.0 / 3.0, timings=None, split=None, factor_split=None,
-                        row_split=None):
+                        row_split=None, head_split=None):
     """`online_many` with a re-solve at every time point (NOT one of the reference's scripts, which solve once and re-round that
     factor while the stations walk).  The start is `online_many`'s: the bisection on the drops' states, one more solve at the Z it
     ends at with the same sketch seed, and point 0 is that factor rounded on the unmoved state.  Z stays at that Z throughout.
@@ -349,7 +362,7 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     states = [d.state() for d in drops]
     found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                        factor_split=factor_split, row_split=row_split)
+                        factor_split=factor_split, row_split=row_split, head_split=head_split)
     Zs = [int(r["Z"]) for r in found]
     out = [{"Z": Zs[i], "probes": found[i]["probes"], "z_vec": np.empty((n_points, drops[i].K)), "remainder": np.empty(n_points, dtype=np.int64),
             "bler": np.empty((n_points, drops[i].K)), "iters": [int(nit)] + [n_p] * (n_points - 1)} for i in range(B)]
@@ -359,6 +372,7 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
         try:
             _split(b, split)
             _row_split(b, row_split)
+            _head_split(b, head_split)
             _factor_split(b, factor_split)
         except Exception:
             b.close()
@@ -468,7 +482,7 @@ def _geometry(d):
     return (d.sta_locs, d.ap_locs) if hasattr(d, "sta_locs") else (np.asarray(d[0], dtype=np.float64), np.asarray(d[1], dtype=np.float64))
 
 
-def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None,
+def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None, head_split=None,
                  warm_start=False, warm_fraction=1.0 / 3.0):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
@@ -484,7 +498,7 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         states = [env.state(i) for i in range(B)]
         t0 = time.perf_counter()
         found = search_many(states, nit=nit, eta=eta, seed=seed, nattempt=nattempt, rank_radio=rank_radio, device=device, epilogue="batch", split=split,
-                            factor_split=factor_split, row_split=row_split, warm_start=warm_start, warm_fraction=warm_fraction)
+                            factor_split=factor_split, row_split=row_split, head_split=head_split, warm_start=warm_start, warm_fraction=warm_fraction)
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
@@ -543,7 +557,7 @@ class single:
     one, with search_many's seeds: `binary_search_relaxation` driven by it probes what search_many probes for instance `index`
     (with the same warm_start / warm_fraction too)."""
 
-    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None, row_split=None,
+    def __init__(self, state, index=0, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, epilogue="handle", split=None, factor_split=None, row_split=None, head_split=None,
                  warm_start=False, warm_fraction=1.0 / 3.0):
         _check_warm(warm_fraction)
         self.warm_start, self.warm_fraction = bool(warm_start), float(warm_fraction)
@@ -556,6 +570,7 @@ class single:
         self._b = None
         self._split = split
         self._row_split = row_split
+        self._head_split = head_split
         self._factor_split = factor_split
         self._hs = _Handles([state], self.nit, self.eta, self.rank_radio, self.device)
 
@@ -565,6 +580,7 @@ class single:
             self._b = _lib.BatchSolver([Z], [state], self.nit, self.eta, rank_radio=self.rank_radio, device=self.device)
             _split(self._b, self._split)
             _row_split(self._b, self._row_split)
+            _head_split(self._b, self._head_split)
             _factor_split(self._b, self._factor_split)
         warm = self.warm_start and len(self.probes) > 0  # as search_many: the first probe cold, every later one from its predecessor
         n = warm_iterations(self.nit, self.warm_fraction) if warm else self.nit

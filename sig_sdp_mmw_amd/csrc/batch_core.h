@@ -34,6 +34,18 @@ inline int check_parts(const char* who, const int32_t* p, int B, std::vector<int
     else dst.clear();
     return MMW_OK;
 }
+// Row ranges of one instance (the row split's and the head split's): boundary p is the first row at which the prefix of indptr reaches
+// p nnzL / rows (compared in integers), boundary `rows` is K.  Contiguous, a cover of [0, K), balanced by stored entries; ranges may be
+// empty.  out: rows + 1 boundaries.
+inline void batch_row_bounds(const int32_t* indptr, int K, int rows, int32_t* out) {
+    const int64_t nnz = indptr[K];
+    int r = 0;
+    for (int p = 0; p < rows; ++p) {
+        while (r < K && (int64_t)indptr[r] * rows < (int64_t)p * nnz) ++r;
+        out[p] = r;
+    }
+    out[rows] = K;
+}
 
 struct BatchCore {
     int device = 0, B = 0, rank_radio = 2, max_order = MAX_ORDER;

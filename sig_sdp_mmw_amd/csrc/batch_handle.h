@@ -1,6 +1,6 @@
 // Batched solver (mmw_batch_*): many small fp64 instances, one workgroup each (csrc/kernels_batch.h).  The handle holds a core
 // (batch_core.h: patterns, counters, the two arenas) and four parts by value, each with the state and the device buffers of one feature:
-// gap and split (batch_iterate.h), rows (batch_rows.h), epi (batch_epilogue.h), greedy (batch_gm.h), and sequences them.  Whatever a part holds that a new
+// gap and split (batch_iterate.h), head (batch_head.h), rows (batch_rows.h), epi (batch_epilogue.h), greedy (batch_gm.h), and sequences them.  Whatever a part holds that a new
 // run invalidates, it drops in its on_restart: reset and set_slots call those and name no field of a part.  Two entries work on a
 // pair of batches and stand below the handle: batch_export_into (an fp64 handle) and batch_carry (another batch, on moved states).
 #pragma once
@@ -14,6 +14,7 @@ struct mmw_batch {
     BatchGap gap;
     BatchSplit split;
     BatchRows rows;
+    BatchHead head;
     BatchEpilogue epi;
     BatchGm greedy;
     DevBuf<double> rbuf, skbuf;  // the call's sketches (iterate), the block handed out (sketch)
@@ -142,8 +143,15 @@ struct mmw_batch {
         MMW_TRY(gap.stage(core));
         int nmax = 0;
         for (int b = 0; b < B; ++b) nmax = std::max(nmax, dd[b].nrun);
+        // the head split rides on the split paths: alone it is the column split's path with one slice per instance
+        BatchHead* hd = head.wanted(dd) ? &head : nullptr;
+        if (hd) MMW_TRY(head.stage(core, dd));
+        else head.off();
         if (rows.wanted(dd)) {
-            MMW_TRY(rows.run(core, gap, split.parts, dd, rv));
+            MMW_TRY(rows.run(core, gap, split.parts, dd, rv, hd));
+        } else if (hd) {
+            MMW_TRY(split.run(core, gap, dd, rv, hd));
+            rows.record(1, (int64_t)nmax + head.launches, 0, std::max<int64_t>(std::max<int64_t>(split.d_wexpm.n, head.widest), std::max<int64_t>(split.d_wx.n, B)));
         } else if (split.wanted(dd)) {
             MMW_TRY(split.run(core, gap, dd, rv));
             rows.record(1, 3 * (int64_t)nmax, 0, std::max<int64_t>(split.d_wexpm.n, std::max<int64_t>(split.d_wx.n, B)));
@@ -156,6 +164,7 @@ struct mmw_batch {
         }
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(st));
+        if (hd) head.done();
         for (int b = 0; b < B; ++b) core.iter[b] += dd[b].nrun;
         return MMW_OK;
     }
@@ -174,6 +183,7 @@ struct mmw_batch {
             case MMW_F_ST_DATA: return read_host(P.st_data, out, n);
             case MMW_F_FACTOR_CALL: return read_host(std::vector<double>(epi.fs.call, epi.fs.call + 4), out, n);
             case MMW_F_SPLIT_CALL: return read_host(std::vector<double>(rows.call, rows.call + 4), out, n);
+            case MMW_F_HEAD_CALL: return read_host(std::vector<double>(head.call, head.call + 4), out, n);
             default: break;
         }
         if (core.host_only) return BatchCore::host_only_batch();
@@ -226,6 +236,14 @@ struct mmw_batch {
         if (nrows < 1 || nrows > MMW_BATCH_MAX_ROW_PARTS)
             return fail(MMW_ERR_ARG, "mmw_batch_row_ranges: rows = " + std::to_string(nrows) + " is outside [1, " + std::to_string(MMW_BATCH_MAX_ROW_PARTS) + "]");
         batch_row_bounds(core.H[b].l_indptr.data(), core.H[b].K, nrows, out);
+        return MMW_OK;
+    }
+    int set_head_split(const int32_t* p) { return head.set(core, p); }
+    int head_ranges(int b, int32_t nparts, int32_t* out) const {
+        MMW_TRY(core.check_inst(b));
+        if (nparts < 1 || nparts > MMW_BATCH_MAX_HEAD_PARTS)
+            return fail(MMW_ERR_ARG, "mmw_batch_head_ranges: parts = " + std::to_string(nparts) + " is outside [1, " + std::to_string(MMW_BATCH_MAX_HEAD_PARTS) + "]");
+        batch_row_bounds(core.H[b].l_indptr.data(), core.H[b].K, nparts, out);
         return MMW_OK;
     }
     int set_factor_split(const int32_t* p) { return epi.set_split(core, p); }

@@ -2,6 +2,7 @@
 // split of an instance over several workgroups (mmw_batch_set_split, kernels_batch_split.h).
 #pragma once
 #include "batch_core.h"
+#include "batch_head.h"
 #include "kernels_batch_split.h"
 
 // The gap log: a buffer of its own, made when the gap is first enabled, so the arenas do not move.
@@ -65,8 +66,9 @@ struct BatchSplit {
             if (dd[b].nrun > 0 && parts[b] > 1) return true;
         return false;
     }
-    // One iteration as three launches for all instances (kernels_batch_split.h); `dd` is on the device already.
-    int run(const BatchCore& c, const BatchGap& gap, const std::vector<BatchDesc>& dd, const double* rv) {
+    // One iteration as three launches for all instances (kernels_batch_split.h); `dd` is on the device already.  head: the staged
+    // head split (batch_head.h) while it is on -- its launches stand for k_batch_split_head and k_batch_split_x -- else null.
+    int run(const BatchCore& c, const BatchGap& gap, const std::vector<BatchDesc>& dd, const double* rv, BatchHead* head = nullptr) {
         std::vector<SplitSlice> we;
         std::vector<SplitRange> wx;
         int nmax = 0;
@@ -74,20 +76,26 @@ struct BatchSplit {
             const BatchDesc& d = dd[b];
             if (d.nrun <= 0) continue;
             nmax = std::max(nmax, d.nrun);
-            const int W = split_width(d.D, parts[b]), G = split_slices(d.D, parts[b]), slab0 = (int)we.size();
+            const int cp = parts.empty() ? 1 : parts[b];  // (empty: the head split alone is on)
+            const int W = split_width(d.D, cp), G = split_slices(d.D, cp), slab0 = (int)we.size();
             for (int g = 0; g < G; ++g) we.push_back(SplitSlice{b, g, W, slab0 + g});
-            for (int p = 0; p < parts[b]; ++p) wx.push_back(SplitRange{b, p, parts[b], slab0, G});
+            for (int p = 0; p < cp; ++p) wx.push_back(SplitRange{b, p, cp, slab0, G});
         }
         MMW_TRY(d_wexpm.upload(we, c.st));
         MMW_TRY(d_wx.upload(wx, c.st));
         MMW_TRY(slab.alloc(we.size()));
         for (int it = 0; it < nmax; ++it) {
-            if (gap.on)
+            if (head)
+                head->front(c, gap.on ? gap.d_gdesc.p : nullptr, gap.ga.p, it);
+            else if (gap.on)
                 hipLaunchKernelGGL(k_batch_split_head<true>, dim3(c.B), dim3(BATCH_THREADS), 0, c.st, c.d_desc.p, c.ia.p, c.fa.p, gap.d_gdesc.p, gap.ga.p, it);
             else
                 hipLaunchKernelGGL(k_batch_split_head<false>, dim3(c.B), dim3(BATCH_THREADS), 0, c.st, c.d_desc.p, c.ia.p, c.fa.p, (const GapDesc*)nullptr, (double*)nullptr, it);
             hipLaunchKernelGGL(k_batch_split_expm, dim3((unsigned)we.size()), dim3(BATCH_THREADS), 0, c.st, c.d_desc.p, d_wexpm.p, c.ia.p, c.fa.p, rv, slab.p, it);
-            hipLaunchKernelGGL(k_batch_split_x, dim3((unsigned)wx.size()), dim3(BATCH_THREADS), 0, c.st, c.d_desc.p, d_wx.p, c.ia.p, c.fa.p, slab.p, it);
+            if (head)
+                head->x(c, d_wx, slab.p, it);
+            else
+                hipLaunchKernelGGL(k_batch_split_x, dim3((unsigned)wx.size()), dim3(BATCH_THREADS), 0, c.st, c.d_desc.p, d_wx.p, c.ia.p, c.fa.p, slab.p, it);
         }
         return MMW_OK;
     }

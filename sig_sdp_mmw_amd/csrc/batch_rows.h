@@ -4,18 +4,6 @@
 #include "batch_iterate.h"
 #include "kernels_batch_rows.h"
 
-// Row ranges of one instance: boundary p is the first row at which the prefix of indptr reaches p nnzL / rows (compared in integers),
-// boundary `rows` is K.  Contiguous, a cover of [0, K), balanced by stored entries; ranges may be empty.  out: rows + 1 boundaries.
-inline void batch_row_bounds(const int32_t* indptr, int K, int rows, int32_t* out) {
-    const int64_t nnz = indptr[K];
-    int r = 0;
-    for (int p = 0; p < rows; ++p) {
-        while (r < K && (int64_t)indptr[r] * rows < (int64_t)p * nnz) ++r;
-        out[p] = r;
-    }
-    out[rows] = K;
-}
-
 struct BatchRows {
     std::vector<int> rows;  // row parts per instance (empty: one each)
     DevBuf<RowsWork> d_work;
@@ -35,8 +23,10 @@ struct BatchRows {
         call[0] = path; call[1] = (double)launches; call[2] = (double)idle; call[3] = (double)widest;
     }
     // One iteration as head, plan, the launches of the longest schedule and x, for all instances (kernels_batch_rows.h); `dd` is on the
-    // device already.  colparts: BatchSplit's setting (empty: one slice each).
-    int run(const BatchCore& c, const BatchGap& gap, const std::vector<int>& colparts, const std::vector<BatchDesc>& dd, const double* rv) {
+    // device already.  colparts: BatchSplit's setting (empty: one slice each).  head: the staged head split (batch_head.h) while it is
+    // on -- its launches stand for k_batch_split_head, k_batch_rows_plan and k_batch_split_x -- else null.
+    int run(const BatchCore& c, const BatchGap& gap, const std::vector<int>& colparts, const std::vector<BatchDesc>& dd, const double* rv,
+            BatchHead* head = nullptr) {
         std::vector<RowsWork> wk;
         std::vector<SplitRange> wx;
         std::vector<int32_t> bd;
@@ -74,11 +64,16 @@ struct BatchRows {
         const int* pending = nullptr;  // the flags of an iteration's last step launch, tallied by the next plan launch
         const unsigned nwk = (unsigned)wk.size();
         for (int it = 0; it < nmax; ++it) {
-            if (gap.on)
+            if (head)
+                head->front(c, gap.on ? gap.d_gdesc.p : nullptr, gap.ga.p, it);
+            else if (gap.on)
                 hipLaunchKernelGGL(k_batch_split_head<true>, dim3(c.B), dim3(BATCH_THREADS), 0, st, c.d_desc.p, c.ia.p, c.fa.p, gap.d_gdesc.p, gap.ga.p, it);
             else
                 hipLaunchKernelGGL(k_batch_split_head<false>, dim3(c.B), dim3(BATCH_THREADS), 0, st, c.d_desc.p, c.ia.p, c.fa.p, (const GapDesc*)nullptr, (double*)nullptr, it);
-            hipLaunchKernelGGL(k_batch_rows_plan, dim3(c.B), dim3(BATCH_THREADS), 0, st, c.d_desc.p, c.ia.p, c.fa.p, rec.p, pending, nsid, cnt.p, it);
+            if (head)
+                head->plan(c, rec.p, pending, nsid, cnt.p, it);
+            else
+                hipLaunchKernelGGL(k_batch_rows_plan, dim3(c.B), dim3(BATCH_THREADS), 0, st, c.d_desc.p, c.ia.p, c.fa.p, rec.p, pending, nsid, cnt.p, it);
             MMW_HIP(hipGetLastError());
             MMW_TRY(copy_d2h(hrec.data(), rec.p, hrec.size() * sizeof(double), st));  // the iteration's one synchronisation
             int lmax = 0;
@@ -88,9 +83,12 @@ struct BatchRows {
                 hipLaunchKernelGGL(k_batch_rows_step, dim3(nwk), dim3(BATCH_THREADS), 0, st, c.d_desc.p, d_work.p, rec.p, c.ia.p, c.fa.p, rv, slab_t.p,
                                    slab_f.p, st_prev.p, st_on.p, deg.p, flags.p, cnt.p, (int)nslab, nsid, it, l);
             pending = flags.p + (size_t)((lmax - 1) & 1) * nsid;
-            hipLaunchKernelGGL(k_batch_split_x, dim3((unsigned)wx.size()), dim3(BATCH_THREADS), 0, st, c.d_desc.p, d_wx.p, c.ia.p, c.fa.p, deg.p, it);
+            if (head)
+                head->x(c, d_wx, deg.p, it);
+            else
+                hipLaunchKernelGGL(k_batch_split_x, dim3((unsigned)wx.size()), dim3(BATCH_THREADS), 0, st, c.d_desc.p, d_wx.p, c.ia.p, c.fa.p, deg.p, it);
             MMW_HIP(hipGetLastError());
-            launches += 2 + lmax + 1;
+            launches += head ? lmax : 2 + lmax + 1;
         }
         // the record: the idle launches the device tallied, and the last launch's flags read here
         std::vector<int> hf((size_t)nsid);
@@ -98,7 +96,8 @@ struct BatchRows {
         MMW_TRY(copy_d2h(&idle, cnt.p, sizeof(int), st));
         MMW_TRY(copy_d2h(hf.data(), pending, hf.size() * sizeof(int), st));
         idle += std::all_of(hf.begin(), hf.end(), [](int x) { return x == 0; });
-        record(2, launches, idle, std::max<int64_t>(std::max<int64_t>(nwk, (int64_t)wx.size()), c.B));
+        if (head) launches += head->launches;
+        record(2, launches, idle, std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(nwk, (int64_t)wx.size()), c.B), head ? head->widest : 0));
         return MMW_OK;
     }
 };

@@ -190,6 +190,8 @@ int mmw_batch_read_gap(mmw_batch* b, int32_t inst, double* out, int64_t n) { ret
 int mmw_batch_set_split(mmw_batch* b, const int32_t* parts) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_split(parts); }); }
 int mmw_batch_set_row_split(mmw_batch* b, const int32_t* rows) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_row_split(rows); }); }
 int mmw_batch_row_ranges(mmw_batch* b, int32_t inst, int32_t rows, int32_t* out) { return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->row_ranges(inst, rows, out); }); }
+int mmw_batch_set_head_split(mmw_batch* b, const int32_t* parts) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_head_split(parts); }); }
+int mmw_batch_head_ranges(mmw_batch* b, int32_t inst, int32_t parts, int32_t* out) { return entry("mmw_batch", !b || !out, "null pointer", [&] { return b->head_ranges(inst, parts, out); }); }
 int mmw_batch_set_factor_split(mmw_batch* b, const int32_t* parts) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->set_factor_split(parts); }); }
 int mmw_batch_iterate(mmw_batch* b, int32_t n, const double* randv, const uint64_t* seeds) { return entry("mmw_batch", !b, "null batch handle", [&] { return b->iterate(n, randv, seeds); }); }
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n) { return entry("mmw_batch", !b || (!out && n), "null pointer", [&] { return b->read_f64(inst, which, out, n); }); }
