@@ -220,6 +220,8 @@ int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t 
  * feasibility assignment in descending ||gX_k|| order.  z_out[nbatch,K] gets the slot or -1 for a user
  * left unassigned (the caller draws those, sdp_solver.py:104-105); rem_out[nbatch] the count.
  * gX == NULL: the K x Dp factor mmw_factor computed last on this handle, read where it lies on the device.
+ * Ties: equal norms are visited by lower user index, equal inner products prefer the lower slot.  Zr > 4800 (32 Zr bytes
+ * of flags beyond the greedy kernel's LDS) is refused with MMW_ERR_ARG before anything is allocated, copied, launched or timed.
  */
 int mmw_round(mmw_solver* s, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv,
               int32_t* z_out, int32_t* rem_out);

@@ -183,7 +183,10 @@ template <typename T> struct Extras {
         // gX == nullptr: the factor this handle computed last, where mmw_factor left it on the device (no copy out and in again)
         if (!gX_h && ((size_t)K * Dp != fac.last_n || Dp != fac.last_rank || fac.last_n == 0))
             return fail(MMW_ERR_STATE, "mmw_round: gX is null and the handle holds no factor of K x D'");
-        if ((size_t)Z * sizeof(int) > 60000) return fail(MMW_ERR_ARG, "mmw_round: Z too large");
+        // every Z this call cannot run is refused here, before anything is allocated, copied, launched or timed: k_greedy_b keeps
+        // GB_WAVES rows of Z flags in LDS (Z <= 4800, which also keeps k_slot_pref's 8 Z bytes within the default 64 KiB)
+        const size_t baseb = (size_t)GB_WAVES * Z * 4;
+        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: 32 Z bytes exceed the greedy kernel's LDS");
         const size_t nP = (size_t)nb * K * Z;
         if (gX_h) MMW_TRY(ensure(gX, (size_t)K * Dp));
         const double* gX_d = gX_h ? gX.p : fac.out64.p;
@@ -236,8 +239,6 @@ template <typename T> struct Extras {
             MMW_HIP(hipStreamSynchronize(st));
             fprintf(stderr, "[round] %d users in %d steps (%.1f per step)\n", K, ns, (double)K / std::max(ns, 1));
         }
-        const size_t baseb = (size_t)GB_WAVES * Z * 4;
-        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: 64 Z bytes exceed the greedy kernel's LDS");
         const bool slot_lds = baseb + (size_t)K * 4 <= 150 * 1024;
         const size_t sh = baseb + (slot_lds ? (size_t)K * 4 : 0);
         if (slot_lds) {
