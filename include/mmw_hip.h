@@ -84,6 +84,11 @@ enum mmw_field {
                              head split ran (mmw_batch_set_head_split), else 0; launches of the head path's own kernels (k_batch_head_*)
                              enqueued; workgroups of the widest of them; 0}; zeros before the first call and with the head split off;
                              batches only */
+    MMW_F_PATTERN = 25,     /* [2*nnzL + 4*K] the pattern part of an instance's fp64 arena as the batch kernels read it: S_T'[row,col] and
+                             S_T'[col,row] on the L pattern, h_max, S_sum, 1 / norm_H, cH; batches only, MMW_ERR_STATE on a host-only one */
+    MMW_F_BUILD_INFO = 26,  /* [2]    live, per instance: {how the batch was built: 0 from host arrays (mmw_batch_create), 1 on the
+                             device (mmw_batch_create_from_env); 1 while the instance's host lists are complete, 0 while a batch built on
+                             the device has not fetched them yet}; batches only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -97,7 +102,10 @@ enum mmw_ifield {
     MMW_I_ASSO_X = 6,     /* [E_asso] nz_idx_asso_x_ut (mmw.py:57) */
     MMW_I_ASSO_Y = 7,
     MMW_I_DIAG_POS = 8,   /* [K] position of (k,k) in the L pattern */
-    MMW_I_ASSO_POS = 9    /* [E_asso] position of (x,y), x<y, in the L pattern */
+    MMW_I_ASSO_POS = 9,   /* [E_asso] position of (x,y), x<y, in the L pattern */
+    MMW_I_PATTERN = 10    /* [2*K + 1 + 3*nnzL + E_asso] an instance's slice of the int32 arena as the batch kernels read it: indptr,
+                             columns, rows, pair ids (-1: none), diagonal positions, pair positions; batches only, MMW_ERR_STATE on a
+                             host-only one */
 };
 
 const char* mmw_last_error(void);
@@ -448,7 +456,9 @@ int mmw_batch_row_ranges(mmw_batch* b, int32_t inst, int32_t rows, int32_t* out)
 int mmw_batch_set_head_split(mmw_batch* b, const int32_t* parts);
 int mmw_batch_head_ranges(mmw_batch* b, int32_t inst, int32_t parts, int32_t* out);
 /* the fields of instance `inst` by the MMW_F_* / MMW_I_* ids: Y, E_ACCU, E_THIS, LVAL, XVAL, XAVG, YAVG, XHALF, SKETCH, S_SUM, NORM_H,
- * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; other ids are refused */
+ * ST_DATA, EXPM_INFO ({rho, Taylor steps taken, substeps, mu}) and every pattern array; MMW_F_PATTERN / MMW_I_PATTERN (the pattern
+ * part of the instance's two arenas as the kernels read it) and MMW_F_BUILD_INFO (how the batch was built, mmw_batch_create_from_env);
+ * other ids are refused */
 int mmw_batch_read_f64(mmw_batch* b, int32_t inst, int which, double* out, int64_t n);
 int mmw_batch_read_i32(mmw_batch* b, int32_t inst, int which, int32_t* out, int64_t n);
 /* the block the device generator draws for instance `inst` in `iteration` of a run with `seed` (mmw_sketch's semantics) */
@@ -621,6 +631,21 @@ int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const i
                            double slot_time, double* const* sinr_out, double* const* bler_out);
 int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first,
                         const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out);
+/* The batch for the states an environment holds, built on the device (csrc/kernels_batch_pattern.h, csrc/batch_from_env.h): B = the
+ * environment's instances, on its device, on the state of its last move.  It is the batch mmw_batch_create makes from the arrays
+ * mmw_batch_env_state hands out for every instance at the same Z[b], rank_radio, eta and nit[b]: mmw_batch_sizes, every
+ * mmw_batch_read_i32 list and every mmw_batch_read_f64 field are equal bit for bit, and so is everything computed from them.
+ * Creation is a count pass, ONE readback for all instances (the sizes, l_indptr, S_sum, the squared row sums, h_max), norm_H and cH
+ * on the host (they depend on Z), one upload, the fill pass and one launch for the initial point: no per-instance copy and no host
+ * pass over stored entries.  The batch copies the state's lists device to device and keeps no reference to the environment, which
+ * may move or be destroyed at once.  The host lists behind mmw_batch_read_i32 (but MMW_I_L_INDPTR), MMW_F_ST_DATA, mmw_batch_export
+ * and mmw_batch_carry(_map) are fetched per instance the first time an entry needs them, from that copy (MMW_F_BUILD_INFO says
+ * whether that has happened); the first mmw_batch_gm fetches Q of every instance for its clique decision and completes no list.
+ * Refused by instance, *out untouched: an environment that has not moved (MMW_ERR_STATE); nit[b] < 1, K < 2, a Z[b] that
+ * mmw_batch_set_slots refuses and the batch limits of mmw_batch_create, in its words (MMW_ERR_ARG).  Z, D and K are checked before
+ * anything is allocated; nnzL, the arena size and norm_H after the count pass, before the arenas are made.  There is no host-only
+ * form. */
+int mmw_batch_create_from_env(mmw_batch** out, mmw_batch_env* env, const int32_t* Z, int32_t rank_radio, double eta, const int32_t* nit);
 /* mmw_batch_gm on the state of the environment's last move: see there */
 int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out,
                      int32_t* zz_out, int32_t* rem_out, double* key_out);

@@ -23,12 +23,15 @@ F_FACTOR_CALL = 21
 F_FACTOR_ROWNORM = 23
 F_SPLIT_CALL = 22
 F_HEAD_CALL = 24
+BATCH_F_PATTERN = 25  # (named apart from the F_ ids both kinds of handle share) batches: the pattern part of the fp64 arena [2 nnzL + 4 K]: sab, sba, h_max, S_sum, 1 / norm_H, cH
+BATCH_F_BUILD_INFO = 26  # batches, per instance: {0 built from host arrays / 1 on the device, 1 once the host lists are complete}
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
 BATCH_MAX_HEAD_PARTS = 64  # MMW_BATCH_MAX_HEAD_PARTS: head parts per instance at most (mmw_batch_set_head_split)
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
+I_PATTERN = 10  # batches: the int32 arena of an instance [2 K + 1 + 3 nnzL + E_asso]: indptr, col, row, pair id, diag pos, pair pos
 
 EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "mmw_destroy", "mmw_sizes", "mmw_set_expm",
            "mmw_set_timing", "mmw_set_profile", "mmw_bench_spmm", "mmw_reset", "mmw_set_slots", "mmw_set_slots_warm", "mmw_set_eta", "mmw_iterate", "mmw_sync", "mmw_sketch", "mmw_read_f64", "mmw_read_i32", "mmw_gap",
@@ -40,7 +43,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_round_randv", "mmw_batch_env_create", "mmw_batch_env_destroy", "mmw_batch_env_move", "mmw_batch_env_sizes",
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
-           "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges"]
+           "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
+           "mmw_batch_create_from_env"]
 
 
 class MMWError(RuntimeError):
@@ -143,6 +147,7 @@ def lib():
     L.mmw_batch_env_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
     L.mmw_batch_factor_random.argtypes = [C.c_void_p, p_i32, C.POINTER(C.c_uint64)]
     L.mmw_batch_factor_spectral.argtypes = [C.c_void_p, p_i32, p_i32]
+    L.mmw_batch_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, p_i32, C.c_int32, C.c_double, p_i32]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -489,6 +494,27 @@ class BatchSolver(_Handle):
                                      ptrs("sp", C.c_int32), ptrs("si", C.c_int32), ptrs("sx", C.c_double),
                                      ptrs("qp", C.c_int32), ptrs("qi", C.c_int32), ptrs("qx", C.c_double), ptrs("h", C.c_double)))
         self._keep = None
+        self._created(device, nits)
+
+    @classmethod
+    def from_env(cls, env, Zs, nit, eta, rank_radio=2):
+        """The batch for the states a `BatchEnv` holds after its last move, built on the environment's device without the host round
+        trip (mmw_batch_create_from_env): the object `BatchSolver(Zs, [env.state(i) for i in range(env.B)], nit, eta, rank_radio)`
+        gives, field for field.  It keeps nothing of `env`, which may move on at once."""
+        B = int(env.B)
+        if len(Zs) != B:
+            raise MMWError("BatchSolver.from_env: %d slot counts for the environment's %d instances" % (len(Zs), B))
+        nits = np.broadcast_to(np.asarray(nit, dtype=np.int32), (B,))
+        self = cls.__new__(cls)
+        self.B = B
+        Zarr, narr = _i32(Zs), _i32(nits)
+        self._h = C.c_void_p()
+        check(lib().mmw_batch_create_from_env(C.byref(self._h), env._h, _pi(Zarr), int(rank_radio), float(eta), _pi(narr)))
+        self._created(env.device, nits)
+        return self
+
+    def _created(self, device, nits):
+        B = self.B
         self.device = int(device)
         self.nits = [int(x) for x in nits]
         self.active = [True] * B
@@ -599,6 +625,10 @@ class BatchSolver(_Handle):
                 n = sz["K"] * sz["D"]
             elif which == F_EXPM_INFO:
                 n = 4
+            elif which == BATCH_F_PATTERN:
+                n = 2 * sz["nnzL"] + 4 * sz["K"]
+            elif which == BATCH_F_BUILD_INFO:
+                n = 2
             else:
                 n = sz[self._LEN[which]]
         out = np.empty(int(n), dtype=np.float64)
@@ -610,8 +640,12 @@ class BatchSolver(_Handle):
     _ILEN = _ILEN
 
     def read_i32(self, inst, which):
-        name, off = self._ILEN[which]
-        n = self.sizes[inst][name] + off
+        if which == I_PATTERN:
+            sz = self.sizes[inst]
+            n = 2 * sz["K"] + 1 + 3 * sz["nnzL"] + sz["E_asso"]
+        else:
+            name, off = self._ILEN[which]
+            n = self.sizes[inst][name] + off
         out = np.empty(int(n), dtype=np.int32)
         check(lib().mmw_batch_read_i32(self._h, int(inst), int(which), _pi(out), int(n)))
         return out
@@ -1003,6 +1037,7 @@ class BatchEnv(_Handle):
         if B < 1 or len(Ks) != B or any(a.ndim != 2 or a.shape[1] != 2 for a in aps):
             raise MMWError("BatchEnv: one (A, 2) array of AP locations and one station count per instance, at least one instance")
         self.Ks, self.As = [int(k) for k in Ks], [int(a.shape[0]) for a in aps]
+        self.device = int(device)
         self._h = C.c_void_p()
         check(lib().mmw_batch_env_create(C.byref(self._h), int(device), B, _pi(_i32(self.Ks)), _pi(_i32(self.As)), self._ptrs(aps), float(fre_Hz),
                                          float(txp_offset), float(min_s_n_ratio), float(min_sinr), float(noise_floor_dbm)))

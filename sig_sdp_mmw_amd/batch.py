@@ -336,7 +336,7 @@ def online_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
 
 def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10,
                         rank_radio=2, device=0, resolve_nit=None, carry=False, warm_fraction=1.0 / 3.0, timings=None, split=None, factor_split=None,
-                        row_split=None, head_split=None):
+                        row_split=None, head_split=None, handover="host"):
     """`online_many` with a re-solve at every time point (NOT one of the reference's scripts, which solve once and re-round that
     factor while the stations walk).  The start is `online_many`'s: the bisection on the drops' states, one more solve at the Z it
     ends at with the same sketch seed, and point 0 is that factor rounded on the unmoved state.  Z stays at that Z throughout.
@@ -350,7 +350,12 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
     re-solve's at the same iterations.
     The drops are moved in place.  Returns `online_many`'s dictionaries plus "iters", the iterations behind every point's factor.
     timings: a list that receives per point {"create_s" (move, states, the new batch), "carry_s", "iterate_s", "epilogue_s" (factor
-    and round), "evaluate_s", "step_s"}."""
+    and round), "evaluate_s", "step_s"}.
+    handover: how a time point's states reach its new batch.  "host" (the default): `BatchEnv.state` per instance and
+    `BatchSolver` on those arrays.  "device": `BatchSolver.from_env`, which builds the same batch on the device from the
+    environment itself; the returned dictionaries are bitwise the same."""
+    if handover not in ("host", "device"):
+        raise ValueError("online_resolve_many: handover must be \"host\" or \"device\", got %r" % (handover,))
     B = len(drops)
     for i, d in enumerate(drops):
         if d.K > _lib.BATCH_EPILOGUE_MAX_K:
@@ -368,7 +373,11 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
             "bler": np.empty((n_points, drops[i].K)), "iters": [int(nit)] + [n_p] * (n_points - 1)} for i in range(B)]
 
     def solver(sts, n):
-        b = _lib.BatchSolver(Zs, sts, n, eta, rank_radio=rank_radio, device=device)
+        """The batch on the states `sts`, or (sts None) on the ones `env` holds, built on the device."""
+        if sts is None:
+            b = _lib.BatchSolver.from_env(env, Zs, n, eta, rank_radio=rank_radio)
+        else:
+            b = _lib.BatchSolver(Zs, sts, n, eta, rank_radio=rank_radio, device=device)
         try:
             _split(b, split)
             _row_split(b, row_split)
@@ -393,7 +402,7 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
                 t1 = t2 = t3 = time.perf_counter()
                 z, rem, used = prev.round_env(env, nattempt, seeds)
             else:
-                b = solver([env.state(i) for i in range(B)], n_p)
+                b = solver([env.state(i) for i in range(B)] if handover == "host" else None, n_p)
                 try:
                     t1 = time.perf_counter()
                     if carry:

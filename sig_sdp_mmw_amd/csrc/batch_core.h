@@ -1,11 +1,17 @@
 // What every part of the batched solver reads (batch_handle.h): the instances' host patterns (built by the host code mmw_create uses,
 // build_pattern / update_slots), their run counters, and the int32 and the fp64 arena all of them are packed into.
+//
+// A batch built on the device (mmw_batch_create_from_env, batch_from_env.h) holds of every host pattern only what its creation read
+// back: the sizes, l_indptr, S_sum, the squared row sums, h_max and the Z-dependent scalars.  It keeps its own device copy of the
+// state (si / sf), and full(b) completes instance b's pattern from that copy with build_pattern the first time an entry needs a list.
 #pragma once
 #include <cstring>
 #include <limits>
+#include <stdexcept>
 
 #include "kernels_batch.h"
 #include "kernels_batch_carry.h"
+#include "kernels_batch_pattern.h"
 #include "kernels_batch_relayout.h"
 #include "solver.h"
 
@@ -53,7 +59,14 @@ struct BatchCore {
     hipStream_t st = nullptr;
     double tol = 1e-9;
     std::vector<double> eta;  // per instance
-    std::vector<HostPattern> H;
+    mutable std::vector<HostPattern> H;  // read through pat(b) / full(b)
+    // built on the device: the state's copy (BatchPatItem says where instance b's lists lie) and, per instance, whether its host lists
+    // are still to be fetched
+    bool on_device = false;
+    std::vector<BatchPatItem> sat;
+    DevBuf<int> si;
+    DevBuf<double> sf;
+    mutable std::vector<char> lazy;
     std::vector<int> nit, iter;
     std::vector<char> active;
     std::vector<BatchDesc> desc;  // offsets and sizes; nrun / iter0 / seed / o_randv are set per call
@@ -61,6 +74,53 @@ struct BatchCore {
     DevBuf<double> fa;
     DevBuf<double> fb, rl;  // a slot change writes the fp64 arena anew into fb and swaps (relayout); rl is that call's upload
     DevBuf<BatchDesc> d_desc;
+    // what every pattern holds from creation on: K, Z, the sizes, l_indptr, S_sum, h_max, norm_H, cH
+    const HostPattern& pat(int b) const { return H[b]; }
+    // the whole pattern; a failure on the way is thrown and reported by the entry (runtime.h guarded)
+    const HostPattern& full(int b) const {
+        if (on_device && lazy[b]) complete(b);
+        return H[b];
+    }
+    void fetch(void* dst, const void* src, size_t bytes) const {
+        if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
+        if (copy_d2h(dst, src, bytes, st) != MMW_OK) throw std::runtime_error("reading the batch's copy of the state: " + last_error_ref());
+    }
+    // Q_asso of instance b from the batch's own copy of the state
+    void fetch_q(int b, std::vector<int32_t>& qp, std::vector<int32_t>& qi, std::vector<double>& qx) const {
+        const BatchPatItem& t = sat[b];
+        const size_t K = (size_t)H[b].K;
+        qp.resize(K + 1);
+        fetch(qp.data(), si.p + t.c_qptr, (K + 1) * sizeof(int32_t));
+        qi.resize((size_t)qp[K]); qx.resize((size_t)qp[K]);
+        fetch(qi.data(), si.p + t.c_qidx, qi.size() * sizeof(int32_t));
+        fetch(qx.data(), sf.p + t.v_qval, qx.size() * sizeof(double));
+    }
+    // S_gain, Q_asso and h_max of instance b from that copy
+    void fetch_state(int b, std::vector<int32_t>& sp, std::vector<int32_t>& six, std::vector<double>& sx, std::vector<int32_t>& qp,
+                     std::vector<int32_t>& qi, std::vector<double>& qx, std::vector<double>& h) const {
+        const BatchPatItem& t = sat[b];
+        const size_t K = (size_t)H[b].K;
+        sp.resize(K + 1); h.resize(K);
+        fetch(sp.data(), si.p + t.c_sptr, (K + 1) * sizeof(int32_t));
+        fetch(h.data(), sf.p + t.v_hmax, K * sizeof(double));
+        six.resize((size_t)sp[K]); sx.resize((size_t)sp[K]);
+        fetch(six.data(), si.p + t.c_sidx, six.size() * sizeof(int32_t));
+        fetch(sx.data(), sf.p + t.v_sval, sx.size() * sizeof(double));
+        fetch_q(b, qp, qi, qx);
+    }
+    void complete(int b) const {
+        std::vector<int32_t> sp, six, qp, qi;
+        std::vector<double> sx, qx, h;
+        fetch_state(b, sp, six, sx, qp, qi, qx, h);
+        HostPattern T;
+        const std::string err = build_pattern(T, H[b].K, H[b].Z, sp.data(), six.data(), sx.data(), qp.data(), qi.data(), qx.data(), h.data());
+        if (!err.empty()) throw std::runtime_error("mmw_batch: instance " + std::to_string(b) + ": completing the host pattern: " + err);
+        if (T.nnzL() != H[b].nnzL() || T.E_asso() != H[b].E_asso() || T.nnzST() != H[b].nnzST() || T.E_gain() != H[b].E_gain())
+            throw std::runtime_error("mmw_batch: instance " + std::to_string(b) + ": the host pattern differs from the one built on the device");
+        T.sq_sum = std::move(H[b].sq_sum);
+        H[b] = std::move(T);
+        lazy[b] = 0;
+    }
     static int host_only_batch() { return fail(MMW_ERR_STATE, "this batch was created with device -1 (host patterns only)"); }
     int check_inst(int b) const {
         if (b < 0 || b >= B) return fail(MMW_ERR_ARG, "mmw_batch: instance index out of range");
@@ -162,10 +222,26 @@ struct BatchCore {
         iter[b] = 0;
         const BatchDesc& d = desc[b];
         std::vector<double> init((size_t)(d.o_info - d.o_lval), 0.0);  // the iterate (lval ... W2) in one copy
-        for (int k = 0; k < d.K; ++k) init[d.o_xval - d.o_lval + H[b].diag_pos[k]] = 1.0;
+        for (int k = 0; k < d.K; ++k) init[d.o_xval - d.o_lval + full(b).diag_pos[k]] = 1.0;
         // the running sums start empty: iteration i adds X_i and Y_i when it starts, so after n iterations they hold X_0 + ... + X_{n-1}
         for (int c = 0; c < d.C; ++c) init[d.o_Y - d.o_lval + c] = 1.0 / (double)d.C;
         return copy_h2d(fa.p + d.o_lval, init.data(), init.size() * sizeof(double), st);
+    }
+    // the same for every instance of a batch built on the device, in one launch (k_batch_pattern_init): no host list is needed
+    int init_point() {
+        constexpr size_t DW = sizeof(BatchDesc) / sizeof(double);
+        std::vector<double> stage(DW * B + (size_t)B);
+        std::memcpy(stage.data(), desc.data(), sizeof(BatchDesc) * B);
+        for (int b = 0; b < B; ++b) {
+            iter[b] = 0;
+            stage[DW * B + b] = 1.0 / (double)desc[b].C;
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(rl.upload(stage, st));
+        hipLaunchKernelGGL(k_batch_pattern_init, dim3(B), dim3(BATCH_THREADS), 0, st, (const BatchDesc*)rl.p, rl.p + DW * B, ia.p, fa.p, 1);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipStreamSynchronize(st));
+        return MMW_OK;
     }
     // A slot change on the device (kernels_batch_relayout.h).  The patterns hold the new slot counts already; mode[b] says what
     // instance b starts from.  One upload -- both descriptor tables, the per-instance items and the host-computed 1 / norm_H and cH --

@@ -34,6 +34,9 @@ struct BatchEpilogue {
     } fs;
     std::vector<RoundLists> rlists;
 
+    // where the rounding lists lie: the upload of round_lists, or the state's copy a batch built on the device keeps (batch_core.h)
+    const int* lists_i(const BatchCore& c) const { return c.on_device ? c.si.p : rs_i.p; }
+    const double* lists_f(const BatchCore& c) const { return c.on_device ? c.sf.p : rs_f.p; }
     void on_restart() { fdesc.clear(); }  // a new run, or buffers laid out anew: the factors held so far are gone
     bool has_factor(int b) const { return !fdesc.empty() && fdesc[b].rank != 0; }
     static int no_factor(const std::string& who, int b) { return fail(MMW_ERR_STATE, who + ": instance " + std::to_string(b) + " has no factor (mmw_batch_factor)"); }
@@ -93,7 +96,7 @@ struct BatchEpilogue {
         if (split) {
             MMW_TRY(factor_split(c, tk, launch));
         } else {
-            hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, c.ia.p, c.fa.p, ew.p, ei.p, rs_i.p, rs_f.p);
+            hipLaunchKernelGGL(k_batch_factor, dim3((unsigned)launch.size()), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, c.ia.p, c.fa.p, ew.p, ei.p, lists_i(c), lists_f(c));
             fs.call[0] = 0.0; fs.call[1] = 1.0; fs.call[2] = 0.0; fs.call[3] = (double)launch.size();
         }
         MMW_HIP(hipGetLastError());
@@ -131,7 +134,7 @@ struct BatchEpilogue {
         MMW_TRY(fs.slab.alloc((size_t)nslot * FSPLIT_SLOT));
         MMW_TRY(fs.rec.alloc((size_t)n * FSPLIT_REC));
         hipLaunchKernelGGL(k_batch_factor_head, dim3((unsigned)n), dim3(BATCH_THREADS), 0, c.st, d_fdesc.p, fs.d_spans.p, c.ia.p, c.fa.p, ew.p, fs.slab.p, fs.rec.p,
-                           rs_i.p, rs_f.p);
+                           lists_i(c), lists_f(c));
         int64_t launches = 1, sweeps = 0;
         size_t widest = std::max((size_t)n, items.size());
         std::vector<char> live((size_t)n, 1);
@@ -245,6 +248,14 @@ struct BatchEpilogue {
     int round_lists(const BatchCore& c) {
         if (!rlists.empty()) return MMW_OK;
         std::vector<RoundLists> rl(c.B);
+        if (c.on_device) {  // the lists are on the device already, in the layout the environment gave them
+            for (int b = 0; b < c.B; ++b) {
+                const BatchPatItem& t = c.sat[b];
+                rl[b] = {t.c_soptr, t.c_soidx, t.c_qptr, t.c_qidx, t.v_soval, t.v_sohmax, t.v_hmax};
+            }
+            rlists = std::move(rl);
+            return MMW_OK;
+        }
         std::vector<int> hi;
         std::vector<double> hf;
         auto pad = [](auto& v) { v.resize((v.size() + 31) & ~(size_t)31); };
@@ -320,8 +331,8 @@ struct BatchEpilogue {
         MMW_TRY(ri.alloc((size_t)oi));
         MMW_TRY(d_rdesc.alloc(rd.size()));
         MMW_TRY(copy_h2d(d_rdesc.p, rd.data(), rd.size() * sizeof(RoundDesc), c.st));
-        hipLaunchKernelGGL(k_batch_round, dim3((unsigned)rd.size()), dim3(BATCH_THREADS), 0, c.st, d_rdesc.p, ew.p, src ? src->si : rs_i.p,
-                           src ? src->sf : rs_f.p, rw.p, ri.p);
+        hipLaunchKernelGGL(k_batch_round, dim3((unsigned)rd.size()), dim3(BATCH_THREADS), 0, c.st, d_rdesc.p, ew.p, src ? src->si : lists_i(c),
+                           src ? src->sf : lists_f(c), rw.p, ri.p);
         MMW_HIP(hipGetLastError());
         MMW_HIP(hipStreamSynchronize(c.st));
         std::vector<int> host((size_t)nback);

@@ -1,5 +1,6 @@
 // The sweeps' greedy baselines in the batched solver (mmw_batch_gm, kernels_batch_gm.h): what the pattern does not keep of Q -- its
 // values, and the clique structure decided at creation (GmState::find_cliques) -- goes up once, beside the epilogue's rounding lists.
+// A batch built on the device (batch_from_env.h) decides it for ALL its instances at the first baseline, from its own copy of Q.
 #pragma once
 #include "batch_epilogue.h"
 #include "kernels_batch_gm.h"
@@ -16,20 +17,33 @@ struct BatchGm {
     DevBuf<int> gm_i;
     DevBuf<double> gm_f;
     GmWork gmw;
-    void extra(const BatchCore& c, int b, const int32_t* Qp, const double* Qx) {
+    bool decided = false;  // a batch built on the device: gmx holds every instance's decision
+    void extra(int b, int32_t K, const int32_t* Qp, const int32_t* Qi, const double* Qx) {
         GmState g;
-        g.K = c.H[b].K;
-        g.q_indptr = c.H[b].q_indptr; g.q_indices = c.H[b].q_indices;
-        g.q_data.assign(Qx, Qx + Qp[g.K]);
+        g.K = K;
+        g.q_indptr.assign(Qp, Qp + K + 1); g.q_indices.assign(Qi, Qi + Qp[K]);
+        g.q_data.assign(Qx, Qx + Qp[K]);
         GmExtra& x = gmx[b];
         x.clique = g.find_cliques();
         x.G = g.G;
         x.grp = std::move(g.grp);
         x.q_data = std::move(g.q_data);
     }
+    // Every instance at once, whichever take part in this call: lists() uploads the decisions of the whole batch one time, so none
+    // may be missing then.  Only Q is fetched; the host patterns stay as they are.
+    void decide_all(const BatchCore& c) {
+        if (!c.on_device || decided) return;
+        std::vector<int32_t> qp, qi;
+        std::vector<double> qx;
+        for (int b = 0; b < c.B; ++b) {
+            c.fetch_q(b, qp, qi, qx);
+            extra(b, c.pat(b).K, qp.data(), qi.data(), qx.data());
+        }
+        decided = true;
+    }
     // the instance's state as the greedy procedures read it (host-only batch)
     GmState state(const BatchCore& c, int b) const {
-        const HostPattern& P = c.H[b];
+        const HostPattern& P = c.full(b);
         GmState g;
         g.K = P.K; g.G = gmx[b].G; g.clique = gmx[b].clique;
         g.so_indptr = P.so_indptr; g.so_indices = P.so_indices; g.so_data = P.so_data;
@@ -58,9 +72,10 @@ struct BatchGm {
         MMW_TRY(batch_gm_args(who, kind, nattempt));
         std::vector<int> tk;
         MMW_TRY(c.takers(who.c_str(), take, tk));
+        decide_all(c);
         for (int b : tk) {
             const std::string inst = who + ": instance " + std::to_string(b);
-            if (c.H[b].K > EPI_MAX_K) return fail(MMW_ERR_ARG, inst + ": K = " + std::to_string(c.H[b].K) + " exceeds the limit " + std::to_string(EPI_MAX_K) + " (it stays on a GreedyHandle)");
+            if (c.pat(b).K > EPI_MAX_K) return fail(MMW_ERR_ARG, inst + ": K = " + std::to_string(c.pat(b).K) + " exceeds the limit " + std::to_string(EPI_MAX_K) + " (it stays on a GreedyHandle)");
             if (!gmx[b].clique) return fail(MMW_ERR_ARG, inst + ": Q_asso is not a union of cliques with weights >= 1 (it stays on a GreedyHandle)");
         }
         if (c.host_only) {
@@ -85,11 +100,11 @@ struct BatchGm {
         std::vector<GmDesc> gd;
         for (int b : tk) {
             GmDesc g{};
-            g.K = c.H[b].K; g.G = gmx[b].G; g.kind = kind; g.Zb = Z[b] <= 0 ? g.K : Z[b]; g.nattempt = nattempt;
+            g.K = c.pat(b).K; g.G = gmx[b].G; g.kind = kind; g.Zb = Z[b] <= 0 ? g.K : Z[b]; g.nattempt = nattempt;
             set_lists(g, epi.rlists[b]);
             g.g_grp = gm_ogrp[b]; g.g_qdata = gm_oq[b];
             gd.push_back(g);
         }
-        return gmw.run(c.st, c.B, tk, gd, epi.rs_i.p, epi.rs_f.p, gm_i.p, gm_f.p, z_out, zz_out, rem_out, key_out);
+        return gmw.run(c.st, c.B, tk, gd, epi.lists_i(c), epi.lists_f(c), gm_i.p, gm_f.p, z_out, zz_out, rem_out, key_out);
     }
 };

@@ -39,7 +39,7 @@ struct mmw_batch {
                 return fail(MMW_ERR_ARG, who + ": K = " + std::to_string(K[b]) + " exceeds the batch limit " + std::to_string(BATCH_MAX_K) + " (run it on a handle)");
             const std::string err = build_pattern(core.H[b], K[b], Z[b], S_indptr[b], S_indices[b], S_data[b], Q_indptr[b], Q_indices[b], Q_data[b], h_max[b]);
             if (!err.empty()) return fail(MMW_ERR_ARG, who + ": " + err);
-            greedy.extra(core, b, Q_indptr[b], Q_data[b]);
+            greedy.extra(b, K[b], Q_indptr[b], Q_indices[b], Q_data[b]);
         }
         if (!core.host_only) {
             MMW_TRY(check_device("mmw_batch_create", device, DEV_ID));
@@ -53,7 +53,7 @@ struct mmw_batch {
     }
     int sizes(int b, int64_t out[10]) const {
         MMW_TRY(core.check_inst(b));
-        const HostPattern& P = core.H[b];
+        const HostPattern& P = core.pat(b);
         const BatchDesc& d = core.desc[b];
         const int64_t v[10] = {P.K, P.Z, d.D, d.D, P.nnzL(), P.nnzST(), P.E_gain(), P.E_asso(), P.C(), core.iter[b]};
         for (int i = 0; i < 10; ++i) out[i] = v[i];
@@ -83,8 +83,9 @@ struct mmw_batch {
         MMW_HIP(hipSetDevice(core.device));
         for (int b = 0; b < core.B; ++b) {
             core.nit[b] = nit_;
-            MMW_TRY(core.reset_one(b));
+            if (!core.on_device) MMW_TRY(core.reset_one(b));
         }
+        if (core.on_device) MMW_TRY(core.init_point());
         return on_restart();
     }
     // Same states, new slot counts: the Z-dependent scalars on the host (update_slots), the arena on the device (BatchCore::relayout).
@@ -176,11 +177,12 @@ struct mmw_batch {
     static int read_host(const std::vector<double>& v, double* out, int64_t n) { return export_vec(v, out, n, "mmw_batch_read_f64"); }
     int read_f64(int b, int which, double* out, int64_t n) {
         MMW_TRY(core.check_inst(b));
-        const HostPattern& P = core.H[b];
+        const HostPattern& P = core.pat(b);
         switch (which) {
             case MMW_F_S_SUM: return read_host(P.S_sum, out, n);
             case MMW_F_NORM_H: return read_host(P.norm_H, out, n);
-            case MMW_F_ST_DATA: return read_host(P.st_data, out, n);
+            case MMW_F_ST_DATA: return read_host(core.full(b).st_data, out, n);
+            case MMW_F_BUILD_INFO: return read_host({core.on_device ? 1.0 : 0.0, core.on_device && core.lazy[b] ? 0.0 : 1.0}, out, n);
             case MMW_F_FACTOR_CALL: return read_host(std::vector<double>(epi.fs.call, epi.fs.call + 4), out, n);
             case MMW_F_SPLIT_CALL: return read_host(std::vector<double>(rows.call, rows.call + 4), out, n);
             case MMW_F_HEAD_CALL: return read_host(std::vector<double>(head.call, head.call + 4), out, n);
@@ -202,6 +204,7 @@ struct mmw_batch {
                 if (core.iter[b] == 0) return fail(MMW_ERR_STATE, "mmw_batch_read_f64: no iteration has run on this instance");
                 return read_dev(d.o_R, KD, out, n);
             case MMW_F_EXPM_INFO: return read_dev(d.o_info, 4, out, n);
+            case MMW_F_PATTERN: return read_dev(d.o_sab, 2 * (int64_t)d.nnzL + 4 * (int64_t)d.K, out, n);
             case MMW_F_FACTOR:
             case MMW_F_FACTOR_ROWNORM:
             case MMW_F_FACTOR_INFO: return epi.read(core, b, which, out, n);
@@ -210,7 +213,16 @@ struct mmw_batch {
     }
     int read_i32(int b, int which, int32_t* out, int64_t n) {
         MMW_TRY(core.check_inst(b));
-        const std::vector<int32_t>* v = host_list_i32(core.H[b], which);
+        if (which == MMW_I_PATTERN) {
+            if (core.host_only) return BatchCore::host_only_batch();
+            const BatchDesc& d = core.desc[b];
+            const int64_t len = d.o_apos + d.E_asso - d.o_indptr;
+            if (n != len) return fail(MMW_ERR_ARG, "mmw_batch_read_i32: wrong length " + std::to_string(n) + ", expected " + std::to_string(len));
+            MMW_HIP(hipSetDevice(core.device));
+            return copy_d2h(out, core.ia.p + d.o_indptr, (size_t)len * sizeof(int32_t), core.st);
+        }
+        if (!host_list_i32(core.pat(b), which)) return fail(MMW_ERR_ARG, "mmw_batch_read_i32: unknown field");  // before a pattern is completed for it
+        const std::vector<int32_t>* v = host_list_i32(which == MMW_I_L_INDPTR ? core.pat(b) : core.full(b), which);
         return v ? export_vec(*v, out, n, "mmw_batch_read_i32") : fail(MMW_ERR_ARG, "mmw_batch_read_i32: unknown field");
     }
     int sketch(int b, uint64_t seed, int32_t iteration, double* out, int64_t n) {
@@ -235,7 +247,7 @@ struct mmw_batch {
         MMW_TRY(core.check_inst(b));
         if (nrows < 1 || nrows > MMW_BATCH_MAX_ROW_PARTS)
             return fail(MMW_ERR_ARG, "mmw_batch_row_ranges: rows = " + std::to_string(nrows) + " is outside [1, " + std::to_string(MMW_BATCH_MAX_ROW_PARTS) + "]");
-        batch_row_bounds(core.H[b].l_indptr.data(), core.H[b].K, nrows, out);
+        batch_row_bounds(core.pat(b).l_indptr.data(), core.pat(b).K, nrows, out);
         return MMW_OK;
     }
     int set_head_split(const int32_t* p) { return head.set(core, p); }
@@ -243,7 +255,7 @@ struct mmw_batch {
         MMW_TRY(core.check_inst(b));
         if (nparts < 1 || nparts > MMW_BATCH_MAX_HEAD_PARTS)
             return fail(MMW_ERR_ARG, "mmw_batch_head_ranges: parts = " + std::to_string(nparts) + " is outside [1, " + std::to_string(MMW_BATCH_MAX_HEAD_PARTS) + "]");
-        batch_row_bounds(core.H[b].l_indptr.data(), core.H[b].K, nparts, out);
+        batch_row_bounds(core.pat(b).l_indptr.data(), core.pat(b).K, nparts, out);
         return MMW_OK;
     }
     int set_factor_split(const int32_t* p) { return epi.set_split(core, p); }
@@ -262,11 +274,11 @@ struct mmw_batch {
 // mmw_batch_export: the instance's iterate into an fp64 handle of the same (state, Z), as if the handle had run those iterations.
 inline int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {
     const BatchDesc& d = bt->core.desc[b];
-    const HostPattern& P = bt->core.H[b];
     if (s->core.host_only || bt->core.host_only) return fail(MMW_ERR_STATE, "mmw_batch_export: host-only batch or handle");
     if (s->core.device != bt->core.device) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle lives on another device");
     if (s->core.K != d.K || s->core.Z != d.Z || s->core.D != d.D || s->core.H.nnzL() != (int64_t)d.nnzL || s->core.H.C() != (int64_t)d.C)
         return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's K / Z / nnzL do not match the instance's");
+    const HostPattern& P = bt->core.full(b);
     if (s->core.H.l_indices != P.l_indices || s->core.H.l_indptr != P.l_indptr) return fail(MMW_ERR_ARG, "mmw_batch_export: the handle's pattern is not the instance's");
     MMW_HIP(hipSetDevice(s->core.device));
     MMW_TRY(s->settle());
@@ -301,9 +313,9 @@ inline int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {
 }
 // what mmw_batch_carry and mmw_batch_carry_map ask of one instance of the pair before either looks at its patterns
 inline int batch_carry_pair(const char* who, const mmw_batch* dst, const mmw_batch* src, int b) {
-    if (dst->core.H[b].K != src->core.H[b].K)
-        return fail(MMW_ERR_ARG, std::string(who) + ": instance " + std::to_string(b) + ": K = " + std::to_string(dst->core.H[b].K) + " here, K = " +
-                                     std::to_string(src->core.H[b].K) + " in the source (a carry keeps the users and moves them)");
+    if (dst->core.pat(b).K != src->core.pat(b).K)
+        return fail(MMW_ERR_ARG, std::string(who) + ": instance " + std::to_string(b) + ": K = " + std::to_string(dst->core.pat(b).K) + " here, K = " +
+                                     std::to_string(src->core.pat(b).K) + " in the source (a carry keeps the users and moves them)");
     return MMW_OK;
 }
 // mmw_batch_carry_map: the two index maps of one instance (BatchCore::carry_maps); host patterns only, so device -1 batches answer too
@@ -311,11 +323,11 @@ inline int batch_carry_map(mmw_batch* dst, mmw_batch* src, int b, int32_t* lmap,
     MMW_TRY(dst->core.check_inst(b));
     MMW_TRY(src->core.check_inst(b));
     MMW_TRY(batch_carry_pair("mmw_batch_carry_map", dst, src, b));
-    const HostPattern& N = dst->core.H[b];
+    const HostPattern& N = dst->core.full(b);
     if (nl != N.nnzL() || nc != N.C())
         return fail(MMW_ERR_ARG, "mmw_batch_carry_map: instance " + std::to_string(b) + ": wrong lengths " + std::to_string(nl) + ", " + std::to_string(nc) +
                                      ", expected nnzL = " + std::to_string(N.nnzL()) + " and C = " + std::to_string(N.C()));
-    BatchCore::carry_maps(N, src->core.H[b], lmap, cmap);
+    BatchCore::carry_maps(N, src->core.full(b), lmap, cmap);
     return MMW_OK;
 }
 // mmw_batch_carry: (e_accu, L, X, Y) of `src`, a batch on the old states that has iterated, re-indexed onto `dst`, a batch on the new
@@ -345,19 +357,19 @@ inline int batch_carry(mmw_batch* dst, mmw_batch* src, const int32_t* take) {
     static_assert(sizeof(CarryItem) % sizeof(double) == 0, "the staging buffer is one array of doubles");
     const size_t n = go.size();
     int64_t words = 0;  // int32 map entries of the call
-    for (int b : go) words += D.H[b].nnzL() + D.H[b].C();
+    for (int b : go) words += D.pat(b).nnzL() + D.pat(b).C();
     const size_t w_src = 0, w_dst = w_src + DW * n, w_item = w_dst + DW * n, w_map = w_item + IW * n;
     std::vector<double> stage(w_map + (size_t)((words + 1) / 2), 0.0);
     int32_t* maps = reinterpret_cast<int32_t*>(stage.data() + w_map);
     int64_t om = 0;
     for (size_t t = 0; t < n; ++t) {
         const int b = go[t];
-        const HostPattern& N = D.H[b];
+        const HostPattern& N = D.full(b);
         std::memcpy(stage.data() + w_src + DW * t, &S.desc[b], sizeof(BatchDesc));
         std::memcpy(stage.data() + w_dst + DW * t, &D.desc[b], sizeof(BatchDesc));
         const CarryItem it{om, om + N.nnzL()};
         std::memcpy(stage.data() + w_item + IW * t, &it, sizeof it);
-        BatchCore::carry_maps(N, S.H[b], maps + it.o_lmap, maps + it.o_cmap);
+        BatchCore::carry_maps(N, S.full(b), maps + it.o_lmap, maps + it.o_cmap);
         om += N.nnzL() + N.C();
     }
     MMW_HIP(hipSetDevice(D.device));

@@ -36,7 +36,7 @@ struct BatchHead {
             ns += 2 * (int64_t)d.K;
             const int hp = parts[b];
             bd.resize((size_t)hp + 1);
-            batch_row_bounds(c.H[b].l_indptr.data(), d.K, hp, bd.data());
+            batch_row_bounds(c.pat(b).l_indptr.data(), d.K, hp, bd.data());
             for (int p = 0; p < hp; ++p) wk.push_back(HeadWork{b, p, hp, bd[p], bd[p + 1]});
         }
         MMW_TRY(d_work.upload(wk, c.st));

@@ -39,7 +39,7 @@ struct BatchRows {
             const int cp = colparts.empty() ? 1 : colparts[b], rp = rows[b];
             const int W = split_width(d.D, cp), G = split_slices(d.D, cp), sid0 = nsid;
             bd.resize((size_t)rp + 1);
-            batch_row_bounds(c.H[b].l_indptr.data(), d.K, rp, bd.data());
+            batch_row_bounds(c.pat(b).l_indptr.data(), d.K, rp, bd.data());
             for (int g = 0; g < G; ++g) {
                 for (int p = 0; p < rp; ++p) wk.push_back(RowsWork{b, g, W, p, rp, bd[p], bd[p + 1], (int)nslab, nsid});
                 nslab += (int64_t)rp * W;

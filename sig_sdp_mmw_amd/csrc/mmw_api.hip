@@ -1,6 +1,7 @@
 // C-ABI of the MI355X MMW hot path (include/mmw_hip.h), the library's one translation unit.  The handles: solver.h (mmw_solver, mmw_env),
-// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch: batch_core.h and the parts' headers), batch_env_handle.h (mmw_batch_env).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
+// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch: batch_core.h and the parts' headers), batch_env_handle.h (mmw_batch_env), batch_from_env.h (a batch built from an environment on the device).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
 #include "batch_env_handle.h"
+#include "batch_from_env.h"
 #include "batch_handle.h"
 #include "gm_handle.h"
 
@@ -270,6 +271,17 @@ int mmw_batch_env_evaluate(mmw_batch_env* e, const double* const* z_vec, const i
                            double* const* sinr_out, double* const* bler_out) {
     return entry("mmw_batch_env", !e || !z_vec || !Z || !sinr_out, "mmw_batch_env_evaluate: null pointer",
                  [&] { return e->evaluate(z_vec, Z, packet_bit, bandwidth, slot_time, sinr_out, bler_out); });
+}
+int mmw_batch_create_from_env(mmw_batch** out, mmw_batch_env* env, const int32_t* Z, int32_t rank_radio, double eta, const int32_t* nit) {
+    return guarded("mmw_batch", [&]() -> int {
+        if (!out || !env || !Z || !nit) return fail(MMW_ERR_ARG, "mmw_batch_create_from_env: null pointer");
+        if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
+        if (!(eta >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
+        auto bt = std::make_unique<mmw_batch>();
+        MMW_TRY(batch_init_from_env(*bt, *env, Z, rank_radio, eta, nit));
+        *out = bt.release();
+        return MMW_OK;
+    });
 }
 int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out,
                      int32_t* rem_out, double* key_out) {

@@ -36,8 +36,9 @@ struct HostPattern {
     // A handle built on the device (pattern_device.h) keeps the lists that only the API's reads need on the device until someone asks:
     // their sizes are known from the count pass (>= 0 here), and sq_sum stands in for the pass over st_data in update_slots.
     int64_t n_st = -1, n_gain = -1, n_asso = -1;
+    int64_t n_l = -1;            // a batch built on the device (batch_from_env.h) also leaves l_indices there until someone asks
     std::vector<double> sq_sum;  // [K] sum_j S_T'[k][j]^2 (ascending j)
-    int64_t nnzL() const { return (int64_t)l_indices.size(); }
+    int64_t nnzL() const { return n_l >= 0 ? n_l : (int64_t)l_indices.size(); }
     int64_t nnzST() const { return n_st >= 0 ? n_st : (int64_t)st_indices.size(); }
     int64_t E_asso() const { return n_asso >= 0 ? n_asso : (int64_t)asso_x.size(); }
     int64_t E_gain() const { return n_gain >= 0 ? n_gain : (int64_t)gain_x.size(); }
