@@ -274,6 +274,48 @@ int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, in
 int mmw_env_bounds(mmw_env* e, int32_t out[2]);
 
 /*
+ * A state that lives on the device as its seven CSR arrays, and the solver handle built from it there: the way in for a graph
+ * that is not the generator's (csrc/csr_device.h, csrc/pattern_csr_device.h).  S_gain and Q_asso are (indptr int32 [K+1], indices
+ * int32 [nnz], data float64 [nnz]), h_max float64 [K].  nnzS and nnzQ are announced by the caller: the library never learns an
+ * array's length from the array.  K >= 1 and 0 <= nnz < 2^31 here; the solver's own limits come with the handle.
+ *
+ * mmw_csr_upload: the library makes and owns device copies of seven host arrays (device == -1: host copies, no HIP call).
+ * mmw_csr_wrap: seven DEVICE pointers are borrowed: the caller keeps them alive and unchanged while the mmw_csr lives, the arrays
+ * must be complete when any call that reads them is made, and every call has finished reading when it returns.  A null pointer
+ * is allowed exactly where its length is 0 (indices / data of a matrix without stored entries).
+ * mmw_csr_sizes: out = {K, 0, nnzS, nnzQ}.  mmw_csr_pointers: the seven device pointers in the argument order of wrap (null for
+ * an empty array, all null with device -1).  mmw_csr_state: the host copy of the state, made on request into caller-sized arrays.
+ * mmw_csr_bounds: the bisection's bounds of binary_search_relaxation.py:13-29, out = {lower, upper}, from a count pass on the
+ * device: lower = longest row of Q + 1, upper = max over rows a of #{j != a : S[a][j] != 0 or S[j][a] != 0} + 2 (for a
+ * non-negative S what the host expression on S + S^T gives).  It validates the arrays first, as the creator below does.
+ *
+ * mmw_create_from_csr: mmw_create for the state `csr` holds, built by kernels: validation, the filtered S and the rounding's lists,
+ * S_T' by column counts, placement and a per-row ranking, the L / X pattern by a count pass, host prefix sums and a fill pass in
+ * which every entry finds its own place, pair ids, edge lists, mirrors, row statistics.  The handle is bit for bit the one
+ * mmw_create makes from the same arrays -- same lists, same values, the same locality blocking (built on the host from the column
+ * indices, as there) -- and the lists only the read entries hand out stay on the device until asked for.
+ * Validation comes first and refuses with MMW_ERR_ARG and build_pattern's words, the first error being the lowest (kind, row) in
+ * this order: indptr[0] != 0; indptr decreasing; indptr[K] != the nnz announced; column out of range; row unsorted or
+ * duplicated; stored zero in Q; diagonal in Q; Q asymmetric; then K < 2; Z < 2; a zero norm_H; nnz(L) beyond int32.  The indptr
+ * arrays are checked before anything reads indices, the column ranges before any column is used as an address.
+ * The handle keeps no reference to `csr` after the call returns.  With a host-only `csr` the handle is mmw_create's with device -1.
+ */
+typedef struct mmw_csr mmw_csr;
+int mmw_csr_upload(mmw_csr** out, int device, int32_t K, int64_t nnzS, int64_t nnzQ, const int32_t* S_indptr,
+                   const int32_t* S_indices, const double* S_data, const int32_t* Q_indptr, const int32_t* Q_indices,
+                   const double* Q_data, const double* h_max);
+int mmw_csr_wrap(mmw_csr** out, int device, int32_t K, int64_t nnzS, int64_t nnzQ, const int32_t* S_indptr,
+                 const int32_t* S_indices, const double* S_data, const int32_t* Q_indptr, const int32_t* Q_indices,
+                 const double* Q_data, const double* h_max);
+int mmw_csr_destroy(mmw_csr* c);
+int mmw_csr_sizes(mmw_csr* c, int64_t out[4]);
+int mmw_csr_pointers(mmw_csr* c, void* out[7]);
+int mmw_csr_state(mmw_csr* c, int32_t* S_indptr, int32_t* S_indices, double* S_data, int32_t* Q_indptr, int32_t* Q_indices,
+                  double* Q_data, double* h_max);
+int mmw_csr_bounds(mmw_csr* c, int32_t out[2]);
+int mmw_create_from_csr(mmw_solver** out, mmw_csr* csr, int dtype, int32_t Z, int32_t rank_radio, double eta, int32_t nit);
+
+/*
  * The greedy baselines of sim_src/alg/gm.py on a light handle (csrc/kernels_gm.h): no MMW pattern, no blocking.
  *
  * mmw_gm_create: the per-call preparation of MAX_GAIN.run / MAX_ASSO.run / MAX_RAND.run (gm.py:11-18, 74-80, 136-142), once per state:

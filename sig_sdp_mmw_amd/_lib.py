@@ -44,7 +44,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
-           "mmw_batch_create_from_env"]
+           "mmw_batch_create_from_env", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
+           "mmw_csr_bounds", "mmw_create_from_csr"]
 
 
 class MMWError(RuntimeError):
@@ -100,6 +101,14 @@ def lib():
     L.mmw_env_evaluate.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_double, C.c_double, C.c_double, p_f64, p_f64]
     L.mmw_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.mmw_env_bounds.argtypes = [C.c_void_p, p_i32]
+    for fn in (L.mmw_csr_upload, L.mmw_csr_wrap):  # (wrap's seven are device addresses: plain integers here)
+        fn.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int64, C.c_int64] + [C.c_void_p] * 7
+    L.mmw_csr_destroy.argtypes = [C.c_void_p]
+    L.mmw_csr_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.mmw_csr_pointers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mmw_csr_state.argtypes = [C.c_void_p, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64]
+    L.mmw_csr_bounds.argtypes = [C.c_void_p, p_i32]
+    L.mmw_create_from_csr.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.mmw_gm_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64]
     L.mmw_gm_destroy.argtypes = [C.c_void_p]
     L.mmw_gm_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -292,6 +301,19 @@ class Solver(_Handle):
         self = cls.__new__(cls)
         self._h = C.c_void_p()
         check(lib().mmw_create_from_env(C.byref(self._h), env._h, int(dtype), int(Z), int(rank_radio), float(eta), int(nit)))
+        self._load_sizes()
+        self.dtype = dtype
+        self._timing = False
+        self._timed = 0
+        return self
+
+    @classmethod
+    def from_csr(cls, csr, Z, nit, eta, rank_radio=2, dtype=F64):
+        """The handle for the state a DeviceCSR holds, built on the device from its seven arrays (mmw_create_from_csr): bit for bit
+        the handle `Solver(Z, csr.state(), ...)` is."""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        check(lib().mmw_create_from_csr(C.byref(self._h), csr._h, int(dtype), int(Z), int(rank_radio), float(eta), int(nit)))
         self._load_sizes()
         self.dtype = dtype
         self._timing = False
@@ -1008,6 +1030,9 @@ class DeviceEnv(_Handle):
         check(lib().mmw_env_bounds(self._h, _pi(out)))
         return int(out[0]), int(out[1])
 
+    def solver(self, Z, nit, eta, rank_radio=2, dtype=F64):
+        return Solver.from_env(self, Z, nit, eta, rank_radio=rank_radio, dtype=dtype)
+
     def device_state(self):
         """The `state` to hand to the solver classes: behaves like the (S_gain, Q_asso, h_max) tuple (materialised on the host only if
         someone indexes it), and lets `mmw` / `binary_search_relaxation` stay on the device (Solver.from_env, bounds())."""
@@ -1083,8 +1108,150 @@ class BatchEnv(_Handle):
         return _gm_call(lib().mmw_batch_env_gm, self._h, self.B, self.Ks, who, kind, Zs, nattempt, t, keys)
 
 
+_CSR_NAMES = ("S_indptr", "S_indices", "S_data", "Q_indptr", "Q_indices", "Q_data", "h_max")
+_CSR_TYPES = ("int32", "int32", "float64", "int32", "int32", "float64", "float64")
+_TYPESTR = {"<i4": "int32", "<i8": "int64", "<f8": "float64", "<f4": "float32"}
+
+
+def _device_array(a, name, want, length):
+    """(address, object to keep alive) of one of wrap's seven arrays: an int address (taken at its word: the lengths are the caller's),
+    an object with data_ptr() / numel() (a torch tensor), or one with __cuda_array_interface__.  dtype and length are checked."""
+    if isinstance(a, (int, np.integer)) or a is None:
+        addr = int(a or 0)
+        if addr == 0 and length:
+            raise MMWError("DeviceCSR.wrap: %s is a null address but its length is %d" % (name, length))
+        return addr, None
+    if hasattr(a, "data_ptr") and hasattr(a, "numel"):
+        dt, n, addr = str(a.dtype).split(".")[-1], int(a.numel()), int(a.data_ptr())
+        if hasattr(a, "is_contiguous") and not a.is_contiguous():
+            raise MMWError("DeviceCSR.wrap: %s must be contiguous" % name)
+        if getattr(getattr(a, "device", None), "type", "cuda") == "cpu":
+            raise MMWError("DeviceCSR.wrap: %s lies on the host (wrap borrows device arrays: use DeviceCSR.upload)" % name)
+    elif hasattr(a, "__cuda_array_interface__"):
+        d = a.__cuda_array_interface__
+        if d.get("strides") is not None:
+            raise MMWError("DeviceCSR.wrap: %s must be contiguous" % name)
+        dt, n, addr = _TYPESTR.get(d["typestr"], d["typestr"]), int(np.prod(d["shape"], dtype=np.int64)), int(d["data"][0] or 0)
+    else:
+        raise MMWError("DeviceCSR.wrap: %s must be a device address, a tensor (data_ptr / numel) or a __cuda_array_interface__ object" % name)
+    if dt != want:
+        hint = " (convert the indices to int32 first: they are not converted silently)" if dt == "int64" else ""
+        raise MMWError("DeviceCSR.wrap: %s is %s, must be %s%s" % (name, dt, want, hint))
+    if n != length:
+        raise MMWError("DeviceCSR.wrap: %s has %d elements, must have %d" % (name, n, length))
+    return (addr if n else 0), a
+
+
+class DeviceCSR(_Handle):
+    """Owning wrapper of one `mmw_csr*`: a state on the device as its seven CSR arrays -- uploaded once (`upload`) or borrowed from
+    whoever built the graph on the GPU (`wrap`, `from_torch`).  `Solver.from_csr` builds the handle from it on the device; `bounds()`
+    gives the bisection's bounds from a device count pass; `device_state()` is the `state` the solver classes take."""
+    _destroy = "mmw_csr_destroy"
+
+    @classmethod
+    def _new(cls, device):
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        self.device = int(device)
+        self._keep = None
+        return self
+
+    def _created(self):
+        sz = (C.c_int64 * 4)()
+        check(lib().mmw_csr_sizes(self._h, sz))
+        self.K, self.nnzS, self.nnzQ = int(sz[0]), int(sz[2]), int(sz[3])
+        return self
+
+    @classmethod
+    def upload(cls, state, device=0):
+        """Device copies of a host state (S_gain, Q_asso, h_max), owned by the library; device = -1 keeps host copies (CPU tests)."""
+        K, arrs = _state_arrays(state)
+        return cls.upload_arrays(K, arrs, device)
+
+    @classmethod
+    def upload_arrays(cls, K, arrays, device=0):
+        """`upload` for the seven arrays as they are (int32 / float64, not canonicalised: what the validation is tested with)."""
+        sp, si, sx, qp, qi, qx, hm = [np.ascontiguousarray(a, dtype=t) for a, t in zip(arrays, _CSR_TYPES)]
+        if sp.size != K + 1 or qp.size != K + 1 or hm.size != K or si.size != sx.size or qi.size != qx.size:
+            raise MMWError("DeviceCSR: indptr arrays of K + 1 entries, h_max of K, indices and data of one length each")
+        self = cls._new(device)
+        ptr = [C.c_void_p(a.ctypes.data if a.size else None) for a in (sp, si, sx, qp, qi, qx, hm)]
+        check(lib().mmw_csr_upload(C.byref(self._h), self.device, int(K), int(si.size), int(qi.size), *ptr))
+        return self._created()
+
+    @classmethod
+    def wrap(cls, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max, K, device=0, nnzS=None, nnzQ=None):
+        """Borrow seven device arrays (see `_device_array` for what an array may be).  nnzS / nnzQ: needed when the arrays are plain
+        addresses, else taken from S_indices / Q_indices.  The arrays must stay alive and unchanged while this object lives (objects are
+        kept referenced here; addresses are the caller's to keep) and be complete when a call that reads them is made."""
+        arrs = (S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max)
+        K = int(K)
+
+        def count(a, given, name):
+            if given is not None:
+                return int(given)
+            if hasattr(a, "numel"):
+                return int(a.numel())
+            if hasattr(a, "__cuda_array_interface__"):
+                return int(np.prod(a.__cuda_array_interface__["shape"], dtype=np.int64))
+            raise MMWError("DeviceCSR.wrap: %s is needed when the arrays are given as addresses" % name)
+        ns, nq = count(S_indices, nnzS, "nnzS"), count(Q_indices, nnzQ, "nnzQ")
+        lengths = (K + 1, ns, ns, K + 1, nq, nq, K)
+        got = [_device_array(a, n, t, m) for a, n, t, m in zip(arrs, _CSR_NAMES, _CSR_TYPES, lengths)]
+        self = cls._new(device)
+        self._keep = [g[1] for g in got]
+        check(lib().mmw_csr_wrap(C.byref(self._h), self.device, K, ns, nq, *[C.c_void_p(g[0] or None) for g in got]))
+        return self._created()
+
+    @classmethod
+    def from_torch(cls, S, Q, h_max):
+        """Borrow a state that torch holds on the ROCm device: S, Q sparse-CSR tensors (float64 values), h_max dense float64.  The index
+        arrays are converted to int32 on the device (torch keeps int64); torch's current stream is synchronised, so the arrays are
+        complete; the tensors stay referenced by this object.  (A torch build that ships its own HIP runtime has to touch the device
+        before this library makes its first HIP call in the process -- bench.py's order -- or torch finds no device.)"""
+        import torch  # (only here: the product imports without torch)
+        if S.layout != torch.sparse_csr or Q.layout != torch.sparse_csr:
+            raise MMWError("DeviceCSR.from_torch: S and Q must be sparse-CSR tensors")
+        if not S.is_cuda or not Q.is_cuda or not h_max.is_cuda:
+            raise MMWError("DeviceCSR.from_torch: the tensors must lie on the ROCm device")
+        K = int(S.shape[0])
+        parts = []
+        for m in (S, Q):
+            parts += [m.crow_indices().to(torch.int32).contiguous(), m.col_indices().to(torch.int32).contiguous(), m.values().to(torch.float64).contiguous()]
+        parts.append(h_max.to(torch.float64).contiguous())
+        torch.cuda.current_stream(S.device).synchronize()
+        return cls.wrap(*parts, K=K, device=S.device.index or 0)
+
+    def _closing(self):
+        self._keep = None
+
+    def state(self):
+        """(S_gain csr, Q_asso csr, h_max): the host copy, made on request."""
+        return _state_out(self.K, self.nnzS, self.nnzQ, lambda *a: check(lib().mmw_csr_state(self._h, *a)))
+
+    def bounds(self):
+        """(lower, upper) slot-count bounds of binary_search_relaxation.py:13-29 for this state, from a count pass on the device."""
+        out = np.zeros(2, dtype=np.int32)
+        check(lib().mmw_csr_bounds(self._h, _pi(out)))
+        return int(out[0]), int(out[1])
+
+    def pointers(self):
+        """The seven device addresses in `wrap`'s order (0 for an empty array)."""
+        out = (C.c_void_p * 7)()
+        check(lib().mmw_csr_pointers(self._h, out))
+        return [int(p or 0) for p in out]
+
+    def solver(self, Z, nit, eta, rank_radio=2, dtype=F64):
+        return Solver.from_csr(self, Z, nit, eta, rank_radio=rank_radio, dtype=dtype)
+
+    def device_state(self):
+        """The `state` to hand to the solver classes (see DeviceEnv.device_state): handles by Solver.from_csr, bounds from bounds()."""
+        return DeviceState(self)
+
+
 class DeviceState:
-    """`state` of a DeviceEnv: a lazy (S_gain, Q_asso, h_max) triple that remembers where it lives."""
+    """`state` of a DeviceEnv or a DeviceCSR (anything with K, state(), bounds() and solver(Z, nit, eta, rank_radio, dtype)): a lazy
+    (S_gain, Q_asso, h_max) triple that remembers where it lives."""
 
     def __init__(self, env):
         self.env = env

@@ -26,7 +26,7 @@ class binary_search_relaxation(STATS_OBJECT):
 
     def set_bounds(self, state):
         if hasattr(state, "env") and hasattr(state.env, "bounds") and not (self.force_lower_bound or self.force_full_bound):
-            return state.env.bounds()  # a device-resident state (_lib.DeviceState): the same bounds from the device's count pass
+            return state.env.bounds()  # a device-resident state (_lib.DeviceState of a DeviceEnv or a DeviceCSR): the same bounds from a count pass on the device
         S, Q = state[0], state[1]
         if self.force_lower_bound:
             lb = int(np.max(np.diff(Q.indptr))) + 1

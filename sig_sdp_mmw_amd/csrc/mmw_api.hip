@@ -37,6 +37,57 @@ int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, in
     });
 }
 int mmw_env_bounds(mmw_env* e, int32_t out[2]) { return entry("mmw_env_bounds", !e || !out, "null pointer", [&] { return e->e.bounds(out); }); }
+// ---- a state on the device as its seven CSR arrays (csr_device.h) and the handle built from it there (solver_create.h: init_csr)
+static int csr_make(const char* who, bool borrow, mmw_csr** out, int device, int32_t K, int64_t nnzS, int64_t nnzQ, const int32_t* Sp, const int32_t* Si, const double* Sx,
+                    const int32_t* Qp, const int32_t* Qi, const double* Qx, const double* h) {
+    return guarded(who, [&]() -> int {
+        if (!out) return fail(MMW_ERR_ARG, std::string(who) + ": null pointer");
+        *out = nullptr;
+        MMW_TRY(CsrDevice::check_sizes(who, K, nnzS, nnzQ));
+        if (!Sp || !Qp || !h || (nnzS && (!Si || !Sx)) || (nnzQ && (!Qi || !Qx))) return fail(MMW_ERR_ARG, std::string(who) + ": null pointer (an array may be null only where its length is 0)");
+        if (borrow && device == -1) return fail(MMW_ERR_ARG, std::string(who) + ": device -1 (host only) has no device pointers to borrow: use mmw_csr_upload");
+        if (device != -1) MMW_TRY(check_device(who, device, DEV_ID_VISIBLE));
+        auto c = std::make_unique<mmw_csr>();
+        MMW_TRY(borrow ? c->c.wrap(device, K, nnzS, nnzQ, Sp, Si, Sx, Qp, Qi, Qx, h) : c->c.upload(device, K, nnzS, nnzQ, Sp, Si, Sx, Qp, Qi, Qx, h));
+        *out = c.release();
+        return MMW_OK;
+    });
+}
+int mmw_csr_upload(mmw_csr** out, int device, int32_t K, int64_t nnzS, int64_t nnzQ, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
+                   const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max) {
+    return csr_make("mmw_csr_upload", false, out, device, K, nnzS, nnzQ, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
+}
+int mmw_csr_wrap(mmw_csr** out, int device, int32_t K, int64_t nnzS, int64_t nnzQ, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
+                 const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max) {
+    return csr_make("mmw_csr_wrap", true, out, device, K, nnzS, nnzQ, S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max);
+}
+int mmw_csr_destroy(mmw_csr* c) { return guarded("mmw_csr_destroy", [&]() -> int { delete c; return MMW_OK; }); }
+int mmw_csr_sizes(mmw_csr* c, int64_t out[4]) {
+    return entry("mmw_csr_sizes", !c || !out, "null pointer", [&] {
+        out[0] = c->c.V.K; out[1] = 0; out[2] = c->c.V.nnzS; out[3] = c->c.V.nnzQ;
+        return MMW_OK;
+    });
+}
+int mmw_csr_pointers(mmw_csr* c, void* out[7]) {
+    return entry("mmw_csr_pointers", !c || !out, "null pointer", [&] {
+        c->c.pointers(out);
+        return MMW_OK;
+    });
+}
+int mmw_csr_state(mmw_csr* c, int32_t* S_indptr, int32_t* S_indices, double* S_data, int32_t* Q_indptr, int32_t* Q_indices, double* Q_data, double* h_max) {
+    return entry("mmw_csr_state", !c || !S_indptr || !Q_indptr || !h_max || (c && c->c.V.nnzS && (!S_indices || !S_data)) || (c && c->c.V.nnzQ && (!Q_indices || !Q_data)),
+                 "mmw_csr_state: null pointer", [&] { return c->c.state(S_indptr, S_indices, S_data, Q_indptr, Q_indices, Q_data, h_max); });
+}
+int mmw_csr_bounds(mmw_csr* c, int32_t out[2]) { return entry("mmw_csr_bounds", !c || !out, "null pointer", [&] { return c->c.bounds(out); }); }
+int mmw_create_from_csr(mmw_solver** out, mmw_csr* csr, int dtype, int32_t Z, int32_t rank_radio, double eta, int32_t nit) {
+    return guarded("mmw_create_from_csr", [&]() -> int {
+        if (!out || !csr) return fail(MMW_ERR_ARG, "mmw_create_from_csr: null pointer");
+        *out = nullptr;
+        if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
+        if (nit < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
+        return create_solver(out, dtype, csr->c.host_only, [&](auto& s) { return std::decay_t<decltype(s)>::Create::init_csr(s, csr->c, Z, rank_radio, eta, nit); });
+    });
+}
 int mmw_destroy(mmw_solver* s) { return guarded("mmw_destroy", [&]() -> int { delete s; return MMW_OK; }); }
 int mmw_sizes(mmw_solver* s, int64_t out[10]) { return entry("mmw_sizes", !s, "null solver handle", [&] { return s->sizes(out); }); }
 int mmw_set_expm(mmw_solver* s, int method, int max_order, double tol) { return entry("mmw_set_expm", !s, "null solver handle", [&] { return s->set_expm(method, max_order, tol); }); }

@@ -2,7 +2,7 @@
 // mmw_api.hip includes this once).  The body holds a core (solver_core.h: device, pattern, iterate, engine, blockings, timers) and its
 // parts by value, each with the state and the device buffers of one concern: loop (solver_loop.h: the phases, their scratch, the chunk
 // policy), pending and emax (solver_replay.h: the chunk not yet settled, the riding MMW_F_E_MAX), reads (solver_read.h), envl
-// (solver_create.h: the lists a handle made from a generator still holds on the device), extras (solver_extras.h).  An ABI method is the
+// (solver_create.h: the lists a handle built on the device -- from a generator or from CSR arrays -- still holds there), extras (solver_extras.h).  An ABI method is the
 // device guard, `settle`, and one call into a part; whatever a new run invalidates in a part goes through on_restart.
 #pragma once
 #include "solver_bench.h"
@@ -13,6 +13,9 @@
 
 struct mmw_env {
     mmw::EnvDevice e;
+};
+struct mmw_csr {
+    mmw::CsrDevice c;
 };
 struct mmw_solver {
     virtual ~mmw_solver() {}
@@ -44,7 +47,7 @@ template <typename T> struct Solver final : mmw_solver {
     PendingChunk<T> pending;
     EmaxRecord emax;
     SolverReads<T> reads;
-    EnvLists envl;
+    DeviceLists envl;
     Extras<T> extras;
     explicit Solver(const Switches& s) : core(s), loop(core.sw), extras(core.sw) {}
     ~Solver() override {
@@ -53,7 +56,7 @@ template <typename T> struct Solver final : mmw_solver {
         (void)hipSetDevice(core.device);
         if (core.st) (void)hipStreamDestroy(core.st);
     }
-    using Create = SolverCreate<T>;  // mmw_create / mmw_create_from_env call Create::init / Create::init_env on a fresh handle
+    using Create = SolverCreate<T>;  // mmw_create / mmw_create_from_env / mmw_create_from_csr call Create::init / init_env / init_csr on a fresh handle
     int sizes(int64_t out[10]) override {
         const HostPattern& H = core.H;
         out[0] = core.K; out[1] = core.Z; out[2] = core.D; out[3] = core.eng.lay.Dpad; out[4] = H.nnzL(); out[5] = H.nnzST();
@@ -341,7 +344,7 @@ int expm_apply_impl(const Switches& sw, int device, int method, int max_order, d
     if (kernel_us) *kernel_us = us / reps;
     return MMW_OK;
 }
-// mmw_create / mmw_create_from_env: a handle of the asked dtype, initialised by `init` (SolverCreate<T>::init or init_env), handed out on success
+// mmw_create / mmw_create_from_env / mmw_create_from_csr: a handle of the asked dtype, initialised by `init` (SolverCreate<T>::init, init_env or init_csr), handed out on success
 template <typename Init> int create_solver(mmw_solver** out, int dtype, bool host_only, Init&& init) {
     auto make = [&](auto s) {
         s->core.host_only = host_only;

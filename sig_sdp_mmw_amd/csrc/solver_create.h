@@ -1,8 +1,10 @@
-// Creation of the solver handle (solver.h): mmw_create (host CSR arrays -> pattern -> uploads) and mmw_create_from_env (the generator's device
-// state -> pattern on the device), and what both share once the pattern is on the device: the iterate's buffers, the engine, the buffers the
+// Creation of the solver handle (solver.h): mmw_create (host CSR arrays -> pattern -> uploads), mmw_create_from_env (the generator's device
+// state -> pattern on the device) and mmw_create_from_csr (seven CSR arrays on the device -> pattern on the device), and what all share
+// once the pattern is on the device: the iterate's buffers, the engine, the buffers the
 // parts would otherwise allocate on first use, the locality blockings, the rounding side.  Nothing here is read after the handle is handed
-// out except EnvLists, through which a handle made from a generator fetches the lists that only the API's read fields hand out.
+// out except DeviceLists, through which a handle built on the device fetches the lists that only the API's read fields hand out.
 #pragma once
+#include "csr_device.h"
 #include "solver_loop.h"
 #include "solver_read.h"
 #include "solver_replay.h"
@@ -13,7 +15,7 @@ template <typename T> struct Solver;
 // per-entry arrays, the edge lists and the row statistics by the kernels of pattern_device.h; the host gets the row pointers (from
 // the count pass's prefix sums), the column indices (the blockings read them) and three K-vectors.  The lists that only the
 // API's read fields hand out stay on the device until asked for (ensure_host).
-struct EnvLists {  // device copies kept for ensure_host
+struct DeviceLists {  // device copies kept for ensure_host (a handle built on the device, from a generator or from CSR arrays)
     DevBuf<int> st_ptr, st_idx, gain_x, gain_y, asso_x, asso_y, gu_ptr, qu_ptr, so_ptr;
     DevBuf<double> st_val, s_sum, sq_sum;
     bool host_done = true;  // false: H's list vectors are still empty
@@ -35,6 +37,14 @@ struct EnvLists {  // device copies kept for ensure_host
         host_done = true;
         return MMW_OK;
     }
+};
+// Where the rounding side (Extras) of a handle built on the device takes its lists from: Q and h_max are copied device to device; S_gain
+// without its diagonal is either compacted here from the generator's CSR (s_*) or already lies in Extras (so_filled: init_csr's fill pass)
+struct RoundSource {
+    const int* q_ptr = nullptr; const int* q_idx = nullptr; int64_t nnzQ = 0;
+    const double* h_max = nullptr;
+    const int* s_ptr = nullptr; const int* s_idx = nullptr; const double* s_val = nullptr;
+    bool so_filled = false;
 };
 // Row order of a geometric instance: boustrophedon strips about one block wide (blocking.h: consecutive runs of it are compact patches)
 inline std::vector<int32_t> spatial_order(int K, const std::vector<double>& xy, int rows_per_block) {
@@ -126,11 +136,11 @@ template <typename T> struct SolverCreate {
         MMW_TRY(co.d_sab.upload_cast(co.H.sab, co.st));
         MMW_TRY(co.d_sba.upload_cast(co.H.sba, co.st));
         MMW_TRY(co.upload_row_vectors());
-        return init_common(s, t_0, t_1, t_struct, /*env=*/nullptr);
+        return init_common(s, t_0, t_1, t_struct, /*round_src=*/nullptr);
     }
     static int init_env(Solver<T>& s, int dev, EnvDevice& E, int32_t Z_, int32_t rr, double eta_, int32_t nit_) {
         SolverCore<T>& co = s.core;
-        EnvLists& envl = s.envl;
+        DeviceLists& envl = s.envl;
         co.device = dev;
         const double t_0 = tnow();
         if (Z_ < 2) return fail(MMW_ERR_ARG, "mmw_create_from_env: Z must be >= 2 (the constraints divide by Z-1)");
@@ -202,27 +212,154 @@ template <typename T> struct SolverCreate {
         MMW_TRY(co.upload_row_vectors());
         envl.host_done = false;
         const double t_1 = tnow();
-        return init_common(s, t_0, t_1, t_struct, &E);
+        RoundSource R;
+        R.q_ptr = E.q_ptr.p; R.q_idx = E.q_idx.p; R.nnzQ = E.nnzQ; R.h_max = E.h_max.p;
+        R.s_ptr = E.s_ptr.p; R.s_idx = E.s_idx.p; R.s_val = E.s_val.p;
+        return init_common(s, t_0, t_1, t_struct, &R);
     }
-    static int init_extras_env(SolverCore<T>& co, EnvLists& envl, Extras<T>& extras, EnvDevice& E) {
+    // ---- mmw_create_from_csr: build_pattern on the device, from seven CSR arrays that lie there (pattern_csr_device.h).  Three round trips:
+    // {validation verdict, row counts of S}, {row statistics, row counts of L}, {the column indices, for the host-side blockings}.
+    static int init_csr(Solver<T>& s, CsrDevice& Cs, int32_t Z_, int32_t rr, double eta_, int32_t nit_) {
+        const char* who = "mmw_create_from_csr";
+        SolverCore<T>& co = s.core;
+        DeviceLists& dl = s.envl;
+        const CsrView V = Cs.V;
+        const int K = V.K;
+        if (co.host_only) {  // device -1: the shared per-row checks in a plain loop, then build_pattern on the host copies
+            MMW_TRY(Cs.validate(who));
+            return init(s, -1, K, Z_, rr, eta_, nit_, V.Sp, V.Si, V.Sx, V.Qp, V.Qi, V.Qx, V.h);
+        }
+        co.device = Cs.device;
+        const double t_0 = tnow();
+        MMW_HIP(hipSetDevice(co.device));
+        MMW_HIP(hipStreamCreateWithFlags(&co.st, hipStreamNonBlocking));
+        const int gk = grid_rows(K);
+        const size_t Ks = (size_t)K;
+        // validation (unless the state already has its verdict) and the first count pass, which runs only if every check passed
+        if (Cs.checked) MMW_TRY(Cs.verdict(who));
+        else MMW_TRY(Cs.enqueue_checks(co.st));
+        DevBuf<int> cnt, nfnew;  // cnt: [4][K] = n_so, n_f, st_cnt, n_qu; later n_l, n_gu, the placement cursors
+        MMW_TRY(cnt.alloc(4 * Ks)); MMW_TRY(nfnew.alloc(Ks));
+        MMW_HIP(hipMemsetAsync(cnt.p, 0, 4 * Ks * sizeof(int), co.st));
+        hipLaunchKernelGGL(k_csrpat_count, dim3(gk), dim3(BLOCK), 0, co.st, V, (const unsigned long long*)Cs.d_err.p, cnt.p, cnt.p + Ks, cnt.p + 2 * Ks, cnt.p + 3 * Ks);
+        MMW_HIP(hipGetLastError());
+        if (!Cs.checked) {
+            MMW_TRY(copy_d2h(Cs.err, Cs.d_err.p, sizeof Cs.err, co.st));
+            Cs.checked = true;
+            MMW_TRY(Cs.verdict(who));
+        }
+        if (K < 2) return fail(MMW_ERR_ARG, std::string(who) + ": K must be >= 2");
+        if (Z_ < 2) return fail(MMW_ERR_ARG, std::string(who) + ": Z must be >= 2 (the constraints divide by Z-1)");
+        std::vector<int32_t> h_cnt(4 * Ks);
+        MMW_TRY(copy_d2h(h_cnt.data(), cnt.p, h_cnt.size() * sizeof(int32_t), co.st));
+        std::vector<int32_t> so_ptr(Ks + 1, 0), f_ptr(Ks + 1, 0), st_ptr(Ks + 1, 0), qu_ptr(Ks + 1, 0), gu_ptr(Ks + 1, 0);
+        for (size_t k = 0; k < Ks; ++k) {  // (every total is at most nnz(S) or nnz(Q): int32)
+            so_ptr[k + 1] = so_ptr[k] + h_cnt[k];
+            f_ptr[k + 1] = f_ptr[k] + h_cnt[Ks + k];
+            st_ptr[k + 1] = st_ptr[k] + h_cnt[2 * Ks + k];
+            qu_ptr[k + 1] = qu_ptr[k] + h_cnt[3 * Ks + k];
+        }
+        const size_t nso = (size_t)so_ptr[K], nst = (size_t)st_ptr[K], na = (size_t)qu_ptr[K];
+        if ((size_t)f_ptr[K] != nst) return fail(MMW_ERR_STATE, std::string(who) + ": internal: the transpose lost entries");
+        DevBuf<int> d_fptr, f_idx, fx, tmp_idx;
+        DevBuf<double> f_val, tmp_val;
+        Extras<T>& ex = s.extras;
+        MMW_TRY(dl.so_ptr.upload(so_ptr, co.st)); MMW_TRY(d_fptr.upload(f_ptr, co.st)); MMW_TRY(dl.st_ptr.upload(st_ptr, co.st)); MMW_TRY(dl.qu_ptr.upload(qu_ptr, co.st));
+        MMW_TRY(ex.so_indices.alloc(nso)); MMW_TRY(ex.so_data.alloc(nso)); MMW_TRY(ex.so_hmax.alloc(nso));
+        MMW_TRY(f_idx.alloc(nst)); MMW_TRY(f_val.alloc(nst)); MMW_TRY(fx.alloc(nst)); MMW_TRY(tmp_idx.alloc(nst)); MMW_TRY(tmp_val.alloc(nst));
+        MMW_TRY(dl.st_idx.alloc(nst)); MMW_TRY(dl.st_val.alloc(nst)); MMW_TRY(dl.s_sum.alloc(Ks)); MMW_TRY(dl.sq_sum.alloc(Ks));
+        int* cursor = cnt.p + 2 * Ks;
+        MMW_HIP(hipMemsetAsync(cursor, 0, Ks * sizeof(int), co.st));
+        hipLaunchKernelGGL(k_csrpat_fill, dim3(gk), dim3(BLOCK), 0, co.st, V, (const int*)dl.so_ptr.p, (const int*)d_fptr.p, (const int*)dl.st_ptr.p, cursor, ex.so_indices.p,
+                           ex.so_data.p, ex.so_hmax.p, f_idx.p, f_val.p, tmp_idx.p, tmp_val.p);
+        hipLaunchKernelGGL(k_csrpat_sort_rows, dim3(gk), dim3(BLOCK), 0, co.st, K, (const int*)dl.st_ptr.p, (const int*)tmp_idx.p, (const double*)tmp_val.p, dl.st_idx.p, dl.st_val.p);
+        hipLaunchKernelGGL(k_pat_rowstats, dim3(grid_elems(Ks)), dim3(BLOCK), 0, co.st, K, dl.st_ptr.p, dl.st_val.p, dl.s_sum.p, dl.sq_sum.p);
+        hipLaunchKernelGGL(k_csrpat_count_L, dim3(gk), dim3(BLOCK), 0, co.st, V, (const int*)dl.st_ptr.p, (const int*)dl.st_idx.p, (const int*)d_fptr.p, (const int*)f_idx.p, fx.p,
+                           nfnew.p, cnt.p, cnt.p + Ks);
+        MMW_HIP(hipGetLastError());
+        co.K = K; co.Z = Z_; co.rank_radio = rr; co.eta = eta_; co.nit = nit_;
+        co.D = co.Z * co.rank_radio;
+        co.H.K = K; co.H.Z = Z_;
+        co.H.S_sum.resize(Ks); co.H.sq_sum.resize(Ks); co.H.h_max.resize(Ks);
+        MMW_TRY(copy_d2h(co.H.S_sum.data(), dl.s_sum.p, Ks * sizeof(double), co.st));
+        MMW_TRY(copy_d2h(co.H.sq_sum.data(), dl.sq_sum.p, Ks * sizeof(double), co.st));
+        MMW_TRY(copy_d2h(co.H.h_max.data(), V.h, Ks * sizeof(double), co.st));
+        MMW_TRY(copy_d2h(h_cnt.data(), cnt.p, 2 * Ks * sizeof(int32_t), co.st));
+        co.H.norm_H.assign(Ks, 0.0);
+        co.H.cH.assign(Ks, 0.0);
+        co.H.n_st = (int64_t)nst; co.H.n_asso = (int64_t)na;
+        co.H.st_indptr = st_ptr;
+        {
+            const std::string err = update_slots(co.H, co.Z);
+            if (!err.empty()) return fail(MMW_ERR_ARG, std::string(who) + ": " + err);
+        }
+        co.H.l_indptr.assign(Ks + 1, 0);
+        for (size_t k = 0; k < Ks; ++k) {
+            if ((int64_t)co.H.l_indptr[k] + h_cnt[k] > (int64_t)INT32_MAX) return fail(MMW_ERR_ARG, std::string(who) + ": pattern too large for int32 indexing");
+            co.H.l_indptr[k + 1] = co.H.l_indptr[k] + h_cnt[k];
+            gu_ptr[k + 1] = gu_ptr[k] + h_cnt[Ks + k];
+        }
+        const size_t nnz = (size_t)co.H.l_indptr[K], ng = (size_t)gu_ptr[K];
+        co.H.n_gain = (int64_t)ng;
+        MMW_TRY(co.d_indptr.upload(co.H.l_indptr, co.st)); MMW_TRY(dl.gu_ptr.upload(gu_ptr, co.st));
+        MMW_TRY(co.d_col.alloc(nnz)); MMW_TRY(co.d_lrow.alloc(nnz)); MMW_TRY(co.d_sab.alloc(nnz)); MMW_TRY(co.d_sba.alloc(nnz)); MMW_TRY(co.d_pid.alloc(nnz)); MMW_TRY(co.d_mirror.alloc(nnz));
+        MMW_TRY(co.d_diag.alloc(Ks)); MMW_TRY(co.d_apos.alloc(na));
+        MMW_TRY(dl.gain_x.alloc(ng)); MMW_TRY(dl.gain_y.alloc(ng)); MMW_TRY(dl.asso_x.alloc(na)); MMW_TRY(dl.asso_y.alloc(na));
+        DevBuf<int> internal;
+        MMW_TRY(internal.alloc(1));
+        MMW_HIP(hipMemsetAsync(internal.p, 0, sizeof(int), co.st));
+        CsrPatOut<T> O;
+        O.l_ptr = co.d_indptr.p; O.st_ptr = dl.st_ptr.p; O.f_ptr = d_fptr.p; O.qu_ptr = dl.qu_ptr.p;
+        O.st_idx = dl.st_idx.p; O.st_val = dl.st_val.p; O.f_idx = f_idx.p; O.f_val = f_val.p; O.fx = fx.p; O.n_fnew = nfnew.p;
+        O.l_idx = co.d_col.p; O.lrow = co.d_lrow.p; O.sab = co.d_sab.p; O.sba = co.d_sba.p; O.pid = co.d_pid.p; O.diag_pos = co.d_diag.p;
+        O.asso_x = dl.asso_x.p; O.asso_y = dl.asso_y.p; O.asso_pos = co.d_apos.p; O.internal = internal.p;
+        hipLaunchKernelGGL((k_csrpat_fill_L<T>), dim3(gk), dim3(BLOCK), 0, co.st, V, O);
+        MMW_HIP(hipGetLastError());
+        // the column indices first: the host-side blockings (mmw_create's own: the pattern-only order, grown blocks) start on them while the
+        // device finishes the rest
+        co.H.l_indices.resize(nnz);
+        MMW_TRY(copy_d2h(co.H.l_indices.data(), co.d_col.p, nnz * sizeof(int32_t), co.st));
+        const double t_struct = tnow();
+        co.bt.want_mfma(K, Z_ * rr, co.sw);
+        if (!co.sw.no_blocking) co.bt.build_thread = std::thread([pc = &co]() { pc->bt.host_blockings(pc->H, pc->sw); });
+        hipLaunchKernelGGL(k_csrpat_gain_edges, dim3(gk), dim3(BLOCK), 0, co.st, K, (const int*)co.d_indptr.p, (const int*)co.d_col.p, (const int*)co.d_pid.p, (const int*)dl.gu_ptr.p,
+                           dl.gain_x.p, dl.gain_y.p);
+        hipLaunchKernelGGL(k_pat_mirror, dim3(grid_elems(nnz)), dim3(BLOCK), 0, co.st, nnz, co.d_indptr.p, co.d_col.p, co.d_lrow.p, co.d_mirror.p);
+        MMW_HIP(hipGetLastError());
+        int h_internal = 0;
+        MMW_TRY(copy_d2h(&h_internal, internal.p, sizeof(int), co.st));
+        if (h_internal) {
+            co.bt.join();
+            return fail(MMW_ERR_ARG, std::string(who) + ": internal: gain edge on an association pair");
+        }
+        MMW_TRY(co.upload_row_vectors());
+        dl.host_done = false;
+        const double t_1 = tnow();
+        RoundSource R;
+        R.q_ptr = V.Qp; R.q_idx = V.Qi; R.nnzQ = V.nnzQ; R.h_max = V.h; R.so_filled = true;
+        return init_common(s, t_0, t_1, t_struct, &R);
+    }
+    static int init_extras_device(SolverCore<T>& co, DeviceLists& envl, Extras<T>& extras, const RoundSource& R) {
         MMW_TRY(extras.init_device(co.st, co.K, &co.kt));
         std::vector<int32_t> so_ptr_h((size_t)co.K + 1);
         MMW_TRY(copy_d2h(so_ptr_h.data(), envl.so_ptr.p, so_ptr_h.size() * sizeof(int32_t), co.st));
         const size_t nso = (size_t)so_ptr_h[co.K];
         MMW_TRY(extras.so_indptr.upload(so_ptr_h, co.st));
-        MMW_TRY(extras.so_indices.alloc(nso)); MMW_TRY(extras.so_data.alloc(nso)); MMW_TRY(extras.so_hmax.alloc(nso));
-        MMW_TRY(extras.q_indptr.alloc((size_t)co.K + 1)); MMW_TRY(extras.q_indices.alloc((size_t)E.nnzQ)); MMW_TRY(extras.h_max.alloc(co.K));
-        hipLaunchKernelGGL(k_pat_so_fill, dim3(grid_rows(co.K)), dim3(BLOCK), 0, co.st, co.K, (const int*)E.s_ptr.p, (const int*)E.s_idx.p, (const double*)E.s_val.p,
-                           (const int*)extras.so_indptr.p, (const double*)E.h_max.p, extras.so_indices.p, extras.so_data.p, extras.so_hmax.p);
-        MMW_HIP(hipGetLastError());
-        MMW_HIP(hipMemcpyAsync(extras.q_indptr.p, E.q_ptr.p, ((size_t)co.K + 1) * sizeof(int), hipMemcpyDeviceToDevice, co.st));
-        MMW_HIP(hipMemcpyAsync(extras.q_indices.p, E.q_idx.p, (size_t)E.nnzQ * sizeof(int), hipMemcpyDeviceToDevice, co.st));
-        MMW_HIP(hipMemcpyAsync(extras.h_max.p, E.h_max.p, (size_t)co.K * sizeof(double), hipMemcpyDeviceToDevice, co.st));
+        MMW_TRY(extras.q_indptr.alloc((size_t)co.K + 1)); MMW_TRY(extras.q_indices.alloc((size_t)R.nnzQ)); MMW_TRY(extras.h_max.alloc(co.K));
+        if (!R.so_filled) {
+            MMW_TRY(extras.so_indices.alloc(nso)); MMW_TRY(extras.so_data.alloc(nso)); MMW_TRY(extras.so_hmax.alloc(nso));
+            hipLaunchKernelGGL(k_pat_so_fill, dim3(grid_rows(co.K)), dim3(BLOCK), 0, co.st, co.K, R.s_ptr, R.s_idx, R.s_val, (const int*)extras.so_indptr.p, R.h_max,
+                               extras.so_indices.p, extras.so_data.p, extras.so_hmax.p);
+            MMW_HIP(hipGetLastError());
+        }
+        MMW_HIP(hipMemcpyAsync(extras.q_indptr.p, R.q_ptr, ((size_t)co.K + 1) * sizeof(int), hipMemcpyDeviceToDevice, co.st));
+        if (R.nnzQ) MMW_HIP(hipMemcpyAsync(extras.q_indices.p, R.q_idx, (size_t)R.nnzQ * sizeof(int), hipMemcpyDeviceToDevice, co.st));
+        MMW_HIP(hipMemcpyAsync(extras.h_max.p, R.h_max, (size_t)co.K * sizeof(double), hipMemcpyDeviceToDevice, co.st));
         MMW_HIP(hipStreamSynchronize(co.st));
         return MMW_OK;
     }
     // ---- everything after the pattern is on the device: the iterate's buffers, the engine, the blockings, the rounding side
-    static int init_common(Solver<T>& s, double t_0, double t_1, double t_struct, EnvDevice* env) {
+    static int init_common(Solver<T>& s, double t_0, double t_1, double t_struct, const RoundSource* round_src) {
         SolverCore<T>& co = s.core;
         const bool verbose = live_switch(LIVE_VERBOSE);
         MMW_TRY(co.alloc_iterate());
@@ -241,7 +378,7 @@ template <typename T> struct SolverCreate {
         MMW_TRY(s.reads.resize(co));
         MMW_TRY(s.loop.resize(co));
         MMW_HIP(hipStreamSynchronize(co.st));
-        if (env) MMW_TRY(init_extras_env(co, s.envl, s.extras, *env));
+        if (round_src) MMW_TRY(init_extras_device(co, s.envl, s.extras, *round_src));
         else MMW_TRY(s.extras.init(co.st, &co.H, co.K, &co.kt));
         return s.reset(co.nit);
     }

@@ -34,6 +34,7 @@ def _order_mode(order):
 
 
 def _host_state(state):
+    """The host triple: a device-resident state (of a DeviceEnv or a DeviceCSR) hands out its host copy, made once (GreedyHandle takes host arrays)."""
     return state.host() if isinstance(state, _lib.DeviceState) else state
 
 

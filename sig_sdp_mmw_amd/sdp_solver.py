@@ -59,9 +59,9 @@ class sdp_solver:
                 s.set_slots(max(int(Z), 2), max(int(nit), 1), warm=warm)
             return s
         self.close()
-        if isinstance(state, _lib.DeviceState):  # straight from the device generator: no host copy of the state at all
-            s = _lib.Solver.from_env(state.env, max(int(Z), 2), max(int(nit), 1), 0.1 if eta is None else eta, rank_radio=self.rank_radio,
-                                     dtype=self._dtype_code)
+        if isinstance(state, _lib.DeviceState):  # straight from the device (a generator's state or CSR arrays): no host copy of the state at all
+            s = state.env.solver(max(int(Z), 2), max(int(nit), 1), 0.1 if eta is None else eta, rank_radio=self.rank_radio,
+                                 dtype=self._dtype_code)
             self._dev = (None, state, s)
             return s
         s = _lib.Solver(max(int(Z), 2), state, max(int(nit), 1), 0.1 if eta is None else eta, rank_radio=self.rank_radio,
