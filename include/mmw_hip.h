@@ -78,8 +78,8 @@ enum mmw_field {
                              the first call; batches only */
     MMW_F_FACTOR_ROWNORM = 23, /* [K] after mmw_batch_factor_spectral: every user's row norm of the K x Z eigenvector block BEFORE its rows
                              were normalised (0: the row is exactly zero and stayed so).  The top eigenvectors are localised: a user with
-                             a tiny norm here has a row of amplified rounding noise in MMW_F_FACTOR.  MMW_ERR_STATE on any other factor;
-                             batches only */
+                             a tiny norm here has a row of amplified rounding noise in MMW_F_FACTOR.  MMW_ERR_STATE on any other factor.
+                             A solver handle answers it the same way after mmw_factor_spectral (MMW_ERR_STATE after mmw_factor) */
     MMW_F_HEAD_CALL = 24,   /* [4]    the last mmw_batch_iterate of a batch, kept on the host, the same for every instance: {on: 1 while the
                              head split ran (mmw_batch_set_head_split), else 0; launches of the head path's own kernels (k_batch_head_*)
                              enqueued; workgroups of the widest of them; 0}; zeros before the first call and with the head split off;
@@ -89,6 +89,14 @@ enum mmw_field {
     MMW_F_BUILD_INFO = 26,  /* [2]    live, per instance: {how the batch was built: 0 from host arrays (mmw_batch_create), 1 on the
                              device (mmw_batch_create_from_env); 1 while the instance's host lists are complete, 0 while a batch built on
                              the device has not fetched them yet}; batches only */
+    MMW_F_LAPLACIAN = 27,   /* [nnzL] the Laplacian of S_gain + S_gain^T (diagonal zeroed; sdp_solver.py:173-176) on the L pattern, fp64:
+                             -(S[r,c] + S[c,r]) off the diagonal (0 where the pattern holds the entry through Q alone), the sum of
+                             S[r,c] + S[c,r] over the row's off-diagonal entries in ascending column order on it.  Built on the first
+                             call that asks; a device -1 handle answers it too; solver handles only */
+    MMW_F_SPECTRAL_INFO = 28, /* [8]  the last mmw_factor_spectral: {outer rounds completed before the Rayleigh-Ritz step that ended it, last
+                             relative residual, Z, block width b, theta_Z, theta_Z+1 (0 when b = Z), filter passes that ran on the matrix
+                             cores, 0}; zeros before the first call; solver handles only */
+    MMW_F_SPECTRAL_EIG = 29,  /* [Z]  the Ritz values the last mmw_factor_spectral kept, ascending (the block's column order) */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -204,6 +212,21 @@ int mmw_gap(mmw_solver* s, double out[3]);
 int mmw_factor(mmw_solver* s, int32_t rank, double* out, uint64_t seed);
 
 /*
+ * mmw_factor_spectral: sdp_solver.spectral_sdp_solver.run_with_state (sdp_solver.py:165-185) on a handle, any K.  The Z eigenvectors
+ * of largest eigenvalue of the Laplacian of S_gain + S_gain^T (MMW_F_LAPLACIAN) by mmw_factor's own iteration -- the Laplacian is
+ * positive semidefinite, so largest |lambda| is largest lambda -- as a K x Z block, columns in ascending eigenvalue like eigsh
+ * (signs arbitrary), every row divided by its norm; a row whose norm is exactly 0 (an isolated user) stays 0 where the reference
+ * divides by zero.  index_order = 1: row k is then multiplied by 1 - k 2^-32 (rand_sdp_solver.index_ordered, bit for bit), so that the
+ * rounding visits the unit rows in index order.  out: K*Z float64, or NULL: the block stays on the device for mmw_round(gX == NULL)
+ * and MMW_F_FACTOR, as after mmw_factor.  MMW_F_FACTOR_ROWNORM hands out the norms before the division, MMW_F_SPECTRAL_INFO and
+ * MMW_F_SPECTRAL_EIG the call's record.  Stops at mmw_factor's tolerance (relative residual 1e-9 in fp64, 2e-5 in fp32; the
+ * reference asks eigsh for 1e-5); MMW_ERR_STATE when the iteration does not converge.  The handle's slot count, its iterate and its
+ * sums play no part and do not move.  Z outside [1, K] or index_order outside {0, 1}: MMW_ERR_ARG before anything else; a device -1
+ * handle: MMW_ERR_STATE.
+ */
+int mmw_factor_spectral(mmw_solver* s, int32_t Z, int32_t index_order, double* out, uint64_t seed);
+
+/*
  * mmw_expm_apply: the stand-alone seam mmw.expm_half_randsk (mmw.py:224-229) minus the draw:
  * out[K,D] = exp(A) B for a symmetric CSR matrix A (pattern arbitrary) and a dense block B.
  * info (may be NULL): one-norm bound, order m, substeps, shift.  `reps` > 1 repeats the device work
@@ -227,7 +250,7 @@ int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t 
  * entry: inprod = randv gX^T on the fp64 matrix cores, per-user slot preference order, the greedy
  * feasibility assignment in descending ||gX_k|| order.  z_out[nbatch,K] gets the slot or -1 for a user
  * left unassigned (the caller draws those, sdp_solver.py:104-105); rem_out[nbatch] the count.
- * gX == NULL: the K x Dp factor mmw_factor computed last on this handle, read where it lies on the device.
+ * gX == NULL: the K x Dp factor mmw_factor (or the block mmw_factor_spectral) computed last on this handle, read where it lies on the device.
  * Ties: equal norms are visited by lower user index, equal inner products prefer the lower slot.  Zr > 4800 (32 Zr bytes
  * of flags beyond the greedy kernel's LDS) is refused with MMW_ERR_ARG before anything is allocated, copied, launched or timed.
  */

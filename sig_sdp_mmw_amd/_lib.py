@@ -25,6 +25,9 @@ F_SPLIT_CALL = 22
 F_HEAD_CALL = 24
 BATCH_F_PATTERN = 25  # (named apart from the F_ ids both kinds of handle share) batches: the pattern part of the fp64 arena [2 nnzL + 4 K]: sab, sba, h_max, S_sum, 1 / norm_H, cH
 BATCH_F_BUILD_INFO = 26  # batches, per instance: {0 built from host arrays / 1 on the device, 1 once the host lists are complete}
+SOLVER_F_LAPLACIAN = 27  # solver handles: the Laplacian of S_gain + S_gain^T on the L pattern [nnzL]
+SOLVER_F_SPECTRAL_INFO = 28  # solver handles: the last mmw_factor_spectral's record [8]
+SOLVER_F_SPECTRAL_EIG = 29  # solver handles: the Ritz values it kept, ascending [Z]
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
 BATCH_MAX_HEAD_PARTS = 64  # MMW_BATCH_MAX_HEAD_PARTS: head parts per instance at most (mmw_batch_set_head_split)
@@ -45,7 +48,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
-           "mmw_csr_bounds", "mmw_create_from_csr"]
+           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral"]
 
 
 class MMWError(RuntimeError):
@@ -89,6 +92,7 @@ def lib():
     L.mmw_read_i32.argtypes = [C.c_void_p, C.c_int, p_i32, C.c_int64]
     L.mmw_gap.argtypes = [C.c_void_p, p_f64]
     L.mmw_factor.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_uint64]
+    L.mmw_factor_spectral.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
     L.mmw_sym_eig.argtypes = [C.c_int, C.c_int32, p_f64, C.c_double, C.c_int32, p_f64, p_f64, C.POINTER(C.c_int32)]
     L.mmw_expm_apply.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int32, C.c_int32, p_i32, p_i32, p_f64,
                                  p_f64, p_f64, p_f64, C.c_int32, p_f64]
@@ -254,7 +258,7 @@ def _state_out(K, nnzS, nnzQ, fill):
 # mmw_read_f64 / mmw_read_i32: the size a field's length is (mmw_sizes' names), for the int fields (size, + offset)
 _SIZE_NAMES = ("K", "Z", "D", "Dpad", "nnzL", "nnzST", "E_gain", "E_asso", "C", "iter")
 _LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", F_XAVG: "nnzL", F_YAVG: "C",
-        F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST"}
+        F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST", SOLVER_F_LAPLACIAN: "nnzL", F_FACTOR_ROWNORM: "K"}
 _ILEN = {I_L_INDPTR: ("K", 1), I_L_INDICES: ("nnzL", 0), I_ST_INDPTR: ("K", 1), I_ST_INDICES: ("nnzST", 0), I_GAIN_X: ("E_gain", 0),
          I_GAIN_Y: ("E_gain", 0), I_ASSO_X: ("E_asso", 0), I_ASSO_Y: ("E_asso", 0), I_DIAG_POS: ("K", 0), I_ASSO_POS: ("E_asso", 0)}
 
@@ -459,6 +463,45 @@ class Solver(_Handle):
         check(lib().mmw_factor(self._h, int(rank), _pd(out), C.c_uint64(int(seed))))
         self._factor_serial = getattr(self, "_factor_serial", 0) + 1
         return out
+
+    def factor_spectral(self, Z, seed=0, resident=False, index_order=False):
+        """spectral_sdp_solver.run_with_state (sdp_solver.py:165-185) on this handle's state, any K (mmw_factor_spectral): the K x Z
+        block of the Laplacian's Z eigenvectors of largest eigenvalue, columns in ascending eigenvalue (signs arbitrary), every row
+        divided by its norm; an exactly zero row stays zero.  index_order=True: `rand_sdp_solver.index_ordered` of that block, bit for
+        bit.  resident=True: a `DeviceFactor` (its `index_ordered` says which of the two it is) that `round` reads where it lies.
+        The handle's own slot count plays no part."""
+        self._keep_resident_factor()
+        Z, io = int(Z), 1 if index_order else 0
+        if resident:
+            check(lib().mmw_factor_spectral(self._h, Z, io, None, C.c_uint64(int(seed))))
+            self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+            df = DeviceFactor(self, Z, self._factor_serial, index_ordered=bool(io))
+            self._resident = weakref.ref(df)
+            return df
+        out = np.empty((self.K, max(Z, 0)), dtype=np.float64)  # (a Z out of range is the library's to refuse)
+        check(lib().mmw_factor_spectral(self._h, Z, io, _pd(out), C.c_uint64(int(seed))))
+        self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+        return out
+
+    def laplacian(self):
+        """The Laplacian of S_gain + S_gain^T (diagonal zeroed) on the L pattern, float64 [nnzL] in `read_i32(I_L_INDICES)`'s order
+        (MMW_F_LAPLACIAN); a device = -1 handle answers it too."""
+        return self.read(SOLVER_F_LAPLACIAN)
+
+    def spectral_info(self):
+        """The last `factor_spectral`: {"outer", "resid", "Z", "block", "theta_Z", "theta_next" (0 when block = Z), "mfma_passes"}."""
+        v = self.read(SOLVER_F_SPECTRAL_INFO, 8)
+        return {"outer": int(v[0]), "resid": float(v[1]), "Z": int(v[2]), "block": int(v[3]), "theta_Z": float(v[4]), "theta_next": float(v[5]),
+                "mfma_passes": int(v[6])}
+
+    def spectral_eig(self, Z):
+        """The Z Ritz values the last `factor_spectral` kept, ascending (the block's column order)."""
+        return self.read(SOLVER_F_SPECTRAL_EIG, int(Z))
+
+    def factor_row_norms(self):
+        """After `factor_spectral`: every user's row norm of the eigenvector block before its rows were normalised
+        (MMW_F_FACTOR_ROWNORM); status -3 after any other factor."""
+        return self.read(F_FACTOR_ROWNORM)
 
     def _keep_resident_factor(self):
         """A resident factor somebody still holds is copied out before the handle overwrites it (next factor) or goes away (close)."""
@@ -969,8 +1012,9 @@ class DeviceFactor(np.lib.mixins.NDArrayOperatorsMixin):
     `run_with_state` straight to `rounding` (binary_search_relaxation.py:50-53): `Solver.round` recognises this object and reads the factor
     where it lies.  For everything else it is an array: `np.asarray`, arithmetic, indexing and attribute access copy it out (once)."""
 
-    def __init__(self, solver, rank, serial):
+    def __init__(self, solver, rank, serial, index_ordered=False):
         self._solver, self._serial, self._host = solver, serial, None
+        self.index_ordered = index_ordered  # True: a block of unit rows already scaled for the index-order visit (Solver.factor_spectral)
         self.shape, self.ndim, self.dtype = (solver.K, rank), 2, np.dtype(np.float64)
 
     def on_device_of(self, solver):

@@ -13,6 +13,7 @@
 #include "expm_engine.h"
 #include "kernels_dense.h"
 #include "kernels_loop.h"
+#include "kernels_spectral.h"
 #include "runtime.h"
 
 namespace mmw {
@@ -186,6 +187,16 @@ template <typename T> struct DenseWork {
     }
 };
 
+// What run() fills when it exports eigenvectors (mmw_factor_spectral) instead of V sqrt|theta|: the same loop, another last step.
+struct EigExport {
+    int index_order = 0;        // in: 1 = rows scaled by 1 - k 2^-32 after the division (rand_sdp_solver.index_ordered)
+    double* rownorm = nullptr;  // in: device [K], gets the row norms before the division
+    std::vector<double> eig;    // out: the kept Ritz values, ascending
+    double theta_next = 0.0;    // out: the first Ritz value left out (0 when the block is no wider than the rank)
+    int block = 0;              // out: block width b
+    int mf_passes = 0;          // out: filter passes that ran on the matrix cores
+};
+
 template <typename T> struct Factorizer {
     const Switches& sw;
     explicit Factorizer(const Switches& s) : sw(s), dw(s) {}
@@ -336,8 +347,10 @@ template <typename T> struct Factorizer {
         return MMW_OK;
     }
     // factor of A = ascale * (values `val` on the pattern).  out: K*rank float64 (host), or nullptr
-    int run(const int* indptr, const int* col, const T* val, double ascale, int rank, uint64_t seed, double* out) {
-        if (rank < 1 || rank >= K + 1) return fail(MMW_ERR_ARG, "mmw_factor: rank must be in [1, K]");
+    // eig != nullptr: the row-normalised eigenvector block of the top `rank` instead (k_export_eigvec), everything up to the export unchanged
+    int run(const int* indptr, const int* col, const T* val, double ascale, int rank, uint64_t seed, double* out, EigExport* eig = nullptr) {
+        const std::string who = eig ? "mmw_factor_spectral" : "mmw_factor";
+        if (rank < 1 || rank >= K + 1) return fail(MMW_ERR_ARG, who + ": rank must be in [1, K]");
         const bool verbose = live_switch(LIVE_FACTOR_VERBOSE);
         auto vnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double v_t0 = vnow();
@@ -346,7 +359,7 @@ template <typename T> struct Factorizer {
         const int b = block_width(K, rank);  // small or nearly full: one exact Rayleigh-Ritz on the whole space
         BlockLayout lay;
         std::string err;
-        if (make_layout(b, V16<T>::N, lay, err) != MMW_OK) return fail(MMW_ERR_ARG, "mmw_factor: " + err);
+        if (make_layout(b, V16<T>::N, lay, err) != MMW_OK) return fail(MMW_ERR_ARG, who + ": " + err);
         const int ld = lay.Dpad;
         const size_t bs = (size_t)K * ld;
         const int nblk = grid_slabs(K);
@@ -400,6 +413,7 @@ template <typename T> struct Factorizer {
         bool mf_stalled = false, mf_last_pass = false;  // the matrix-core split stopped paying / the pass before this residual ran on it
         int degree = 12;  // filter degree schedule 12, 30, 40, 40, ...: few Rayleigh-Ritz / orthonormalisation rounds
         int rr_skip = 0;  // filter passes still to run before the next Rayleigh-Ritz
+        int mf_passes = 0;  // filter passes that ran on the matrix cores (a record only)
         bool skip_rr = false;
         for (; outer < max_outer && !done; ++outer) {
             // Matrix-core products (two-half bf16 split, error <= 2.3e-5 || |A| || per product) serve the filter while the last
@@ -487,11 +501,29 @@ template <typename T> struct Factorizer {
             cut = std::max(cut, 1e-12 * mu_top);
             cut = std::min(cut, 0.999 * theta[rank - 1] * theta[rank - 1] + 1e-300);
             const double e = 0.5 * cut, cen = 0.5 * cut;
-            const double a0 = skip_rr ? rho * rho : std::max(mu_top, rho * rho * 1e-30);  // no Ritz values yet: the 1-norm bounds the spectrum
+            double a0 = skip_rr ? rho * rho : std::max(mu_top, rho * rho * 1e-30);  // no Ritz values yet: the 1-norm bounds the spectrum
+            // A Laplacian's top eigenvectors are localised: the Ritz values of a random block sit near the mean degree, far below
+            // lambda_max, and the passes that run back to back on them grow the top components by (lambda_max^2 / a0)^degree -- 1e45 at
+            // degree 40 on the journal instances, beyond fp32.  Its 1-norm is twice the largest degree and d_max <= lambda_max <= 2 d_max,
+            // so (rho / 2)^2 is a floor for a0 that never exceeds lambda_max^2 and is within 4x of it: growth <= 4^40 = 1e24.
+            if (eig) a0 = std::max(a0, 0.25 * rho * rho);
+            // ... and its spectrum is dense where the block ends (journal K = 1 058, Z = 97: lambda_1 = 88.7, lambda_Z = 49.8, lambda_b+1 = 48.1),
+            // so a pass of degree n grows the top of the block over its wanted end by T_n(x_top) / T_n(x_Z) ~ exp(n (acosh x_top -
+            // acosh x_Z)): 1e31 at n = 40.  Beyond 1 / eps_T every column is its rounding noise along the top eigenvectors, amplified, and the
+            // orthonormalisation cannot give the lower part of the block back (measured: the iteration ended at residual 2e-3 in fp64 and
+            // 0.19 in fp32).  The export mode keeps that growth below 1 / eps_T by capping the pass's degree; the schedule itself is as it was.
+            int degree_pass = degree;
+            if (eig) {
+                const double x_top = (a0 - cen) / e, x_z = std::max(1.0, (theta[rank - 1] * theta[rank - 1] - cen) / e);
+                const double rate = std::acosh(std::max(1.0, x_top)) - std::acosh(x_z);
+                const double log_inv_eps = f32 ? 24.0 * 0.6931471805599453 : 53.0 * 0.6931471805599453;
+                if (rate > 0.0 && rate * degree > log_inv_eps) degree_pass = std::max(4, (int)(log_inv_eps / rate));
+            }
             double sigma1 = e / (a0 - cen), sigma = sigma1;
             // Y = sigma1/e (B V - cen V): T1 = A V (already W); Ycur = c1 * A W + c2 * V
             const bool mf_pass = mf_stage && !mf_stalled && (no_rr || last_resid > mf_floor * tol || skip_rr);  // this pass's residual is known by now
             mf_last_pass = mf_pass;
+            if (mf_pass) ++mf_passes;
             if (mf_pass) {
                 if (!(mf_stage && no_rr)) MMW_TRY(split(W.p));  // W came from the fp32 kernel (or was rotated by the Rayleigh-Ritz step)
                 MMW_TRY((spmm_mf<SPMM_AXPBY>(ld, W.p, Y1.p, V.p, V.p, ascale * sigma1 / e, -cen * sigma1 / e, 0.0)));
@@ -501,7 +533,7 @@ template <typename T> struct Factorizer {
             T* prev = V.p;
             T* cur = Y1.p;
             T* nxt = Y2.p;
-            for (int i = 2; i <= degree; ++i) {
+            for (int i = 2; i <= degree_pass; ++i) {
                 const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
                 // nxt = 2 sigma2/e (A W - cen cur) - sigma sigma2 prev
                 if (mf_pass) {
@@ -539,8 +571,8 @@ template <typename T> struct Factorizer {
         if (verbose)
             fprintf(stderr, "[factor] K=%d rank=%d b=%d outer=%d degree_last=%d resid=%.2e jacobi_sweeps=%d jacobi_calls=%d\n", K, rank, b, outer, degree,
                     last_resid, dw.sweeps_total, dw.calls_total);
-        if (!done && last_resid > 100 * tol)
-            return fail(MMW_ERR_STATE, "mmw_factor: subspace iteration did not converge (relative residual " + std::to_string(last_resid) + ")");
+        if (!done && (last_resid > 100 * tol || (eig && !(last_resid <= 100 * tol))))  // (the export refuses a residual that is not a number too)
+            return fail(MMW_ERR_STATE, who + ": subspace iteration did not converge (relative residual " + std::to_string(last_resid) + ")");
         // ---- X_half = V[:, top rank] sqrt|theta|, columns in ascending |theta| (svds order, mmw.py:215-216)
         std::vector<int> sel(rank);
         std::vector<double> sc(rank);
@@ -549,9 +581,18 @@ template <typename T> struct Factorizer {
             sc[c] = std::sqrt(std::fabs(theta[rank - 1 - c]));
         }
         if (out64.n < (size_t)K * rank) MMW_TRY(out64.alloc((size_t)K * rank));
+        if (eig) {  // ---- V[:, top rank] itself, columns in ascending theta (eigsh's order), rows normalised
+            eig->eig.resize(rank);
+            for (int c = 0; c < rank; ++c) eig->eig[c] = theta[rank - 1 - c];
+            eig->theta_next = b > rank ? theta[rank] : 0.0;
+            eig->block = b;
+            eig->mf_passes = mf_passes;
+            hipLaunchKernelGGL((k_export_eigvec<T>), dim3(grid_rows(K)), dim3(BLOCK), 0, st, K, rank, ld, (const T*)V.p, eig->index_order, eig->rownorm, out64.p);
+        } else {
         MMW_HIP(hipMemcpyAsync(dw.perm.p, sel.data(), rank * sizeof(int), hipMemcpyHostToDevice, st));
         MMW_HIP(hipMemcpyAsync(dw.diag.p, sc.data(), rank * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL((k_export_factor<T>), dim3(grid_elems((size_t)K * rank)), dim3(BLOCK), 0, st, K, rank, ld, V.p, dw.perm.p, dw.diag.p, out64.p);
+        }
         MMW_HIP(hipGetLastError());
         last_n = 0;
         last_on_host = false;

@@ -105,6 +105,9 @@ int mmw_read_f64(mmw_solver* s, int which, double* out, int64_t n) { return entr
 int mmw_read_i32(mmw_solver* s, int which, int32_t* out, int64_t n) { return entry("mmw_read_i32", !s, "null solver handle", [&] { return !out && n ? fail(MMW_ERR_ARG, "null output") : s->read_i32(which, out, n); }); }
 int mmw_gap(mmw_solver* s, double out[3]) { return entry("mmw_gap", !s, "null solver handle", [&] { return s->gap(out); }); }
 int mmw_factor(mmw_solver* s, int32_t rank, double* out, uint64_t seed) { return entry("mmw_factor", !s, "null solver handle", [&] { return s->factor(rank, out, seed); }); }
+int mmw_factor_spectral(mmw_solver* s, int32_t Z, int32_t index_order, double* out, uint64_t seed) {
+    return entry("mmw_factor_spectral", !s, "null solver handle", [&] { return s->factor_spectral(Z, index_order, out, seed); });
+}
 int mmw_round(mmw_solver* s, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) {
     return entry("mmw_round", !s, "null solver handle", [&] { return s->round(Zr, Dp, gX, nbatch, randv, z_out, rem_out); });
 }

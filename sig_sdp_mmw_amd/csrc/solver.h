@@ -34,6 +34,7 @@ struct mmw_solver {
     virtual int read_i32(int which, int32_t* out, int64_t n) = 0;
     virtual int gap(double out[3]) = 0;
     virtual int factor(int32_t rank, double* out, uint64_t seed) = 0;
+    virtual int factor_spectral(int32_t Z, int32_t index_order, double* out, uint64_t seed) = 0;
     virtual int round(int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
                       int32_t* rem_out) = 0;
 };
@@ -257,11 +258,17 @@ template <typename T> struct Solver final : mmw_solver {
         // the fields a host-only handle holds too
         const HostPattern& H = core.H;
         const std::vector<double>* hv = which == MMW_F_S_SUM ? &H.S_sum : which == MMW_F_NORM_H ? &H.norm_H : which == MMW_F_ST_DATA ? &H.st_data : nullptr;
+        if (core.host_only && which == MMW_F_LAPLACIAN) {  // kernels_spectral.h's row function in a plain loop
+            if (n != H.nnzL()) return fail(MMW_ERR_ARG, "mmw_read_f64(LAPLACIAN): wrong length " + std::to_string(n) + ", expected " + std::to_string(H.nnzL()));
+            for (int r = 0; r < core.K; ++r) lap_row(H.l_indptr.data(), H.l_indices.data(), H.so_indptr.data(), H.so_indices.data(), H.so_data.data(), r, out);
+            return MMW_OK;
+        }
         if (core.host_only) return hv ? export_vec(*hv, out, n, "mmw_read_f64") : host_only_pattern();
         MMW_HIP(hipSetDevice(core.device));
         MMW_TRY(sync());
         if (which == MMW_F_ST_DATA) MMW_TRY(envl.ensure_host(core));
         if (hv) return export_vec(*hv, out, n, "mmw_read_f64");
+        if (which == MMW_F_LAPLACIAN) return extras.read_laplacian(core.d_indptr.p, core.d_col.p, core.d_diag.p, (size_t)H.nnzL(), out, n);
         return reads.read_f64(core, loop, emax, extras, which, out, n);
     }
     int read_i32(int which, int32_t* out, int64_t n) override {
@@ -286,6 +293,16 @@ template <typename T> struct Solver final : mmw_solver {
         if (core.iter < core.nit) return fail(MMW_ERR_STATE, "mmw_factor: run all announced iterations first (the average divides by nit)");
         MMW_TRY(core.x.csr_view(core));
         return extras.factor(core.d_indptr.p, core.d_col.p, core.xavg.p, core.nit, rank, out, seed);
+    }
+    // sdp_solver.spectral_sdp_solver.run_with_state on the handle's state: the factor's iteration on the Laplacian (solver_extras.h).  The
+    // iterate, its sums and the handle's slot count play no part.
+    int factor_spectral(int32_t Z, int32_t index_order, double* out, uint64_t seed) override {
+        if (Z < 1 || Z > core.K) return fail(MMW_ERR_ARG, "mmw_factor_spectral: Z = " + std::to_string(Z) + " must be in [1, K = " + std::to_string(core.K) + "]");
+        if (index_order != 0 && index_order != 1) return fail(MMW_ERR_ARG, "mmw_factor_spectral: index_order must be 0 or 1");
+        if (core.host_only) return host_only_handle();
+        MMW_HIP(hipSetDevice(core.device));
+        MMW_TRY(settle());
+        return extras.factor_spectral(core.d_indptr.p, core.d_col.p, core.d_diag.p, (size_t)core.H.nnzL(), Z, index_order, out, seed);
     }
     int round(int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) override {
         if (core.host_only) return host_only_handle();

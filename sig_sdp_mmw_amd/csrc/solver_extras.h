@@ -152,7 +152,58 @@ template <typename T> struct Extras {
     }
 
     int factor(const int* indptr, const int* col, const T* xavg, int nit, int32_t rank, double* out, uint64_t seed) {
-        return fac.run(indptr, col, xavg, 1.0 / (double)nit, rank, seed, out);
+        const int rc = fac.run(indptr, col, xavg, 1.0 / (double)nit, rank, seed, out);
+        if (rc == MMW_OK) spec_live = false;  // (MMW_F_FACTOR_ROWNORM belongs to a spectral factor)
+        return rc;
+    }
+
+    // ---- the spectral baseline (sdp_solver.py:165-185; kernels_spectral.h): the Laplacian of S_gain + S_gain^T as a second value vector
+    // on the L pattern, built on the first call that asks for it, and the factor's own iteration on it with the eigenvector export
+    DevBuf<double> lap64, spec_rownorm;
+    DevBuf<T> lapT;  // fp32 handles: the values narrowed for the products (fp64 handles read lap64)
+    bool lap_ready = false;
+    bool spec_live = false;      // out64 holds a spectral block: MMW_F_FACTOR_ROWNORM answers
+    double spec_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<double> spec_eig;
+    int ensure_laplacian(const int* indptr, const int* col, const int* diag_pos, size_t nnz) {
+        if (lap_ready) return MMW_OK;
+        MMW_TRY(lap64.alloc(nnz));
+        hipLaunchKernelGGL(k_lap_fill, dim3(grid_rows(K)), dim3(BLOCK), 0, st, K, indptr, col, diag_pos, (const int*)so_indptr.p, (const int*)so_indices.p,
+                           (const double*)so_data.p, lap64.p);
+        MMW_HIP(hipGetLastError());
+        if constexpr (sizeof(T) == 4) {
+            MMW_TRY(lapT.alloc(nnz));
+            hipLaunchKernelGGL((k_lap_narrow<T>), dim3(grid_elems(nnz)), dim3(BLOCK), 0, st, nnz, (const double*)lap64.p, lapT.p);
+            MMW_HIP(hipGetLastError());
+        }
+        lap_ready = true;
+        return MMW_OK;
+    }
+    int read_laplacian(const int* indptr, const int* col, const int* diag_pos, size_t nnz, double* out, int64_t n) {
+        if ((int64_t)nnz != n) return fail(MMW_ERR_ARG, "mmw_read_f64(LAPLACIAN): wrong length " + std::to_string(n) + ", expected " + std::to_string(nnz));
+        MMW_TRY(ensure_laplacian(indptr, col, diag_pos, nnz));
+        return copy_d2h(out, lap64.p, nnz * sizeof(double), st);
+    }
+    int factor_spectral(const int* indptr, const int* col, const int* diag_pos, size_t nnz, int32_t Z, int index_order, double* out, uint64_t seed) {
+        MMW_TRY(ensure_laplacian(indptr, col, diag_pos, nnz));
+        MMW_TRY(ensure(spec_rownorm, (size_t)K));
+        EigExport eig;
+        eig.index_order = index_order;
+        eig.rownorm = spec_rownorm.p;
+        const T* val;
+        if constexpr (sizeof(T) == 4) val = lapT.p;
+        else val = lap64.p;
+        MMW_TRY(fac.run(indptr, col, val, 1.0, Z, seed, out, &eig));  // (a refused or failed call exports nothing: the last factor stands)
+        spec_live = true;
+        spec_eig = eig.eig;
+        const double rec[8] = {(double)fac.outer_done, fac.last_resid, (double)Z, (double)eig.block, eig.eig[0], eig.theta_next, (double)eig.mf_passes, 0.0};
+        std::copy(rec, rec + 8, spec_info);
+        return MMW_OK;
+    }
+    int read_rownorm(double* out, int64_t n) {
+        if (!spec_live) return fail(MMW_ERR_STATE, "mmw_read_f64(FACTOR_ROWNORM): the handle's last factor is not a spectral one");
+        if (n != (int64_t)K) return fail(MMW_ERR_ARG, "mmw_read_f64(FACTOR_ROWNORM): wrong length");
+        return copy_d2h(out, spec_rownorm.p, (size_t)K * sizeof(double), st);
     }
     int read_factor(double* out, int64_t n) {
         if ((int64_t)fac.last_n != n || n == 0) return fail(MMW_ERR_STATE, "mmw_read_f64(FACTOR): no factor of that size has been computed");

@@ -69,6 +69,13 @@ template <typename T> struct SolverReads {
             case MMW_F_DUAL_INFO:
                 return export_vals({(double)lp.n_rs_iters, (double)lp.n_fused_iters, (double)lp.n_first_iters, (double)lp.n_first16_iters}, out, n, "dual info has 4 entries");
             case MMW_F_FACTOR: return extras.read_factor(out, n);
+            case MMW_F_FACTOR_ROWNORM: return extras.read_rownorm(out, n);
+            case MMW_F_SPECTRAL_INFO: {
+                if (n != 8) return fail(MMW_ERR_ARG, "spectral info has 8 entries");
+                std::copy(extras.spec_info, extras.spec_info + 8, out);
+                return MMW_OK;
+            }
+            case MMW_F_SPECTRAL_EIG: return export_vec(extras.spec_eig, out, n, "mmw_read_f64(SPECTRAL_EIG)");
             case MMW_F_KERNEL_US: {
                 if (n != 2 * KT_NSLOT) return fail(MMW_ERR_ARG, "kernel timers have 2*9 entries");
                 for (int i = 0; i < KT_NSLOT; ++i) { out[2 * i] = co.kt.total_us[i]; out[2 * i + 1] = co.kt.count[i]; }

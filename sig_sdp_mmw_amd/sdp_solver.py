@@ -179,17 +179,42 @@ class spectral_sdp_solver(STATS_OBJECT, rand_sdp_solver):
     row on the device; the host path divides by zero there, like the reference.
 
     The rows are unit, so the rounding visits the users in index order through `rand_sdp_solver.index_ordered`, as for the random
-    embedding (and as `BatchSolver.round` does on a spectral factor).  A `DeviceState` is read through its host copy."""
+    embedding (and as `BatchSolver.round` does on a spectral factor).  A `DeviceState` is read through its host copy.
 
-    def __init__(self, nit=100, rank_radio=2, alpha=1., *, device=0):
+    handle=True (and device >= 0): a state with K > 1024, and a `DeviceState` of any K, runs on the solver handle instead
+    (`Solver.factor_spectral`: the factor's Chebyshev-filtered block iteration on the Laplacian, relative residual 1e-9 against the
+    reference's `tol=1e-5`) -- the cached handle the rounding uses afterwards, built for a `DeviceState` without a host copy of the
+    state.  `run_with_state` then returns the block resident and already index-ordered (a `DeviceFactor`), which the rounding reads
+    where it lies.  Host states with K <= 1024 keep the batch path; handle=False is the behaviour above, unchanged."""
+
+    def __init__(self, nit=100, rank_radio=2, alpha=1., *, device=0, handle=False):
         sdp_solver.__init__(self, nit=nit, rank_radio=rank_radio, alpha=alpha)
         self.device = int(device)
+        self.handle = bool(handle)
         if self.device >= 0:
             self._device_index = self.device
 
-    def run_with_state(self, bs_iteration, Z, state):
+    @staticmethod
+    def index_ordered(gX):
+        if isinstance(gX, _lib.DeviceFactor) and gX.index_ordered:  # scaled on the device already: a second pass would copy it out
+            return gX
+        return rand_sdp_solver.index_ordered(gX)
+
+    def _run_on_handle(self, bs_iteration, Z, state):
         ps_tic = self._get_tic()
+        K = self._state_K(state)
+        solver = self._device_solver(Z, state)  # (the Laplacian's values are filled by the handle's first solve, on the device)
+        self._add_np_log("spectral_problem_setup", bs_iteration, np.array([Z, K, self._get_tim(ps_tic)]))
+        solving_tic = self._get_tic()
+        block = solver.factor_spectral(Z, resident=True, index_order=True)
+        self._add_np_log("spectral_solve", bs_iteration, np.array([Z, K, self._get_tim(solving_tic)]))
+        return True, block
+
+    def run_with_state(self, bs_iteration, Z, state):
         Z = int(Z)
+        if self.handle and self.device >= 0 and (isinstance(state, _lib.DeviceState) or self._state_K(state) > _lib.BATCH_EPILOGUE_MAX_K):
+            return self._run_on_handle(bs_iteration, Z, state)
+        ps_tic = self._get_tic()
         if isinstance(state, _lib.DeviceState):
             state = state.host()
         K = state[0].shape[0]
