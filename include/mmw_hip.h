@@ -163,6 +163,8 @@ int mmw_reset(mmw_solver* s, int32_t nit);
  * mmw_set_slots: rebind the handle to another slot count Z on the SAME state (the binary search probes
  * several Z per state, binary_search_relaxation.py:46-50): norm_H and the D = Z*rank_radio wide blocks are
  * rebuilt, the pattern, its locality blocking and the device copies of the state are reused; then mmw_reset(nit).
+ * Z < 2, or a width D past what the kernels cover (1024 columns on an fp32 handle, 512 on an fp64 one), is refused with
+ * MMW_ERR_ARG before anything changes: the handle stays on its slot count, with its iterate.
  */
 int mmw_set_slots(mmw_solver* s, int32_t Z, int32_t nit);
 /*
@@ -177,8 +179,8 @@ int mmw_set_eta(mmw_solver* s, double eta);
 
 /*
  * mmw_iterate: `n` passes of the loop body mmw.py:75-200 (averaging, DUAL, LOSS, EXPM), device resident.
- * randv: NULL -> the sketch of every iteration is generated on the device (Philox4x32-10 normals,
- * counter = (seed, iteration, row, column), rows normalised); otherwise n*K*D float64, iteration-major,
+ * randv: NULL -> the sketch of every iteration is generated on the device (Philox4x32-10 normals, key = the seed's
+ * low and high word, counter = (row, column group, iteration, tag): see mmw_sketch; rows normalised); otherwise n*K*D float64, iteration-major,
  * each block the row-normalised (K,D) sketch the reference would draw at mmw.py:226-227 (parity mode).
  * Returns after the work is enqueued; any read or mmw_sync waits for it.
  */
@@ -186,10 +188,13 @@ int mmw_iterate(mmw_solver* s, int32_t n, const double* randv, uint64_t seed);
 int mmw_sync(mmw_solver* s);
 /*
  * mmw_sketch: the row-normalised (K, D) sketch the device generator draws for `iteration` of a run with `seed` (what
- * np.random.randn + the row normalisation of mmw.py:226-227 are to the reference).  The generator is counter-based (Philox4x32-10
- * keyed by seed, counter = iteration, row, column), so the block is exactly the one mmw_iterate(n, NULL, seed) multiplied in that
- * iteration, in whatever chunk it ran: parity tests hand it to the oracle to follow a device-RNG run.  out: K*D float64, row-major.
- * Waits for enqueued work; does not touch the iterate.
+ * np.random.randn + the row normalisation of mmw.py:226-227 are to the reference).  The generator is counter-based: Philox4x32-10
+ * with key (seed & 0xffffffff, seed >> 32) and counter (row, column group, iteration, 0x4d4d5753); a group is the 16 bytes one draw
+ * fills -- columns 2p, 2p+1 from a 53-bit / 64-bit uniform pair on an fp64 handle, columns 4p ... 4p+3 from four 24-bit uniforms on an
+ * fp32 one (Box-Muller) -- columns >= D are zero and do not count in the row's norm (DESIGN.md section 2 states the whole contract,
+ * tests/helpers/philox_ref.py restates it in NumPy).  So the block is exactly the one mmw_iterate(n, NULL, seed) multiplied in that
+ * iteration, in whatever chunk and whichever launch it was drawn: parity tests hand it to the oracle to follow a device-RNG run.
+ * out: K*D float64, row-major.  Waits for enqueued work; does not touch the iterate.
  */
 int mmw_sketch(mmw_solver* s, uint64_t seed, int32_t iteration, double* out, int64_t n);
 

@@ -23,12 +23,12 @@ inline int make_layout(int D, int vec, BlockLayout& lay, std::string& err) {
         lay.NCH = 1;
     } else {
         lpr = (lpr + 7) / 8 * 8;  // rows in whole 128-byte cache lines: a gathered 128-byte piece then is ONE line, not two halves
-        lay.G = 1;
-        lay.NCH = (lpr + WAVE - 1) / WAVE;
-        if (lay.NCH > 4) {
+        if ((lpr + WAVE - 1) / WAVE > 4) {  // (refused before `lay` is touched: the caller's layout stays the one it runs on)
             err = "sketch width D too large for this build (max 1024 f32 / 512 f64 columns)";
             return MMW_ERR_ARG;
         }
+        lay.G = 1;
+        lay.NCH = (lpr + WAVE - 1) / WAVE;
     }
     lay.D = D;
     lay.LPR = lpr;

@@ -111,6 +111,12 @@ template <typename T> struct Solver final : mmw_solver {
         MMW_TRY(settle());
         MMW_HIP(hipStreamSynchronize(core.st));
         if (warm && core.iter == 0) warm = 0;  // nothing to continue from
+        if (Z_ >= 2) {  // a width the kernels do not cover is refused before anything of the handle changes: it stays on its slot count
+            BlockLayout probe{};
+            std::string lerr;
+            if ((int64_t)Z_ * core.rank_radio > INT32_MAX || make_layout(Z_ * core.rank_radio, V16<T>::N, probe, lerr) != MMW_OK)
+                return fail(MMW_ERR_ARG, "mmw_set_slots: " + (lerr.empty() ? std::string("sketch width D too large for this build") : lerr));
+        }
         std::string err = update_slots(core.H, Z_);
         if (!err.empty()) return fail(MMW_ERR_ARG, "mmw_set_slots: " + err);
         core.Z = Z_;
