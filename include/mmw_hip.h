@@ -300,6 +300,28 @@ int mmw_env_evaluate(mmw_env* e, const double* z_vec, int32_t Z, double packet_b
  */
 int mmw_create_from_env(mmw_solver** out, mmw_env* env, int dtype, int32_t Z, int32_t rank_radio, double eta, int32_t nit);
 int mmw_env_bounds(mmw_env* e, int32_t out[2]);
+/*
+ * The online sweeps on one instance of any K (sim_script/journal_version/sim_mmw_online.py:34-88: solve once, then let the stations
+ * walk and round the same factor against the state at every time point; ton_major_rv/sim_mmw_online_cmp_methods.py for the arms).
+ *
+ * mmw_env_move: mob_env.step_time's effect on the state (sim_src/env/env.py:74-87 -> generate_S_Q_hmax, :136-196): the K stations of
+ * an existing environment at sta_xy[K][2]; K, A, the access points and the radio parameters stay.  Receive powers, transmit
+ * powers, association, AP member lists and S_gain / Q_asso / h_max as CSR are computed again on the device by mmw_env_create's own
+ * kernels; the buffers grow when nnz grows.  Afterwards mmw_env_sizes, mmw_env_state, mmw_env_bounds and mmw_env_evaluate answer
+ * bitwise what a fresh mmw_env_create at those coordinates answers.  A handle made earlier by mmw_create_from_env or
+ * mmw_gm_create_from_env is untouched (neither keeps a reference to `env`).  A coordinate that is not finite: MMW_ERR_ARG, nothing moves.
+ *
+ * mmw_round_env: mmw_round (sdp_solver.rounding_one_attempt, sdp_solver.py:27-107, as sim_mmw_online.py:60 calls it on the moved
+ * state) of gX -- or, with gX == NULL, of the handle's resident factor or spectral block -- against the state `env` holds NOW.  The
+ * rounding's view of that state (S_gain's off-diagonal out-lists, the Q lists, h_max) is built on the device from the environment's
+ * CSR into a second list set the handle owns, kept for the (environment, generation) it was built from; no host copy of the state.
+ * Same kernels, same tie rules, same Zr > 4800 refusal and same outputs as mmw_round.  Nothing of the handle's own state, iterate
+ * or factor changes.  Refused with MMW_ERR_ARG before anything is allocated or launched: an environment whose K differs from the
+ * handle's, an environment on another device.  A device -1 handle: MMW_ERR_STATE.
+ */
+int mmw_env_move(mmw_env* e, const double* sta_xy);
+int mmw_round_env(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv,
+                  int32_t* z_out, int32_t* rem_out);
 
 /*
  * A state that lives on the device as its seven CSR arrays, and the solver handle built from it there: the way in for a graph
@@ -356,6 +378,21 @@ int mmw_create_from_csr(mmw_solver** out, mmw_csr* csr, int dtype, int32_t Z, in
 typedef struct mmw_gm mmw_gm;
 int mmw_gm_create(mmw_gm** out, int device, int32_t K, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
                   const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max);
+/*
+ * mmw_gm_create_from_env: mmw_gm_create for the state `env` holds now (the greedy arm of the online comparison,
+ * ton_major_rv/sim_mmw_online_cmp_methods.py:79-88), WITHOUT the host round trip: the S rows, the Q rows and h_max are built on the
+ * device from the environment's CSR, and the clique groups come straight from its association (its Q is the same-AP relation,
+ * env.py:181-189).  mmw_gm_sizes, mmw_gm_pass, mmw_gm_run and mmw_gm_assign answer exactly what they answer on
+ * mmw_gm_create(mmw_env_state(...)).  The handle keeps no reference to `env`: it is a snapshot of the generation it was built from.
+ */
+int mmw_gm_create_from_env(mmw_gm** out, mmw_env* e);
+/*
+ * mmw_gm_key: the visiting keys of MAX_GAIN (kind 0, gm.py:11-18: the column sums of S_gain with the diagonal zeroed) and MAX_ASSO
+ * (kind 1, gm.py:81: the row sums of Q_asso) for the handle's state, key_out[K], in scipy's summation orders: bitwise the
+ * reference's expressions.  A handle built by mmw_gm_create_from_env forms them on the device from its own lists -- there is no host
+ * matrix to take them from --; a handle made from host arrays forms them on the host.
+ */
+int mmw_gm_key(mmw_gm* g, int kind, double* key_out);
 int mmw_gm_destroy(mmw_gm* g);
 int mmw_gm_sizes(mmw_gm* g, int64_t out[4]);
 /*

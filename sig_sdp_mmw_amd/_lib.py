@@ -48,7 +48,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
-           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral"]
+           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key"]
 
 
 class MMWError(RuntimeError):
@@ -105,6 +105,10 @@ def lib():
     L.mmw_env_evaluate.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_double, C.c_double, C.c_double, p_f64, p_f64]
     L.mmw_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.mmw_env_bounds.argtypes = [C.c_void_p, p_i32]
+    L.mmw_env_move.argtypes = [C.c_void_p, p_f64]
+    L.mmw_round_env.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_int32, p_f64, p_i32, p_i32]
+    L.mmw_gm_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
+    L.mmw_gm_key.argtypes = [C.c_void_p, C.c_int, p_f64]
     for fn in (L.mmw_csr_upload, L.mmw_csr_wrap):  # (wrap's seven are device addresses: plain integers here)
         fn.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int64, C.c_int64] + [C.c_void_p] * 7
     L.mmw_csr_destroy.argtypes = [C.c_void_p]
@@ -513,6 +517,15 @@ class Solver(_Handle):
 
     def round(self, Z, gX, randv):
         """randv: (nbatch, Z, D') row-normalised; returns (z[nbatch,K] int32 with -1 = unassigned, rem[nbatch])."""
+        return self._round(None, Z, gX, randv)
+
+    def round_env(self, env, Z, gX, randv):
+        """`round` against the state the DeviceEnv `env` holds now (mmw_round_env): the handle's factor -- gX, or a resident
+        `DeviceFactor` of this handle read where it lies -- rounded on the moved stations, the lists built on the device from the
+        environment's CSR and kept until it moves again.  The handle's own state, iterate and factor stay as they are."""
+        return self._round(env, Z, gX, randv)
+
+    def _round(self, env, Z, gX, randv):
         on_device = isinstance(gX, DeviceFactor) and gX.on_device_of(self)
         if not on_device:
             gX = _f64(gX)
@@ -524,7 +537,11 @@ class Solver(_Handle):
             raise MMWError("round: gX must be (K, D') and randv (nbatch, Z, D')")
         z = np.empty((nb, self.K), dtype=np.int32)
         rem = np.empty(nb, dtype=np.int32)
-        check(lib().mmw_round(self._h, int(Z), int(Dp), None if on_device else _pd(gX), int(nb), _pd(randv), _pi(z), _pi(rem)))
+        args = (int(Z), int(Dp), None if on_device else _pd(gX), int(nb), _pd(randv), _pi(z), _pi(rem))
+        if env is None:
+            check(lib().mmw_round(self._h, *args))
+        else:
+            check(lib().mmw_round_env(self._h, env._h, *args))
         return z, rem
 
 
@@ -1060,9 +1077,25 @@ class DeviceEnv(_Handle):
         self._h = C.c_void_p()
         check(lib().mmw_env_create(C.byref(self._h), int(device), self.K, self.A, _pd(sta), _pd(ap), float(fre_Hz), float(txp_offset),
                                    float(min_s_n_ratio), float(min_sinr), float(noise_floor_dbm)))
+        self.device = int(device)
+        self.generation = 0  # counts the moves: a DeviceState belongs to the generation it was made in
+        self._load_sizes()
+
+    def _load_sizes(self):
         sz = (C.c_int64 * 4)()
         check(lib().mmw_env_sizes(self._h, sz))
         self.nnzS, self.nnzQ = int(sz[2]), int(sz[3])
+
+    def move(self, sta_locs):
+        """generate_S_Q_hmax at the stations' new positions sta_locs (K, 2), on the device (mmw_env_move): afterwards `state`, `bounds`
+        and `evaluate` answer bitwise what a fresh DeviceEnv at those positions answers.  Handles built from this environment before
+        are untouched; a `device_state()` handed out before belongs to the old generation and raises when it is used."""
+        sta = _f64(sta_locs)
+        if sta.shape != (self.K, 2):
+            raise MMWError("move: station locations must be a (K, 2) array")
+        self.generation += 1  # (first: after a move that failed nothing of an older generation may be read either)
+        check(lib().mmw_env_move(self._h, _pd(sta)))
+        self._load_sizes()
 
     def state(self):
         """(S_gain csr, Q_asso csr, h_max) as env.generate_S_Q_hmax returns them."""
@@ -1298,13 +1331,30 @@ class DeviceState:
     (S_gain, Q_asso, h_max) triple that remembers where it lives."""
 
     def __init__(self, env):
-        self.env = env
+        self._env = env
         self.K = env.K
         self._host = None
+        self.generation = getattr(env, "generation", 0)  # (a DeviceCSR never changes: one generation)
+
+    def check(self):
+        """A device-resident state is immutable -- identity is content (sdp_solver._same_state).  A DeviceEnv that has moved since
+        holds another state under the same object: this one then refuses every use instead of reading the new arrays."""
+        now = getattr(self._env, "generation", 0)
+        if now != self.generation:
+            raise MMWError("this DeviceState belongs to generation %d of its environment, which has moved since (generation %d): "
+                           "take a new one from device_state()" % (self.generation, now))
+
+    @property
+    def env(self):
+        """Where the state lives (its `solver` and `bounds` routes): checked on every access."""
+        self.check()
+        return self._env
 
     def host(self):
         if self._host is None:
             self._host = self.env.state()
+        else:
+            self.check()
         return self._host
 
     def __getitem__(self, i):
@@ -1329,6 +1379,31 @@ class GreedyHandle(_Handle):
         sz = (C.c_int64 * 4)()
         check(lib().mmw_gm_sizes(self._h, sz))
         self.groups = int(sz[1])  # -1: Q is not a union of cliques (general association check)
+
+    @classmethod
+    def from_env(cls, env):
+        """The handle for the state a DeviceEnv holds now, its lists built on the device and its clique groups taken from the
+        generator's association (mmw_gm_create_from_env): answers exactly what `GreedyHandle(env.state())` answers, and keeps
+        answering for that state when the environment moves on."""
+        self = cls.__new__(cls)
+        self.K, self.device = env.K, env.device
+        self._h = C.c_void_p()
+        check(lib().mmw_gm_create_from_env(C.byref(self._h), env._h))
+        self.groups = self.sizes()[1]
+        return self
+
+    def sizes(self):
+        """mmw_gm_sizes: [K, clique groups (-1: general check), nnz of the S rows, nnz(Q)]."""
+        sz = (C.c_int64 * 4)()
+        check(lib().mmw_gm_sizes(self._h, sz))
+        return [int(x) for x in sz]
+
+    def key(self, kind):
+        """MAX_GAIN's (kind 0) or MAX_ASSO's (kind 1) visiting key of the handle's state, float64 [K], bitwise the reference's
+        scipy expression (mmw_gm_key); a handle built from an environment forms it on the device."""
+        out = np.empty(self.K, dtype=np.float64)
+        check(lib().mmw_gm_key(self._h, int(kind), _pd(out)))
+        return out
 
     def pass_(self, order, nattempt=1):
         """One slot for the visiting order `order` (unassigned users): the accepted users, in acceptance order."""

@@ -273,6 +273,20 @@ struct EnvDevice {
         ptr.assign(len.size() + 1, 0);
         for (size_t i = 0; i < len.size(); ++i) ptr[i + 1] = ptr[i] + len[i];
     }
+    // which environment and which of its states a list set cached elsewhere was built from (Extras::round_env): `uid` is unique per
+    // environment of the process (an address may be handed out again), `gen` counts the moves
+    uint64_t uid = next_uid(), gen = 0;
+    static uint64_t next_uid() {
+        static std::atomic<uint64_t> n{0};
+        return ++n;
+    }
+    EnvListSource list_source() const {
+        EnvListSource L;
+        L.uid = uid; L.gen = gen; L.device = device; L.K = K; L.nnzQ = nnzQ;
+        L.s_ptr = s_ptr.p; L.s_idx = s_idx.p; L.s_val = s_val.p; L.q_ptr = q_ptr.p; L.q_idx = q_idx.p; L.q_val = q_val.p; L.h_max = h_max.p;
+        L.A = A; L.asso = asso.p; L.ap_ptr = ap_ptr.p; L.ap_mem = ap_mem.p;
+        return L;
+    }
     int init(int dev, int K_, int A_, const double* sta_xy, const double* ap_xy, double fre_Hz, double txp_offset, double min_s_n_ratio,
              double min_sinr_, double noise_dbm) {
         device = dev; K = K_; A = A_; min_sinr = min_sinr_;
@@ -290,6 +304,23 @@ struct EnvDevice {
         MMW_TRY(rx.alloc((size_t)K * A));
         MMW_TRY(asso.alloc(K)); MMW_TRY(ap_cnt.alloc(A)); MMW_TRY(ap_ptr.alloc(A + 1)); MMW_TRY(ap_mem.alloc(K));
         MMW_TRY(s_len.alloc(K)); MMW_TRY(q_len.alloc(K)); MMW_TRY(s_ptr.alloc(K + 1)); MMW_TRY(q_ptr.alloc(K + 1)); MMW_TRY(h_max.alloc(K));
+        return generate();
+    }
+    // mmw_env_move (mob_env.step_time -> generate_S_Q_hmax, sim_src/env/env.py:74-87, 136-196): the K stations at new coordinates, everything
+    // else as it was.  The launches are init's own, so the state is bitwise the one a fresh environment builds at these coordinates; the CSR
+    // buffers grow with nnz (DevBuf::alloc keeps an allocation that is large enough), and what pattern_inputs caches is made again on demand.
+    int move(const double* sta_xy) {
+        for (size_t i = 0; i < 2 * (size_t)K; ++i)
+            if (!std::isfinite(sta_xy[i])) return fail(MMW_ERR_ARG, "mmw_env_move: station coordinate " + std::to_string(i) + " is not finite");
+        MMW_HIP(hipSetDevice(device));
+        ++gen;  // (counted first: a move that fails half-way leaves no state an older generation's lists could stand for)
+        pat_ready = false;
+        h_sta.assign(sta_xy, sta_xy + 2 * (size_t)K);
+        MMW_TRY(copy_h2d(sta.p, h_sta.data(), h_sta.size() * sizeof(double), st));
+        return generate();
+    }
+    // receive powers, association, AP member lists, then the CSR state: what init and move share
+    int generate() {
         const int gk = grid_rows(K), ga = grid_rows(A);
         hipLaunchKernelGGL(k_env_rx, dim3(gk), dim3(BLOCK), 0, st, K, A, P, sta.p, ap.p, rx.p, asso.p);
         hipLaunchKernelGGL(k_env_ap_members, dim3(ga), dim3(BLOCK), 0, st, K, A, asso.p, (const int*)nullptr, ap_cnt.p, (int*)nullptr);

@@ -1,5 +1,6 @@
 #pragma once
 #include "kernels_gm.h"
+#include "pattern_device.h"
 #include "runtime.h"
 
 using namespace mmw;
@@ -51,6 +52,61 @@ struct mmw_gm {
         }
         h_info.assign(GM_INFO_N, 0);
         return MMW_OK;
+    }
+    // mmw_gm_create_from_env: the handle for the state a generator holds now, its lists built on the device (pattern_device.h: RoundListSet)
+    // and its groups taken from the association (k_gm_groups_from_asso).  S keeps K, the clique flag and the group count only: the host
+    // vectors stay empty, the sizes are counted here.  A snapshot: nothing of the generator is referenced afterwards.
+    int64_t n_so = -1, n_q = -1;  // >= 0: a handle built from an environment
+    int64_t nnz_so() const { return n_so >= 0 ? n_so : (int64_t)S.so_indices.size(); }
+    int64_t nnz_q() const { return n_q >= 0 ? n_q : (int64_t)S.q_indices.size(); }
+    int init_from_env(const EnvListSource& E) {
+        device = E.device;
+        S.K = E.K;
+        S.clique = true;  // the generator's Q is a union of AP cliques with weight 1 (env.py:182-189)
+        MMW_HIP(hipSetDevice(device));
+        MMW_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        RoundListSet L;
+        MMW_TRY(L.build(st, E));
+        so_indptr.swap(L.so_indptr); so_indices.swap(L.so_indices); so_data.swap(L.so_data); so_hmax.swap(L.so_hmax);
+        q_indptr.swap(L.q_indptr); q_indices.swap(L.q_indices); h_max.swap(L.h_max);
+        n_so = L.nso; n_q = E.nnzQ;
+        const size_t K = (size_t)S.K;
+        MMW_TRY(q_data.alloc((size_t)E.nnzQ)); MMW_TRY(grp.alloc(K)); MMW_TRY(info.alloc(GM_INFO_N));
+        if (E.nnzQ) MMW_HIP(hipMemcpyAsync(q_data.p, E.q_val, (size_t)E.nnzQ * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_gm_groups_from_asso, dim3(grid_elems(K)), dim3(BLOCK), 0, st, S.K, E.A, E.asso, E.ap_ptr, E.ap_mem, grp.p, info.p);
+        MMW_HIP(hipGetLastError());
+        int G = 0;
+        MMW_TRY(copy_d2h(&G, info.p, sizeof(int), st));
+        S.G = G;
+        MMW_TRY(ord.alloc(K)); MMW_TRY(slot.alloc(K)); MMW_TRY(lists.alloc(2 * K));
+        if (!lds_fits()) {
+            MMW_TRY(gsum.alloc(K)); MMW_TRY(mark.alloc(K)); MMW_TRY(owner.alloc(std::max(S.G, 1)));
+        }
+        h_info.assign(GM_INFO_N, 0);
+        return MMW_OK;
+    }
+    // mmw_gm_key: kind 0, MAX_GAIN's key (gm.py:11-18); kind 1, MAX_ASSO's (:81).  A handle made from host arrays forms them there
+    // (GmState::key_host); a handle built from an environment has no host lists and forms both on the device from its own, once.
+    DevBuf<double> keys;  // [2][K]
+    bool keys_ready = false;
+    int get_key(int kind, double* out) {
+        if (kind != 0 && kind != 1) return fail(MMW_ERR_ARG, "mmw_gm_key: kind must be 0 (MAX_GAIN) or 1 (MAX_ASSO)");
+        if (n_so < 0) {
+            std::vector<double> k;
+            S.key_host(kind, k);
+            std::copy(k.begin(), k.end(), out);
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        const size_t K = (size_t)S.K;
+        if (!keys_ready) {
+            MMW_TRY(keys.alloc(2 * K));
+            hipLaunchKernelGGL(k_gm_keys, dim3(1), dim3(BLOCK), 0, st, S.K, (const int*)so_indptr.p, (const int*)so_indices.p, (const double*)so_data.p,
+                               (const int*)q_indptr.p, (const double*)q_data.p, keys.p, keys.p + K);
+            MMW_HIP(hipGetLastError());
+            keys_ready = true;
+        }
+        return copy_d2h(out, keys.p + (size_t)kind * K, K * sizeof(double), st);
     }
     // one launch of k_gm_slots over ord (already on the device)
     int launch(int n, int z0, int nslot, int nattempt, int full) {

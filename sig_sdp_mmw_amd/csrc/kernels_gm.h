@@ -180,6 +180,52 @@ __global__ __launch_bounds__(WAVE) void k_gm_slots(int K, int n, const int* __re
     }
 }
 
+// The clique structure of Q for a state the generator holds (mmw_gm_create_from_env): its Q is the same-AP relation (env.py:181-189), so a
+// user's group is its access point and nothing has to be searched.  Numbered as GmState::find_cliques numbers them on the host: access
+// points with two users or more, in the order of their first (lowest) user; a user alone behind its access point has no Q row and no
+// group.  One thread per user counts the access points whose first user comes earlier (A is a few hundred); thread 0 counts the groups.
+__global__ __launch_bounds__(BLOCK) void k_gm_groups_from_asso(int K, int A, const int* __restrict__ asso, const int* __restrict__ ap_ptr,
+                                                               const int* __restrict__ ap_mem, int* __restrict__ grp, int* __restrict__ G_out) {
+    for (int k = blockIdx.x * BLOCK + threadIdx.x; k < K; k += gridDim.x * BLOCK) {
+        const int a = asso[k];
+        int g = -1;
+        if (ap_ptr[a + 1] - ap_ptr[a] >= 2) {
+            const int first = ap_mem[ap_ptr[a]];
+            g = 0;
+            for (int b = 0; b < A; ++b)
+                if (ap_ptr[b + 1] - ap_ptr[b] >= 2 && ap_mem[ap_ptr[b]] < first) ++g;
+        }
+        grp[k] = g;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int n = 0;
+        for (int b = 0; b < A; ++b) n += ap_ptr[b + 1] - ap_ptr[b] >= 2 ? 1 : 0;
+        *G_out = n;
+    }
+}
+
+// The keys of gm.py:11-18 / :81 from a handle's own device lists, in scipy's summation orders (GmState::key_host says which): the gain key
+// is the column sum of S without its diagonal accumulated in ASCENDING ROW, so ONE workgroup walks the rows one after another and adds a
+// row's entries side by side (a row's columns are distinct: one writer per address, the barrier orders the rows); the association key
+// is a row's Q weights added in stored order, one thread per row.
+__global__ __launch_bounds__(BLOCK) void k_gm_keys(int K, const int* __restrict__ so_indptr, const int* __restrict__ so_indices,
+                                                   const double* __restrict__ so_data, const int* __restrict__ q_indptr,
+                                                   const double* __restrict__ q_data, double* key_gain, double* __restrict__ key_asso) {
+    for (int k = threadIdx.x; k < K; k += BLOCK) {
+        key_gain[k] = 0.0;
+        double s = 0.0;
+        for (int e = q_indptr[k]; e < q_indptr[k + 1]; ++e) s += q_data[e];
+        key_asso[k] = s;
+    }
+    __syncthreads();
+    for (int j = 0; j < K; ++j) {
+        const int b = so_indptr[j], n = so_indptr[j + 1];
+        if (b == n) continue;  // (uniform over the workgroup: no barrier is skipped by some threads only)
+        for (int e = b + threadIdx.x; e < n; e += BLOCK) key_gain[so_indices[e]] += so_data[e];
+        __syncthreads();
+    }
+}
+
 // ---- the state the greedy baselines read, built on the host once per handle ------------------------------------------------------
 struct GmState {
     int K = 0, G = 0;

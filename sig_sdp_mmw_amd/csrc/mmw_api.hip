@@ -179,6 +179,10 @@ int mmw_env_evaluate(mmw_env* e, const double* z_vec, int32_t Z, double packet_b
                      double* bler_out) {
     return entry("mmw_env_evaluate", !e || !z_vec || !sinr_out, "mmw_env_evaluate: null pointer", [&] { return e->e.evaluate(z_vec, Z, packet_bit, bandwidth, slot_time, sinr_out, bler_out); });
 }
+int mmw_env_move(mmw_env* e, const double* sta_xy) { return entry("mmw_env_move", !e || !sta_xy, "mmw_env_move: null pointer", [&] { return e->e.move(sta_xy); }); }
+int mmw_round_env(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) {
+    return entry("mmw_round_env", !s, "null solver handle", [&] { return s->round_env(e, Zr, Dp, gX, nbatch, randv, z_out, rem_out); });
+}
 int mmw_gm_create(mmw_gm** out, int device, int32_t K, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
                   const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max) {
     return guarded("mmw_gm_create", [&]() -> int {
@@ -194,11 +198,22 @@ int mmw_gm_create(mmw_gm** out, int device, int32_t K, const int32_t* S_indptr, 
         return MMW_OK;
     });
 }
+int mmw_gm_create_from_env(mmw_gm** out, mmw_env* e) {
+    return guarded("mmw_gm_create_from_env", [&]() -> int {
+        if (!out || !e) return fail(MMW_ERR_ARG, "mmw_gm_create_from_env: null pointer");
+        *out = nullptr;
+        auto g = std::make_unique<mmw_gm>();
+        MMW_TRY(g->init_from_env(e->e.list_source()));
+        *out = g.release();
+        return MMW_OK;
+    });
+}
+int mmw_gm_key(mmw_gm* g, int kind, double* key_out) { return entry("mmw_gm_key", !g || !key_out, "mmw_gm_key: null pointer", [&] { return g->get_key(kind, key_out); }); }
 int mmw_gm_destroy(mmw_gm* g) { return guarded("mmw_gm_destroy", [&]() -> int { delete g; return MMW_OK; }); }
 int mmw_gm_sizes(mmw_gm* g, int64_t out[4]) {
     return guarded("mmw_gm_sizes", [&]() -> int {
         if (!g || !out) return fail(MMW_ERR_ARG, "null pointer");
-        out[0] = g->S.K; out[1] = g->S.clique ? g->S.G : -1; out[2] = (int64_t)g->S.so_indices.size(); out[3] = (int64_t)g->S.q_indices.size();
+        out[0] = g->S.K; out[1] = g->S.clique ? g->S.G : -1; out[2] = g->nnz_so(); out[3] = g->nnz_q();
         return MMW_OK;
     });
 }

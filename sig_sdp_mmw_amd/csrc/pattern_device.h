@@ -200,5 +200,61 @@ __global__ __launch_bounds__(BLOCK) void k_pat_so_fill(int K, const int* __restr
         }
     }
 }
+// row lengths of that view: the stored entries of S row k off the diagonal (one wavefront per row; the prefix sums are the host's)
+__global__ __launch_bounds__(BLOCK) void k_pat_so_count(int K, const int* __restrict__ s_ptr, const int* __restrict__ s_idx, int* __restrict__ so_len) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    for (int k = blockIdx.x * WAVES_PER_BLOCK + wib; k < K; k += gridDim.x * WAVES_PER_BLOCK) {
+        int n = 0;
+        const int end = s_ptr[k + 1];
+        for (int i0 = s_ptr[k]; i0 < end; i0 += WAVE) {
+            const int i = i0 + lane;
+            n += __popcll(__ballot(i < end && s_idx[i] != k));
+        }
+        if (lane == 0) so_len[k] = n;
+    }
+}
+
+// ---- the rounding's view of a state that a generator holds NOW, as a list set of its own (mmw_round_env, mmw_gm_create_from_env): the
+// generator's CSR arrays where they lie, and which environment and which of its generations they belong to
+struct EnvListSource {
+    uint64_t uid = 0, gen = 0;
+    int device = 0, K = 0;
+    int64_t nnzQ = 0;
+    const int* s_ptr = nullptr; const int* s_idx = nullptr; const double* s_val = nullptr;
+    const int* q_ptr = nullptr; const int* q_idx = nullptr; const double* q_val = nullptr;
+    const double* h_max = nullptr;
+    int A = 0;  // the association itself, for the greedy baselines' groups (kernels_gm.h)
+    const int* asso = nullptr; const int* ap_ptr = nullptr; const int* ap_mem = nullptr;
+};
+// S_gain's off-diagonal out-lists with their values and the h_max of every stored column, the Q lists and h_max: what the greedy kernels of
+// kernels_round.h and kernels_gm.h read.  Built by a count launch, one readback of K lengths, the host's prefix sums and k_pat_so_fill;
+// the Q lists and h_max are device-to-device copies.  The caller's stream; the source must be complete (the generator synchronises
+// its own stream before it returns).  Nothing of the state crosses to the host.
+struct RoundListSet {
+    DevBuf<int> so_indptr, so_indices, q_indptr, q_indices, so_len;
+    DevBuf<double> so_data, so_hmax, h_max;
+    int64_t nso = 0;
+    int build(hipStream_t st, const EnvListSource& E) {
+        const int K = E.K;
+        const size_t Ks = (size_t)K;
+        MMW_TRY(so_len.alloc(Ks)); MMW_TRY(so_indptr.alloc(Ks + 1)); MMW_TRY(q_indptr.alloc(Ks + 1)); MMW_TRY(q_indices.alloc((size_t)E.nnzQ)); MMW_TRY(h_max.alloc(Ks));
+        hipLaunchKernelGGL(k_pat_so_count, dim3(grid_rows(K)), dim3(BLOCK), 0, st, K, E.s_ptr, E.s_idx, so_len.p);
+        MMW_HIP(hipGetLastError());
+        std::vector<int32_t> len(Ks), ptr(Ks + 1, 0);
+        MMW_TRY(copy_d2h(len.data(), so_len.p, Ks * sizeof(int32_t), st));
+        for (size_t k = 0; k < Ks; ++k) ptr[k + 1] = ptr[k] + len[k];  // (at most nnz(S): int32)
+        nso = ptr[Ks];
+        MMW_TRY(copy_h2d(so_indptr.p, ptr.data(), ptr.size() * sizeof(int32_t), st));
+        MMW_TRY(so_indices.alloc((size_t)nso)); MMW_TRY(so_data.alloc((size_t)nso)); MMW_TRY(so_hmax.alloc((size_t)nso));
+        hipLaunchKernelGGL(k_pat_so_fill, dim3(grid_rows(K)), dim3(BLOCK), 0, st, K, E.s_ptr, E.s_idx, E.s_val, (const int*)so_indptr.p, E.h_max, so_indices.p,
+                           so_data.p, so_hmax.p);
+        MMW_HIP(hipGetLastError());
+        MMW_HIP(hipMemcpyAsync(q_indptr.p, E.q_ptr, (Ks + 1) * sizeof(int), hipMemcpyDeviceToDevice, st));
+        if (E.nnzQ) MMW_HIP(hipMemcpyAsync(q_indices.p, E.q_idx, (size_t)E.nnzQ * sizeof(int), hipMemcpyDeviceToDevice, st));
+        MMW_HIP(hipMemcpyAsync(h_max.p, E.h_max, Ks * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        return MMW_OK;
+    }
+};
 
 }  // namespace mmw

@@ -37,6 +37,8 @@ struct mmw_solver {
     virtual int factor_spectral(int32_t Z, int32_t index_order, double* out, uint64_t seed) = 0;
     virtual int round(int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
                       int32_t* rem_out) = 0;
+    virtual int round_env(mmw_env* env, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
+                          int32_t* rem_out) = 0;
 };
 namespace {
 // the two refusals of a handle made with device -1
@@ -314,6 +316,18 @@ template <typename T> struct Solver final : mmw_solver {
         if (core.host_only) return host_only_handle();
         MMW_HIP(hipSetDevice(core.device));
         return extras.round(Zr, Dp, gX, nbatch, randv, z_out, rem_out);
+    }
+    // mmw_round against the state `env` holds now (solver_extras.h, round_env).  What cannot run is refused before the device is touched.
+    int round_env(mmw_env* env, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) override {
+        if (core.host_only) return host_only_handle();
+        if (!env) return fail(MMW_ERR_ARG, "mmw_round_env: null environment");
+        const EnvDevice& E = env->e;
+        if (E.K != core.K)
+            return fail(MMW_ERR_ARG, "mmw_round_env: the environment has K = " + std::to_string(E.K) + " stations, the handle K = " + std::to_string(core.K));
+        if (E.device != core.device)
+            return fail(MMW_ERR_ARG, "mmw_round_env: the environment lies on device " + std::to_string(E.device) + ", the handle on device " + std::to_string(core.device));
+        MMW_HIP(hipSetDevice(core.device));
+        return extras.round_env(E.list_source(), Zr, Dp, gX, nbatch, randv, z_out, rem_out);
     }
 };
 template <typename T>

@@ -3,6 +3,7 @@
 #include "factor.h"
 #include "kernels_round.h"
 #include "pattern.h"
+#include "pattern_device.h"
 #include "runtime.h"
 
 namespace mmw {
@@ -228,16 +229,46 @@ template <typename T> struct Extras {
         return MMW_OK;
     }
 
-    int round(int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
-        if (Z < 1 || Dp < 1 || nb < 1) return fail(MMW_ERR_ARG, "mmw_round: Z, D' and nbatch must be positive");
-        if (!randv_h || !z_out || !rem_out) return fail(MMW_ERR_ARG, "mmw_round: null pointer");
+    // the lists one rounding reads: the handle's own state, or the set built from an environment (round_env)
+    struct RoundView {
+        const int* so_indptr; const int* so_indices; const int* q_indptr; const int* q_indices;
+        const double* so_data; const double* so_hmax; const double* h_max;
+    };
+    // every refusal of mmw_round / mmw_round_env (`who`) that needs no device: before anything is allocated, copied, launched or timed
+    int round_check(const std::string& who, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) const {
+        if (Z < 1 || Dp < 1 || nb < 1) return fail(MMW_ERR_ARG, who + ": Z, D' and nbatch must be positive");
+        if (!randv_h || !z_out || !rem_out) return fail(MMW_ERR_ARG, who + ": null pointer");
         // gX == nullptr: the factor this handle computed last, where mmw_factor left it on the device (no copy out and in again)
         if (!gX_h && ((size_t)K * Dp != fac.last_n || Dp != fac.last_rank || fac.last_n == 0))
-            return fail(MMW_ERR_STATE, "mmw_round: gX is null and the handle holds no factor of K x D'");
-        // every Z this call cannot run is refused here, before anything is allocated, copied, launched or timed: k_greedy_b keeps
-        // GB_WAVES rows of Z flags in LDS (Z <= 4800, which also keeps k_slot_pref's 8 Z bytes within the default 64 KiB)
+            return fail(MMW_ERR_STATE, who + ": gX is null and the handle holds no factor of K x D'");
+        // every Z this call cannot run is refused here: k_greedy_b keeps GB_WAVES rows of Z flags in LDS (Z <= 4800, which also keeps
+        // k_slot_pref's 8 Z bytes within the default 64 KiB)
+        if ((size_t)GB_WAVES * Z * 4 > 150 * 1024) return fail(MMW_ERR_ARG, who + ": 32 Z bytes exceed the greedy kernel's LDS");
+        return MMW_OK;
+    }
+    int round(int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
+        MMW_TRY(round_check("mmw_round", Z, Dp, gX_h, nb, randv_h, z_out, rem_out));
+        const RoundView own{so_indptr.p, so_indices.p, q_indptr.p, q_indices.p, so_data.p, so_hmax.p, h_max.p};
+        return round_on(own, Z, Dp, gX_h, nb, randv_h, z_out, rem_out);
+    }
+    // ---- mmw_round_env: the same rounding against the state an environment holds now.  The second list set belongs to the handle and is
+    // kept for the (environment, generation) it was built from: the attempts of one time point, and every point of a sweep in which nobody
+    // moved, build it once.  The handle's own lists, its iterate and its factor are not touched.
+    RoundListSet env_lists;
+    uint64_t env_uid = 0, env_gen = 0;  // uid 0: nothing cached
+    int round_env(const EnvListSource& E, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
+        MMW_TRY(round_check("mmw_round_env", Z, Dp, gX_h, nb, randv_h, z_out, rem_out));
+        if (env_uid != E.uid || env_gen != E.gen) {
+            env_uid = 0;
+            MMW_TRY(env_lists.build(st, E));
+            env_uid = E.uid; env_gen = E.gen;
+        }
+        const RoundListSet& L = env_lists;
+        const RoundView view{L.so_indptr.p, L.so_indices.p, L.q_indptr.p, L.q_indices.p, L.so_data.p, L.so_hmax.p, L.h_max.p};
+        return round_on(view, Z, Dp, gX_h, nb, randv_h, z_out, rem_out);
+    }
+    int round_on(const RoundView& V, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
         const size_t baseb = (size_t)GB_WAVES * Z * 4;
-        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_round: 32 Z bytes exceed the greedy kernel's LDS");
         const size_t nP = (size_t)nb * K * Z;
         if (gX_h) MMW_TRY(ensure(gX, (size_t)K * Dp));
         const double* gX_d = gX_h ? gX.p : fac.out64.p;
@@ -270,7 +301,7 @@ template <typename T> struct Extras {
         if (kt) MMW_TRY(kt->end());
         MMW_HIP(hipGetLastError());
         if (kt) MMW_TRY(kt->begin(KT_GREEDY));
-        hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, order.p, so_indptr.p, q_indptr.p, h_max.p, ghdr.p);
+        hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, order.p, V.so_indptr, V.q_indptr, V.h_max, ghdr.p);
         // steps scheduled out of order (kernels_round.h, k_greedy_schedule): interaction masks of the visiting order, the schedule,
         // the headers step by step; then one workgroup per attempt follows it
         MMW_TRY(ensure(gmask, (size_t)K));
@@ -280,7 +311,7 @@ template <typename T> struct Extras {
         MMW_HIP(hipMemsetAsync(gmask.p, 0, (size_t)K * sizeof(unsigned), st));
         const size_t pairs = (size_t)K * GS_W;
         hipLaunchKernelGGL(k_greedy_cmask, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, (const GreedyHdr*)ghdr.p,
-                           so_indices.p, q_indices.p, gmask.p);
+                           V.so_indices, V.q_indices, gmask.p);
         hipLaunchKernelGGL(k_greedy_schedule, dim3(1), dim3(WAVE), 0, st, K, (const unsigned*)gmask.p, gsched.p, gnsteps.p);
         hipLaunchKernelGGL(k_greedy_sched_headers, dim3(grid_elems((size_t)K * 2)), dim3(BLOCK), 0, st, K, (const int*)gnsteps.p, (const int*)gsched.p,
                            (const GreedyHdr*)ghdr.p, ghdr_s.p);
@@ -295,11 +326,11 @@ template <typename T> struct Extras {
         if (slot_lds) {
             MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
             hipLaunchKernelGGL((k_greedy_b<true, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
-                               so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
+                               V.so_indices, V.so_data, V.so_hmax, V.q_indices, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
         } else {
             MMW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_greedy_b<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
             hipLaunchKernelGGL((k_greedy_b<false, true>), dim3(nb), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr, pref.p,
-                               so_indices.p, so_data.p, so_hmax.p, q_indices.p, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
+                               V.so_indices, V.so_data, V.so_hmax, V.q_indices, gain.p, slot.p, rem.p, (const int*)gnsteps.p);
         }
         if (kt) MMW_TRY(kt->end());
         MMW_HIP(hipGetLastError());

@@ -5,6 +5,10 @@ draws from the global NumPy stream in the same order (the `randint` fill of user
 seeded script continues with the same stream.  The slot passes run in HIP kernels (`mmw_gm_*`, include/mmw_hip.h,
 csrc/kernels_gm.h); the host forms the keys with the reference's own scipy expressions.
 
+A device-resident state of a generator (`DeviceEnv.device_state()`) gets its handle built on the device (`GreedyHandle.from_env`)
+and its keys from the handle itself (`GreedyHandle.key`): the state is never copied to the host.  A `DeviceState` of CSR
+arrays still hands out its host copy.
+
 Visiting order (MAX_GAIN / MAX_ASSO), chosen by the keyword `order` or the environment variable MMW_GM_ORDER:
   * "reference" (default): every slot visits the unassigned users in `kindx[np.argsort(-key[not_assigned])]`, evaluated on the
     host exactly as the reference does (gm.py:31-32); one device pass per slot.  On the same host this is the reference's result.
@@ -33,9 +37,28 @@ def _order_mode(order):
     return mode
 
 
+def _on_env(state, device):
+    """True for the device-resident state of a generator: its greedy handle is built where the state lies (device -1, the host C++
+    procedures, still takes the host copy)."""
+    return (DEVICE if device is None else int(device)) >= 0 and isinstance(state, _lib.DeviceState) and isinstance(state.env, _lib.DeviceEnv)
+
+
 def _host_state(state):
-    """The host triple: a device-resident state (of a DeviceEnv or a DeviceCSR) hands out its host copy, made once (GreedyHandle takes host arrays)."""
+    """The host triple: a device-resident state of CSR arrays hands out its host copy, made once (GreedyHandle takes host arrays)."""
     return state.host() if isinstance(state, _lib.DeviceState) else state
+
+
+def _env_handle(state):
+    """The greedy handle of a generator's device-resident state (`GreedyHandle.from_env`), reused while that very state is asked for."""
+    if _cache["key"] == "env" and _cache["held"] is state and _cache["handle"] is not None:
+        state.check()
+        return _cache["handle"]
+    if _cache["handle"] is not None:
+        _cache["handle"].close()
+        _cache["handle"] = None
+    g = _lib.GreedyHandle.from_env(state.env)
+    _cache.update(key="env", handle=g, held=state)
+    return g
 
 
 def _state_key(state, device):
@@ -78,10 +101,15 @@ def _asso_key(state):
     return np.asarray(state[1].sum(axis=1)).ravel()
 
 
-def _slot_major(key, Z, state, nattempt, not_Z_bound, order, device):
-    state = _host_state(state)
-    K = state[0].shape[0]
-    g = _handle(state, device)
+def _slot_major(kind, Z, state, nattempt, not_Z_bound, order, device):
+    if _on_env(state, device):  # the handle and the key where the state lies (mmw_gm_create_from_env, mmw_gm_key): bitwise the host expressions below
+        g = _env_handle(state)
+        K, key = g.K, g.key(kind)
+    else:
+        state = _host_state(state)
+        K = state[0].shape[0]
+        g = _handle(state, device)
+        key = _asso_key(state) if kind else _gain_key(state)
     if not_Z_bound:
         Z = K
     if _order_mode(order) == "stable":
@@ -114,7 +142,7 @@ class MAX_GAIN:
 
     @staticmethod
     def run(Z, state, nattempt=1, not_Z_bound=False, order=None, device=None):
-        return _slot_major(_gain_key(_host_state(state)), Z, state, nattempt, not_Z_bound, order, device)
+        return _slot_major(0, Z, state, nattempt, not_Z_bound, order, device)
 
 
 class MAX_ASSO:
@@ -122,7 +150,7 @@ class MAX_ASSO:
 
     @staticmethod
     def run(Z, state, nattempt=1, not_Z_bound=False, order=None, device=None):
-        return _slot_major(_asso_key(_host_state(state)), Z, state, nattempt, not_Z_bound, order, device)
+        return _slot_major(1, Z, state, nattempt, not_Z_bound, order, device)
 
 
 class MAX_RAND:
@@ -130,9 +158,13 @@ class MAX_RAND:
 
     @staticmethod
     def run(Z, state, nattempt=1, device=None):
-        state = _host_state(state)
-        K = state[0].shape[0]
-        g = _handle(state, device)
+        if _on_env(state, device):
+            g = _env_handle(state)
+            K = g.K
+        else:
+            state = _host_state(state)
+            K = state[0].shape[0]
+            g = _handle(state, device)
         inprod = np.random.randn(Z, K)  # gm.py:148-150, same draws in the same order
         sorted_indices = np.argsort(-inprod, axis=0)
         rank = np.argsort(np.random.randn(K))

@@ -51,6 +51,8 @@ class sdp_solver:
 
     def _device_solver(self, Z, state, nit=1, eta=None, need_loop=False, warm=False):
         """A device handle holding `state` (reused across the binary search's solve/rounding pairs)."""
+        if isinstance(state, _lib.DeviceState):
+            state.check()  # (an environment that has moved since: this state's arrays are gone, even where a handle of them is still held)
         if self._same_state(state):
             s = self._dev[2]
             if need_loop:  # same state, another slot count: keep pattern, blocking and device copies
