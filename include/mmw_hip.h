@@ -87,7 +87,7 @@ enum mmw_field {
     MMW_F_PATTERN = 25,     /* [2*nnzL + 4*K] the pattern part of an instance's fp64 arena as the batch kernels read it: S_T'[row,col] and
                              S_T'[col,row] on the L pattern, h_max, S_sum, 1 / norm_H, cH; batches only, MMW_ERR_STATE on a host-only one */
     MMW_F_BUILD_INFO = 26,  /* [2]    live, per instance: {how the batch was built: 0 from host arrays (mmw_batch_create), 1 on the
-                             device (mmw_batch_create_from_env); 1 while the instance's host lists are complete, 0 while a batch built on
+                             device (mmw_batch_create_from_env, mmw_batch_create_from_csr); 1 while the instance's host lists are complete, 0 while a batch built on
                              the device has not fetched them yet}; batches only */
     MMW_F_LAPLACIAN = 27,   /* [nnzL] the Laplacian of S_gain + S_gain^T (diagonal zeroed; sdp_solver.py:173-176) on the L pattern, fp64:
                              -(S[r,c] + S[c,r]) off the diagonal (0 where the pattern holds the entry through Q alone), the sum of
@@ -753,6 +753,30 @@ int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int
  * anything is allocated; nnzL, the arena size and norm_H after the count pass, before the arenas are made.  There is no host-only
  * form. */
 int mmw_batch_create_from_env(mmw_batch** out, mmw_batch_env* env, const int32_t* Z, int32_t rank_radio, double eta, const int32_t* nit);
+/* The batch for B CSR states that lie on the device (mmw_csr), built there, one workgroup per instance
+ * (csrc/kernels_batch_csr_pattern.h, csrc/batch_from_csr.h): mmw._process_state and the prologue of mmw._run
+ * (sim_src/alg/mmw.py:26-60) per instance, without a host copy of any state.  All csr[b] lie on one device and the batch is made
+ * there; the same mmw_csr may appear more than once.  It is the batch mmw_batch_create makes from the arrays mmw_csr_state hands out
+ * for every csr[b] at the same Z[b], rank_radio, eta and nit[b]: mmw_batch_sizes, every mmw_batch_read_i32 list and every
+ * mmw_batch_read_f64 field are equal bit for bit, and so is everything computed from them.
+ * Round trips, none of which depends on B: one upload (the per-instance table of the seven pointers and sizes), the count launch,
+ * which validates every instance itself, ONE readback for all instances (the verdicts, the sizes, l_indptr, S_sum, the squared row
+ * sums, h_max), norm_H and cH on the host (they depend on Z), one upload, the fill launch and one launch for the initial point.
+ * The batch copies the state's lists device to device and keeps no reference to any mmw_csr: each may be destroyed as soon as the
+ * call returns, and the arrays behind a wrapped one may be freed.  The host lists behind mmw_batch_read_i32 (but MMW_I_L_INDPTR),
+ * MMW_F_ST_DATA, mmw_batch_export and mmw_batch_carry(_map) are fetched per instance the first time an entry needs them, from that
+ * copy (MMW_F_BUILD_INFO: {1, 0 then 1}); the first mmw_batch_gm fetches Q of every instance for its clique decision.
+ * If every csr[b] is host-only (device -1) the result is the host-only batch mmw_batch_create(device = -1) makes from the same
+ * arrays, after the same per-row checks.
+ * Refused, *out untouched:
+ *   before anything is allocated or launched, MMW_ERR_ARG: B < 1, a NULL csr[b], host-only states mixed with states on a device,
+ *     states on different devices, nit[b] < 1, K < 2, Z[b] < 2, K or D over the batch limits of mmw_batch_create, in its words;
+ *   a malformed state, MMW_ERR_ARG "mmw_batch_create_from_csr: instance b: " and mmw_create's words for it (the checks are
+ *     mmw_create_from_csr's, run inside the count launch: an instance whose check failed writes nothing that depends on its
+ *     columns); the lowest failing instance is the one reported;
+ *   after the count pass, before the arenas are made, MMW_ERR_ARG: nnzL or the arena size over the limits, a zero norm_H. */
+int mmw_batch_create_from_csr(mmw_batch** out, int32_t B, mmw_csr* const* csr, const int32_t* Z, int32_t rank_radio, double eta,
+                              const int32_t* nit);
 /* mmw_batch_gm on the state of the environment's last move: see there */
 int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out,
                      int32_t* zz_out, int32_t* rem_out, double* key_out);

@@ -47,7 +47,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_env_state", "mmw_batch_env_evaluate", "mmw_batch_round_env", "mmw_batch_gm", "mmw_batch_env_gm",
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
-           "mmw_batch_create_from_env", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
+           "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
            "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key"]
 
 
@@ -165,6 +165,7 @@ def lib():
     L.mmw_batch_factor_random.argtypes = [C.c_void_p, p_i32, C.POINTER(C.c_uint64)]
     L.mmw_batch_factor_spectral.argtypes = [C.c_void_p, p_i32, p_i32]
     L.mmw_batch_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, p_i32, C.c_int32, C.c_double, p_i32]
+    L.mmw_batch_create_from_csr.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), p_i32, C.c_int32, C.c_double, p_i32]
     for name in EXPORTS:
         if name not in ("mmw_last_error",):
             getattr(L, name).restype = C.c_int
@@ -593,6 +594,29 @@ class BatchSolver(_Handle):
         self._h = C.c_void_p()
         check(lib().mmw_batch_create_from_env(C.byref(self._h), env._h, _pi(Zarr), int(rank_radio), float(eta), _pi(narr)))
         self._created(env.device, nits)
+        return self
+
+    @classmethod
+    def from_csr(cls, csrs, Zs, nit, eta, rank_radio=2):
+        """The batch for states that lie on the device as CSR arrays, built there without a host copy of any of them
+        (mmw_batch_create_from_csr): the object `BatchSolver(Zs, [c.state() for c in csrs], nit, eta, rank_radio)` gives, field for
+        field.  csrs: `DeviceCSR`s, or `DeviceState`s whose owner is one, all on one device (the same one may appear more than once);
+        all with device = -1 gives the host-only batch.  It keeps nothing of them: each may be closed at once."""
+        owners = [csr_owner(c) for c in csrs]
+        B = len(owners)
+        if B < 1 or len(Zs) != B:
+            raise MMWError("BatchSolver.from_csr: one slot count per state, at least one state")
+        for i, c in enumerate(owners):
+            if c is None or not c._h:
+                raise MMWError("BatchSolver.from_csr: entry %d is not an open DeviceCSR (or a DeviceState of one)" % i)
+        nits = np.broadcast_to(np.asarray(nit, dtype=np.int32), (B,))
+        self = cls.__new__(cls)
+        self.B = B
+        Zarr, narr = _i32(Zs), _i32(nits)
+        handles = (C.c_void_p * B)(*[c._h.value for c in owners])
+        self._h = C.c_void_p()
+        check(lib().mmw_batch_create_from_csr(C.byref(self._h), B, handles, _pi(Zarr), int(rank_radio), float(eta), _pi(narr)))
+        self._created(owners[0].device, nits)
         return self
 
     def _created(self, device, nits):
@@ -1365,6 +1389,16 @@ class DeviceState:
 
     def __len__(self):
         return 3
+
+
+def csr_owner(state):
+    """The `DeviceCSR` behind `state` -- a DeviceCSR itself or a DeviceState of one -- else None (host triples, a DeviceState of a
+    DeviceEnv): what `BatchSolver.from_csr` takes and the batch workflows route by."""
+    if isinstance(state, DeviceCSR):
+        return state
+    if isinstance(state, DeviceState) and isinstance(state._env, DeviceCSR):
+        return state.env
+    return None
 
 
 class GreedyHandle(_Handle):

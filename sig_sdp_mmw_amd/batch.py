@@ -18,6 +18,10 @@ a round of probes is then one `iterate`, one `factor` and one `round`, and insta
 handle path inside the same call.  The two factor by different methods, so their bases differ: the same bisection, not bitwise
 the same slots.
 
+`states` are (S_gain, Q_asso, h_max) triples.  When every one of them is a `DeviceCSR.device_state()` on one device,
+`run_with_state_many`, `convergence_many` and `search_many` build their batch there (`BatchSolver.from_csr`) and make no host copy
+of a state; the results are bitwise those of the triples `c.state()`.
+
 `search_many` runs the bisection of binary_search_relaxation.py:44-72 for all instances in lockstep: each instance keeps its own
 bounds, all current probes run in one `mmw_batch_iterate`, and an instance whose search has ended sits out.  Sketches are the
 device's Philox blocks keyed by a per-(instance, probe) seed, and the rounding's projections come from a generator keyed the same
@@ -46,13 +50,16 @@ def _rank(K, Z, rank_radio):
 class _Handles:
     """One fp64 handle per state, rebound to each probe's slot count (the export target)."""
 
-    def __init__(self, states, nit, eta, rank_radio, device):
+    def __init__(self, states, nit, eta, rank_radio, device, owners=None):
         self.states, self.nit, self.eta, self.rank_radio, self.device = states, nit, eta, rank_radio, device
+        self.owners = owners  # the states' DeviceCSRs when the batch was built from them (`_batch`): the handles are built there too
         self.h = [None] * len(states)
 
     def get(self, i, Z):
         h = self.h[i]
-        if h is None:
+        if h is None and self.owners is not None:
+            h = self.h[i] = self.owners[i].solver(Z, self.nit, self.eta, rank_radio=self.rank_radio, dtype=_lib.F64)
+        elif h is None:
             h = self.h[i] = _lib.Solver(Z, self.states[i], self.nit, self.eta, rank_radio=self.rank_radio, dtype=_lib.F64, device=self.device)
         elif h.Z != Z:
             h.set_slots(Z, self.nit)
@@ -63,6 +70,28 @@ class _Handles:
             if h is not None:
                 h.close()
         self.h = [None] * len(self.states)
+
+
+def _csr_route(states):
+    """The `DeviceCSR` owners when EVERY state is a `DeviceState` of a `DeviceCSR` and all of them lie on one device >= 0, else None:
+    host triples, a mix, a DeviceState of a DeviceEnv and device = -1 owners take the host path untouched."""
+    owners = []
+    for st in states:
+        c = _lib.csr_owner(st) if isinstance(st, _lib.DeviceState) else None
+        if c is None or c.device < 0 or (owners and c.device != owners[0].device):
+            return None
+        owners.append(c)
+    return owners or None
+
+
+def _batch(Zs, states, nit, eta, rank_radio, device):
+    """(batch, owners): the batch of a workflow.  States that lie on the device as CSR arrays (`_csr_route`) are built into it there
+    (`BatchSolver.from_csr`: no host copy of any state; bitwise the batch of the host triples `c.state()`), on their own device;
+    anything else goes through `BatchSolver(Zs, states, ...)` on `device`, owners None."""
+    owners = _csr_route(states)
+    if owners is not None:
+        return _lib.BatchSolver.from_csr(owners, list(Zs), nit, eta, rank_radio=rank_radio), owners
+    return _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device), None
 
 
 def _factor(batch, i, handle, Z, rank_radio, seed):
@@ -152,8 +181,8 @@ def run_with_state_many(bs_iteration, Zs, states, nit=150, eta=0.04, seeds=None,
     in_batch = _check_epilogue(epilogue)
     _factor_split(None, factor_split, in_batch)
     seeds = np.arange(len(states), dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
-    b = _lib.BatchSolver(list(Zs), states, nit, eta, rank_radio=rank_radio, device=device)
-    hs = _Handles(states, nit, eta, rank_radio, device)
+    b, owners = _batch(Zs, states, nit, eta, rank_radio, device)
+    hs = _Handles(states, nit, eta, rank_radio, device, owners)
     try:
         _split(b, split)
         _row_split(b, row_split)
@@ -179,7 +208,7 @@ def convergence_many(Zs, states, nit, eta, seeds=None, rank_radio=2, device=0, s
     nits = [int(x) for x in np.broadcast_to(np.asarray(nit, dtype=np.int64), (B,))]
     etas = np.broadcast_to(np.asarray(eta, dtype=np.float64), (B,))
     seeds = np.arange(B, dtype=np.uint64) if seeds is None else np.asarray(seeds, dtype=np.uint64)
-    b = _lib.BatchSolver(list(Zs), states, nits, float(etas[0]), rank_radio=rank_radio, device=device)
+    b, _ = _batch(Zs, states, nits, float(etas[0]), rank_radio, device)
     try:
         b.set_eta(etas)
         b.set_gap(True)
@@ -234,8 +263,8 @@ def search_many(states, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, de
     iters = [[] for _ in range(B)]
     out = [None] * B
     mids = [max(2, math.floor(float(l + r) / 2.)) for l, r in zip(left, right)]
-    b = _lib.BatchSolver(mids, states, nit, eta, rank_radio=rank_radio, device=device)
-    hs = _Handles(states, nit, eta, rank_radio, device)
+    b, owners = _batch(mids, states, nit, eta, rank_radio, device)
+    hs = _Handles(states, nit, eta, rank_radio, device, owners)
     try:
         _split(b, split)
         _row_split(b, row_split)

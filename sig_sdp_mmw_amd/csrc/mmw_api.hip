@@ -1,6 +1,7 @@
 // C-ABI of the MI355X MMW hot path (include/mmw_hip.h), the library's one translation unit.  The handles: solver.h (mmw_solver, mmw_env),
-// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch: batch_core.h and the parts' headers), batch_env_handle.h (mmw_batch_env), batch_from_env.h (a batch built from an environment on the device).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
+// gm_handle.h (mmw_gm), batch_handle.h (mmw_batch: batch_core.h and the parts' headers), batch_env_handle.h (mmw_batch_env), batch_from_env.h and batch_from_csr.h (a batch built on the device, from an environment or from CSR states).  Every entry that can throw runs inside guarded() (runtime.h): no C++ exception crosses the C boundary.
 #include "batch_env_handle.h"
+#include "batch_from_csr.h"
 #include "batch_from_env.h"
 #include "batch_handle.h"
 #include "gm_handle.h"
@@ -348,6 +349,19 @@ int mmw_batch_create_from_env(mmw_batch** out, mmw_batch_env* env, const int32_t
         if (!(eta >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
         auto bt = std::make_unique<mmw_batch>();
         MMW_TRY(batch_init_from_env(*bt, *env, Z, rank_radio, eta, nit));
+        *out = bt.release();
+        return MMW_OK;
+    });
+}
+int mmw_batch_create_from_csr(mmw_batch** out, int32_t B, mmw_csr* const* csr, const int32_t* Z, int32_t rank_radio, double eta, const int32_t* nit) {
+    return guarded("mmw_batch", [&]() -> int {
+        if (!out || !csr || !Z || !nit) return fail(MMW_ERR_ARG, "mmw_batch_create_from_csr: null pointer");
+        if (B < 1) return fail(MMW_ERR_ARG, "mmw_batch_create_from_csr: B must be >= 1");
+        if (B > 65535) return fail(MMW_ERR_ARG, "mmw_batch_create_from_csr: at most 65535 instances per batch");
+        if (rank_radio < 1) return fail(MMW_ERR_ARG, "rank_radio must be >= 1");
+        if (!(eta >= 0.0)) return fail(MMW_ERR_ARG, "eta must be non-negative");
+        auto bt = std::make_unique<mmw_batch>();
+        MMW_TRY(batch_init_from_csr(*bt, B, csr, Z, rank_radio, eta, nit));
         *out = bt.release();
         return MMW_OK;
     });
