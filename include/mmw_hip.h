@@ -174,6 +174,26 @@ int mmw_set_slots(mmw_solver* s, int32_t Z, int32_t nit);
  * running sums of X and Y restart from them.  Falls back to mmw_set_slots when the handle has not iterated yet.
  */
 int mmw_set_slots_warm(mmw_solver* s, int32_t Z, int32_t nit);
+/*
+ * mmw_carry: the warm start ACROSS states on the handle side (the stations have moved; a re-solve per time point of the online sweeps at
+ * any K).  `src` is a handle that has iterated on the old state, `dst` a handle on the new state -- from mmw_create, mmw_create_from_env
+ * or mmw_create_from_csr -- that has run no iteration.  The rule is mmw_batch_carry's: L and X entry (row, col) of `dst` take `src`'s
+ * value at (row, col) where `src`'s pattern stores it, else 0; e_accu and Y [D-part K | F-part E_asso | H-part K] carry by user and, the
+ * F-part, by pair (asso_x, asso_y), 0 for a pair `src` lacks -- also where `src` stores the pair's entry as a gain entry.  Y is not
+ * renormalised.  The running sums follow the handle's warm convention, as mmw_set_slots_warm leaves them: xavg = xval, yavg = Y.
+ * e_this, the K x D blocks, the iteration count 0 and nit stay as creation left them.  No index map is made on the host: the two
+ * patterns are matched on the device.  `dst` also takes over the run history mmw_set_slots_warm would have kept on `src` (its first
+ * chunk is short and planned on `src`'s last plan).  `src` is only read: it is settled and its stream waited for.  Ordering: the call
+ * returns after the work on `dst`'s stream has finished, so `src` may be iterated, reset or destroyed as soon as it is back.
+ * A `src` that has run no iteration leaves `dst` cold (MMW_OK).  Refused before anything is written: dst == src (MMW_ERR_ARG), a handle
+ * made with device -1 (MMW_ERR_STATE), different devices, dtypes or K (MMW_ERR_ARG), a `dst` that has iterated (MMW_ERR_STATE).  Z and
+ * rank_radio may differ.
+ * mmw_carry_map: the two maps that rule defines, computed on the host by merging the two patterns -- lmap[nl = nnzL of dst] the position
+ * in `src`'s L / X arrays, cmap[nc = C of dst] the position in `src`'s constraint vector, -1 where `src` holds none.  Needs no device:
+ * handles made with device -1 answer, handles built on the device fetch their lists first.  What the tests hold the device matching to.
+ */
+int mmw_carry(mmw_solver* dst, mmw_solver* src);
+int mmw_carry_map(mmw_solver* dst, mmw_solver* src, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc);
 /* step size for the iterations that follow (the reference reads self.eta on every run, mmw.py:137,167) */
 int mmw_set_eta(mmw_solver* s, double eta);
 

@@ -48,7 +48,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
-           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key"]
+           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map"]
 
 
 class MMWError(RuntimeError):
@@ -85,6 +85,8 @@ def lib():
     L.mmw_set_slots.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.mmw_set_slots_warm.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.mmw_set_eta.argtypes = [C.c_void_p, C.c_double]
+    L.mmw_carry.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmw_carry_map.argtypes = [C.c_void_p, C.c_void_p, p_i32, C.c_int64, p_i32, C.c_int64]
     L.mmw_iterate.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_uint64]
     L.mmw_sync.argtypes = [C.c_void_p]
     L.mmw_sketch.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, p_f64, C.c_int64]
@@ -392,6 +394,23 @@ class Solver(_Handle):
         check((lib().mmw_set_slots_warm if warm else lib().mmw_set_slots)(self._h, int(Z), int(nit)))
         self._load_sizes()
         self._timed = 0
+
+    def carry_from(self, src):
+        """mmw_carry: take over the iterate (e_accu, L, X, Y) of `src`, a handle of the same users on the state they were in before
+        they moved, into this handle, which has not iterated: L and X by (row, col), e_accu and Y by user and by association pair, 0
+        for what `src` does not hold, matched on the device; Y is not renormalised.  The sums restart as `set_slots(..., warm=True)`
+        leaves them (xavg = xval, yavg = Y), `iterations_done` stays 0 and `nit` is unchanged; this handle's first chunk is planned on
+        `src`'s history.  A `src` that never iterated leaves this handle cold.  `src` is only read, and the call returns after the
+        device's work: `src` may be iterated, reset or closed at once."""
+        check(lib().mmw_carry(self._h, src._h))
+
+    def carry_map(self, src):
+        """mmw_carry_map: (lmap int32[nnzL], cmap int32[C]) -- for every entry of this handle's L pattern and of its constraint
+        vector the position in `src`'s, -1 where `src` holds none.  Computed on the host; works on device=-1 handles."""
+        lmap = np.empty(self.nnzL, dtype=np.int32)
+        cmap = np.empty(self.C, dtype=np.int32)
+        check(lib().mmw_carry_map(self._h, src._h, _pi(lmap), int(lmap.size), _pi(cmap), int(cmap.size)))
+        return lmap, cmap
 
     def iterate(self, n, randv=None, seed=0):
         if self._timing:

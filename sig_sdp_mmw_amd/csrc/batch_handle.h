@@ -318,7 +318,7 @@ inline int batch_carry_pair(const char* who, const mmw_batch* dst, const mmw_bat
                                      std::to_string(src->core.pat(b).K) + " in the source (a carry keeps the users and moves them)");
     return MMW_OK;
 }
-// mmw_batch_carry_map: the two index maps of one instance (BatchCore::carry_maps); host patterns only, so device -1 batches answer too
+// mmw_batch_carry_map: the two index maps of one instance (carry_maps, pattern.h); host patterns only, so device -1 batches answer too
 inline int batch_carry_map(mmw_batch* dst, mmw_batch* src, int b, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc) {
     MMW_TRY(dst->core.check_inst(b));
     MMW_TRY(src->core.check_inst(b));
@@ -327,7 +327,7 @@ inline int batch_carry_map(mmw_batch* dst, mmw_batch* src, int b, int32_t* lmap,
     if (nl != N.nnzL() || nc != N.C())
         return fail(MMW_ERR_ARG, "mmw_batch_carry_map: instance " + std::to_string(b) + ": wrong lengths " + std::to_string(nl) + ", " + std::to_string(nc) +
                                      ", expected nnzL = " + std::to_string(N.nnzL()) + " and C = " + std::to_string(N.C()));
-    BatchCore::carry_maps(N, src->core.full(b), lmap, cmap);
+    carry_maps(N, src->core.full(b), lmap, cmap);
     return MMW_OK;
 }
 // mmw_batch_carry: (e_accu, L, X, Y) of `src`, a batch on the old states that has iterated, re-indexed onto `dst`, a batch on the new
@@ -369,7 +369,7 @@ inline int batch_carry(mmw_batch* dst, mmw_batch* src, const int32_t* take) {
         std::memcpy(stage.data() + w_dst + DW * t, &D.desc[b], sizeof(BatchDesc));
         const CarryItem it{om, om + N.nnzL()};
         std::memcpy(stage.data() + w_item + IW * t, &it, sizeof it);
-        BatchCore::carry_maps(N, S.full(b), maps + it.o_lmap, maps + it.o_cmap);
+        carry_maps(N, S.full(b), maps + it.o_lmap, maps + it.o_cmap);
         om += N.nnzL() + N.C();
     }
     MMW_HIP(hipSetDevice(D.device));

@@ -11,7 +11,7 @@
 //   -1               reads as 0.0: an entry of L that did not exist has accumulated no loss, an X entry outside the old pattern
 //                    was never sampled, a constraint that did not exist has accumulated no violation and carries no weight.
 //
-// Both maps are computed on the host by merging sorted rows (BatchCore::carry_maps in batch_core.h) and arrive in the call's upload.
+// Both maps are computed on the host by merging sorted rows (carry_maps in pattern.h) and arrive in the call's upload.
 // Y is NOT renormalised: with pairs lost or gained its sum is no longer 1.  The first iteration's softmax rewrites Y from e_accu;
 // before that only the first term of the running sum of Y and the first row of the gap log read it.
 // Everything else of the new instance stays as its creation left it (sums, e_this, the per-row scalars, the K x D blocks and the

@@ -98,6 +98,22 @@ int mmw_bench_spmm(mmw_solver* s, int blocked, int reps, double* avg_us) { retur
 int mmw_reset(mmw_solver* s, int32_t nit) { return entry("mmw_reset", !s, "null solver handle", [&] { return s->reset(nit); }); }
 int mmw_set_slots(mmw_solver* s, int32_t Z, int32_t nit) { return entry("mmw_set_slots", !s, "null solver handle", [&] { return s->set_slots(Z, nit, 0); }); }
 int mmw_set_slots_warm(mmw_solver* s, int32_t Z, int32_t nit) { return entry("mmw_set_slots_warm", !s, "null solver handle", [&] { return s->set_slots(Z, nit, 1); }); }
+// ---- the iterate carried from a handle on the state before the stations moved to one on the state after (solver_carry.h)
+int mmw_carry(mmw_solver* dst, mmw_solver* src) { return entry("mmw_carry", !dst || !src, "null solver handle", [&] { return dst->carry(src); }); }
+int mmw_carry_map(mmw_solver* dst, mmw_solver* src, int32_t* lmap, int64_t nl, int32_t* cmap, int64_t nc) {
+    return entry("mmw_carry_map", !dst || !src || (!lmap && nl) || (!cmap && nc), "null pointer", [&]() -> int {
+        MMW_TRY(carry_refusal("mmw_carry_map", dst->carry_info(), src->carry_info(), false));
+        const HostPattern* N = nullptr;
+        const HostPattern* O = nullptr;
+        MMW_TRY(dst->carry_pattern(&N));
+        MMW_TRY(src->carry_pattern(&O));
+        if (nl != N->nnzL() || nc != N->C())
+            return fail(MMW_ERR_ARG, "mmw_carry_map: wrong lengths " + std::to_string(nl) + ", " + std::to_string(nc) + ", expected nnzL = " + std::to_string(N->nnzL()) +
+                                         " and C = " + std::to_string(N->C()));
+        carry_maps(*N, *O, lmap, cmap);
+        return MMW_OK;
+    });
+}
 int mmw_set_eta(mmw_solver* s, double eta) { return entry("mmw_set_eta", !s, "null solver handle", [&] { return s->set_eta(eta); }); }
 int mmw_iterate(mmw_solver* s, int32_t n, const double* randv, uint64_t seed) { return entry("mmw_iterate", !s, "null solver handle", [&] { return s->iterate(n, randv, seed); }); }
 int mmw_sync(mmw_solver* s) { return entry("mmw_sync", !s, "null solver handle", [&] { return s->sync(); }); }

@@ -249,6 +249,31 @@ static inline std::string build_pattern(HostPattern& P, int32_t K, int32_t Z, co
     return "";
 }
 
+// The index maps of a carry (kernels_batch_carry.h; the solver handle's mmw_carry_map, solver_carry.h) from the pattern O of the old state onto the pattern N of the new one, both
+// of K users: lmap[nnzL of N] by merging the sorted rows of the two L patterns, cmap[C of N] with the D- and the H-part by user
+// and the F-part by merging the two pair lists, which build_pattern leaves sorted by (asso_x, asso_y).  -1: O does not hold it.
+inline void carry_maps(const HostPattern& N, const HostPattern& O, int32_t* lmap, int32_t* cmap) {
+    const int32_t K = N.K;
+    for (int32_t a = 0; a < K; ++a) {
+        int32_t j = O.l_indptr[a];
+        const int32_t je = O.l_indptr[a + 1];
+        for (int32_t e = N.l_indptr[a]; e < N.l_indptr[a + 1]; ++e) {
+            const int32_t c = N.l_indices[e];
+            while (j < je && O.l_indices[j] < c) ++j;
+            lmap[e] = j < je && O.l_indices[j] == c ? j : -1;
+        }
+    }
+    const int64_t En = N.E_asso(), Eo = O.E_asso();
+    for (int32_t k = 0; k < K; ++k) cmap[k] = k;
+    int64_t j = 0;
+    for (int64_t e = 0; e < En; ++e) {
+        const int32_t x = N.asso_x[e], y = N.asso_y[e];
+        while (j < Eo && (O.asso_x[j] < x || (O.asso_x[j] == x && O.asso_y[j] < y))) ++j;
+        cmap[K + e] = j < Eo && O.asso_x[j] == x && O.asso_y[j] == y ? (int32_t)(K + j) : -1;
+    }
+    for (int32_t k = 0; k < K; ++k) cmap[K + En + k] = (int32_t)(K + Eo + k);
+}
+
 // the int32 list behind an MMW_I_* field of the read entries (null: no such field)
 inline const std::vector<int32_t>* host_list_i32(const HostPattern& H, int which) {
     switch (which) {

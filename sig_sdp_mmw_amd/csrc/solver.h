@@ -2,10 +2,12 @@
 // mmw_api.hip includes this once).  The body holds a core (solver_core.h: device, pattern, iterate, engine, blockings, timers) and its
 // parts by value, each with the state and the device buffers of one concern: loop (solver_loop.h: the phases, their scratch, the chunk
 // policy), pending and emax (solver_replay.h: the chunk not yet settled, the riding MMW_F_E_MAX), reads (solver_read.h), envl
-// (solver_create.h: the lists a handle built on the device -- from a generator or from CSR arrays -- still holds there), extras (solver_extras.h).  An ABI method is the
+// (solver_create.h: the lists a handle built on the device -- from a generator or from CSR arrays -- still holds there), extras (solver_extras.h),
+// carried (solver_carry.h: the plan a carry brought along).  An ABI method is the
 // device guard, `settle`, and one call into a part; whatever a new run invalidates in a part goes through on_restart.
 #pragma once
 #include "solver_bench.h"
+#include "solver_carry.h"
 #include "solver_create.h"
 #include "solver_loop.h"
 #include "solver_read.h"
@@ -19,6 +21,9 @@ struct mmw_csr {
 };
 struct mmw_solver {
     virtual ~mmw_solver() {}
+    virtual CarryInfo carry_info() = 0;
+    virtual int carry_pattern(const mmw::HostPattern** out) = 0;  // the host pattern with the lists carry_maps merges (fetched if they still lie on the device)
+    virtual int carry(mmw_solver* src) = 0;
     virtual int sizes(int64_t out[10]) = 0;
     virtual int set_expm(int method, int max_order, double tol) = 0;
     virtual int set_timing(int enabled) = 0;
@@ -52,6 +57,7 @@ template <typename T> struct Solver final : mmw_solver {
     SolverReads<T> reads;
     DeviceLists envl;
     Extras<T> extras;
+    CarriedPlan carried;
     explicit Solver(const Switches& s) : core(s), loop(core.sw), extras(core.sw) {}
     ~Solver() override {
         core.bt.join();  // the build thread works on this handle's members
@@ -140,6 +146,7 @@ template <typename T> struct Solver final : mmw_solver {
         core.iter = 0;
         emax.drop();
         pending.clear();
+        carried.drop();
         if (core.eng.viol_d.p) MMW_TRY(core.eng.clear_violation());
         return core.eng.reset_plan_history(warm);
     }
@@ -226,6 +233,7 @@ template <typename T> struct Solver final : mmw_solver {
         if (!optimistic) {
             pol.chain_ok = false;
             MMW_TRY(loop.iterate_impl(core, n, randv, seed, false));
+            carried.drop();  // (these iterations read their plans back: eng.last is the run's own now)
             return emax.enqueue(core);
         }
         // Chunks enqueued without plan readbacks.  Each chunk starts from a device snapshot; before the next one starts the
@@ -235,17 +243,46 @@ template <typename T> struct Solver final : mmw_solver {
         int left = n;
         while (left > 0) {
             MMW_TRY(settle());
-            const int chunk = pol.chunk_length(core.eng.last, core.sw, core.iter, left);
-            pol.plan_chunk(core.eng.last, core.sw, core.eng.max_order, core.iter, chunk, sizeof(T) == 4, core.bt.afrag16.p != nullptr, loop.plane_rounding());
+            const ExpmPlan& hist = carried.or_last(core.eng.last);  // (after mmw_carry: the source's last plan, for the first chunk)
+            const int chunk = pol.chunk_length(hist, core.sw, core.iter, left);
+            pol.plan_chunk(hist, core.sw, core.eng.max_order, core.iter, chunk, sizeof(T) == 4, core.bt.afrag16.p != nullptr, loop.plane_rounding());
             MMW_TRY(pending.save(core));
             const int iter0 = core.iter;
             const size_t events0 = core.pt.mark();
             MMW_TRY(loop.iterate_impl(core, chunk, nullptr, seed, chunk > 1));
             pol.warm_fresh = false;
+            carried.drop();
             if (chunk > 1) pending.begin(iter0, chunk, seed, events0);
             left -= chunk;
         }
         return emax.enqueue(core);
+    }
+    // ---- mmw_carry (solver_carry.h): this handle, on the state after the stations moved, takes over the iterate `src_` reached on the
+    // state before.  Every refusal comes before anything of either handle is touched; a source that never iterated leaves this handle cold.
+    CarryInfo carry_info() override { return CarryInfo{core.host_only, core.device, sizeof(T) == 4 ? MMW_F32 : MMW_F64, core.K, core.iter}; }
+    int carry_pattern(const HostPattern** out) override {
+        MMW_TRY(envl.ensure_host(core));
+        *out = &core.H;
+        return MMW_OK;
+    }
+    int carry(mmw_solver* src_) override {
+        if (src_ == this) return fail(MMW_ERR_ARG, "mmw_carry: the handle cannot carry from itself");
+        MMW_TRY(carry_refusal("mmw_carry", carry_info(), src_->carry_info(), true));
+        Solver<T>* src = static_cast<Solver<T>*>(src_);  // (same dtype: checked)
+        if (src->core.iter == 0) return MMW_OK;  // nothing to continue from: the fallback of mmw_set_slots_warm
+        MMW_HIP(hipSetDevice(core.device));
+        MMW_TRY(src->settle());
+        MMW_TRY(src->core.x.csr_view(src->core));
+        MMW_HIP(hipStreamSynchronize(src->core.st));
+        MMW_TRY(SolverCarry<T>::gather(core, src->core));
+        MMW_TRY(SolverCarry<T>::derived(core));
+        emax.drop();
+        pending.clear();
+        MMW_TRY(SolverCarry<T>::history(core, loop, carried, src->core, src->loop));
+        // the gather reads the source's buffers from THIS handle's stream, which nothing orders against the source's: it has to be over
+        // before the caller may continue, reset or destroy the source (mmw_batch_carry ends the same way)
+        MMW_HIP(hipStreamSynchronize(core.st));
+        return MMW_OK;
     }
     int sync() override {
         if (core.host_only) return host_only_pattern();

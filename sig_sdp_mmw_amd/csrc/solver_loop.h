@@ -122,6 +122,8 @@ template <typename T> struct SolverLoop {
         c.m_launch = optimistic ? pol.m_guess : 0;
         // from the plan the last settled chunk ended on; not in the first chunk after a warm restart: with another slot count the matrix grows
         // at another rate than the history the extrapolation rests on (its bound was missed and the chunk replayed, measured)
+        // (after mmw_carry the plan the chunk was planned on lies in Solver::carried and eng.last is still zero: this and plan_has_room below
+        // read eng.last, which is right only because warm_fresh masks the first chunk here and chain_ok is false until a chunk has settled)
         c.lag_chunk = optimistic && pol.lagged_ok(co.eng.last, co.sw) && !pol.warm_fresh && !pol.exact_plans_only;
         c.chain = optimistic && pol.chain_ok;      // this chunk continues the previous one (see ChunkPolicy::chain_ok)
         pol.chain_ok = false;

@@ -37,6 +37,13 @@ from .stats import STATS_OBJECT
 _SKETCH_CHUNK_BYTES = 64 << 20
 
 
+def factor_rank_seed(K, Z, rank_radio, run_seed):
+    """(rank, seed) of the factor behind a run at Z slots whose device sketches were keyed `run_seed`: rank min(K - 1, (Z - 1) *
+    rank_radio) (mmw.py:206), and the factor's start block drawn with the run's own seed.  `mmw._run` and `online.online_resolve_sweep`
+    both ask here."""
+    return int(min(K - 1, (Z - 1) * rank_radio)), int(run_seed)
+
+
 class mmw(STATS_OBJECT, sdp_solver):
     def __init__(self, nit=100, rank_radio=2, alpha=1., eta=0.1, log_gap=False, *, dtype=None, rng=None,
                  expm="lanczos", expm_tol=None, expm_max_order=12, device=None, seed=0, warm_start=None, warm_fraction=1.0 / 3.0):
@@ -129,13 +136,13 @@ class mmw(STATS_OBJECT, sdp_solver):
         self.last_expm_info = solver.read(_lib.F_EXPM_INFO)
 
         tic_xavg = self._get_tic()
-        rank = int(np.min([K - 1, (Z - 1) * self.rank_radio]))
+        rank, factor_seed = factor_rank_seed(K, Z, self.rank_radio, dev_seed)
         if self.rng == "host":
             np.random.standard_normal(K)  # the start vector scipy's svds draws at mmw.py:215 (keeps seeded streams aligned)
         # fast path: X_half stays on the device (a DeviceFactor: an array to everything but `rounding`, which reads it in place);
         # MMW_FACTOR_HOST=1 or rng="host" return the NumPy array itself
         resident = self.rng == "device" and os.environ.get("MMW_FACTOR_HOST", "0") in ("", "0")
-        X_half = solver.factor(rank, seed=dev_seed, resident=resident)
+        X_half = solver.factor(rank, seed=factor_seed, resident=resident)
         self._add_np_log("mmw_xavg", 0, np.array([Z, K, self._get_tim(tic_xavg)]))
         return True, X_half
 

@@ -4,16 +4,18 @@
 (K <= 1024).  Here the same sweeps run for one `graphs.mobile_drop` of any size on the single-instance side: a `DeviceEnv` that
 moves (`mmw_env_move`), the solver handle's resident factor rounded against the state the environment holds at every time point
 (`mmw_round_env`), the device scorer, and for the greedy arm a `GreedyHandle.from_env`.  The state never crosses to the host.
+`online_resolve_sweep` is `batch.online_resolve_many` on the same side: a re-solve at every time point on a handle built on the
+device from the moved environment, optionally continuing from the previous point's iterate (`Solver.carry_from`, `mmw_carry`).
 """
 import time
 
 import numpy as np
 
 from . import _lib
-from .batch import _fill, probe_seed
+from .batch import _check_warm, _fill, probe_seed, warm_iterations
 from .binary_search import binary_search_relaxation
 from .graphs import _NOISE_FLOOR_DBM, min_sinr_dec
-from .mmw import mmw
+from .mmw import factor_rank_seed, mmw
 
 
 def _env(drop, device):
@@ -95,6 +97,73 @@ def online_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
                 timings.append({"device_s": t1 - t0, "step_s": time.perf_counter() - t1})
         return out
     finally:
+        alg.close()
+        env.close()
+
+
+def online_resolve_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2,
+                         device=0, dtype=_lib.F32, resolve_nit=None, carry=False, warm_fraction=1.0 / 3.0, timings=None):
+    """`online_sweep` with a re-solve at every time point, for one `graphs.mobile_drop` of any K: the handle's
+    `batch.online_resolve_many` (NOT one of the reference's scripts, which solve once and re-round that factor while the stations
+    walk).  Setup and point 0 are `online_sweep`'s: the resident factor of the solve the bisection ends with, rounded against the
+    unmoved environment.  Z stays at that Z throughout.  Every later point p: `env.move(drop.sta_locs)`, a new handle on the moved
+    state built on the device (`Solver.from_env(env, Z, n_p, eta, rank_radio, dtype)`), `carry_from` the previous point's handle
+    (carry=True; at p = 1 that is the first solve's), `iterate(n_p)` with device sketches keyed probe_seed(seed, 0, 0xC0000 | p),
+    the factor left resident (rank and seed: `mmw.factor_rank_seed` with that key), `round_point` with the generator keyed
+    probe_seed(seed, 0, 0x80000 | p), `env.evaluate`; the previous handle is closed and the drop walks `step_us` microseconds.
+    Iterations per re-solve n_p: `resolve_nit`, or when that is None `batch.warm_iterations(nit, warm_fraction)` with carry=True and
+    `nit` with carry=False (a cold re-solve from the initial point).  carry=False is the default, as in the batch.
+    The drop is moved in place.  Returns `online_sweep`'s dictionary plus "iters", the iterations behind every point's factor.
+    timings: a list that receives per point {"create_s" (move and the new handle), "carry_s" (`carry_from`, which returns after the device's work), "iterate_s" (to the end of the
+    device's work), "epilogue_s" (factor and round), "evaluate_s", "step_s"}."""
+    _check_warm(warm_fraction)
+    if resolve_nit is not None and int(resolve_nit) < 1:
+        raise ValueError("resolve_nit must be >= 1, got %r" % (resolve_nit,))
+    n_p = int(resolve_nit) if resolve_nit is not None else warm_iterations(nit, warm_fraction) if carry else int(nit)
+    env, alg, solver, Z, gX = _setup(drop, int(nit), float(eta), int(seed), int(rank_radio), int(device), dtype)
+    prev = None  # the previous point's handle where it is this function's to close (the first solve's belongs to `alg`)
+    try:
+        K = drop.K
+        out = {"Z": Z, "z_vec": np.empty((n_points, K)), "remainder": np.empty(n_points, dtype=np.int64), "bler": np.empty((n_points, K)),
+               "iters": [int(nit)] + [n_p] * (n_points - 1)}
+        for p in range(n_points):
+            t0 = time.perf_counter()
+            env.move(drop.sta_locs)
+            if p == 0:
+                t1 = t2 = t3 = time.perf_counter()
+            else:
+                s = _lib.Solver.from_env(env, Z, n_p, eta, rank_radio=rank_radio, dtype=dtype)
+                try:
+                    t1 = time.perf_counter()
+                    if carry:
+                        s.carry_from(solver)
+                    t2 = time.perf_counter()
+                    key = probe_seed(seed, 0, 0xC0000 | p)
+                    s.iterate(n_p, None, seed=key)
+                    s.sync()
+                    t3 = time.perf_counter()
+                    rank, factor_seed = factor_rank_seed(K, Z, rank_radio, key)
+                    gX = s.factor(rank, seed=factor_seed, resident=True)
+                except BaseException:
+                    s.close()
+                    raise
+                if prev is not None:
+                    prev.close()
+                prev = solver = s
+            rng = np.random.default_rng(probe_seed(seed, 0, 0x80000 | p))
+            z_vec, rem = round_point(solver, env, Z, gX, nattempt, rng)
+            t4 = time.perf_counter()
+            _, bler = env.evaluate(z_vec, Z)
+            out["z_vec"][p], out["remainder"][p], out["bler"][p] = z_vec, rem, bler
+            t5 = time.perf_counter()
+            drop.step_time(float(step_us), mob_spd_meter_s, resolution_us)
+            if timings is not None:
+                timings.append({"create_s": t1 - t0, "carry_s": t2 - t1, "iterate_s": t3 - t2, "epilogue_s": t4 - t3, "evaluate_s": t5 - t4,
+                                "step_s": time.perf_counter() - t5})
+        return out
+    finally:
+        if prev is not None:
+            prev.close()
         alg.close()
         env.close()
 
