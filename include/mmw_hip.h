@@ -111,9 +111,11 @@ enum mmw_ifield {
     MMW_I_ASSO_Y = 7,
     MMW_I_DIAG_POS = 8,   /* [K] position of (k,k) in the L pattern */
     MMW_I_ASSO_POS = 9,   /* [E_asso] position of (x,y), x<y, in the L pattern */
-    MMW_I_PATTERN = 10    /* [2*K + 1 + 3*nnzL + E_asso] an instance's slice of the int32 arena as the batch kernels read it: indptr,
+    MMW_I_PATTERN = 10,   /* [2*K + 1 + 3*nnzL + E_asso] an instance's slice of the int32 arena as the batch kernels read it: indptr,
                              columns, rows, pair ids (-1: none), diagonal positions, pair positions; batches only, MMW_ERR_STATE on a
                              host-only one */
+    MMW_I_ROUND_LIST_BUILDS = 11 /* [1] solver handles: how often mmw_round_env / mmw_round_env_attempts built the handle's second list set
+                             (once per (environment, generation) they met in turn); 0 on a handle that never called them */
 };
 
 const char* mmw_last_error(void);
@@ -342,6 +344,34 @@ int mmw_env_bounds(mmw_env* e, int32_t out[2]);
 int mmw_env_move(mmw_env* e, const double* sta_xy);
 int mmw_round_env(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv,
                   int32_t* z_out, int32_t* rem_out);
+/*
+ * All attempts of one sdp_solver.rounding call (sim_src/alg/sdp_solver.py:18-25) in one chain of launches, with the directions drawn
+ * and the winner chosen on the device: what mmw_batch_round does for small instances, on the solver handle at any K.
+ *
+ * mmw_round_attempts: nattempt attempts of mmw_round (sdp_solver.rounding_one_attempt, sdp_solver.py:27-107) on the handle's own
+ * state.  The Zr x Dp directions of attempt a (sdp_solver.py:48-49) are Philox4x32-10 normals with counter (row, column pair, a,
+ * 0x524e4456) under the key (seed & 0xffffffff, seed >> 32), rows normalised: bitwise mmw_batch_round_randv's for the same
+ * (Zr, Dp, seed, a), whatever nattempt is.  The attempts run side by side; then the rule of sdp_solver.py:18-25 picks one on the
+ * device.  pick_rule 0, the reference's: the lowest attempt that leaves nobody over, else the last one -- exactly what the loop over
+ * single attempts that stops at the first feasible one returns.  pick_rule 1 (not the reference's): the attempt with the fewest users
+ * left over, ties to the lower attempt.  z_out[K]: the picked attempt's slots, -1 for a user left over (the caller draws those,
+ * sdp_solver.py:104-105); rem_out[nattempt]: every attempt's count of users left over; *pick_out: the picked attempt; z_all
+ * [nattempt*K], or NULL: every attempt's slots.  gX as for mmw_round (NULL: the resident factor or spectral block).  What crosses to
+ * the host is K + nattempt + 2 integers (and z_all when asked); gX crosses to the device only when the caller hands one.
+ * Refused before anything is allocated, copied or launched, MMW_ERR_ARG: Zr or Dp < 1, nattempt outside [1, 256], pick_rule outside
+ * {0, 1}, a null output, Zr > 4800 (mmw_round's bound); MMW_ERR_STATE: a device -1 handle, gX == NULL with no resident K x Dp factor.
+ *
+ * mmw_round_env_attempts: the same against the state `env` holds NOW (sim_script/journal_version/sim_mmw_online.py:60 calls
+ * rounding on the moved state), with mmw_round_env's cached second list set and its refusals (another K, another device).
+ *
+ * mmw_round_randv: the directions of ONE attempt by the same kernel, out[Zr*Dp] row-major (sdp_solver.py:48-49): the seam through
+ * which tests compare the draw with tests/helpers/philox_ref.py and with mmw_batch_round_randv.  attempt >= 0; n must be Zr*Dp.
+ */
+int mmw_round_attempts(mmw_solver* s, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule,
+                       int32_t* z_out, int32_t* rem_out, int32_t* pick_out, int32_t* z_all);
+int mmw_round_env_attempts(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule,
+                           int32_t* z_out, int32_t* rem_out, int32_t* pick_out, int32_t* z_all);
+int mmw_round_randv(mmw_solver* s, int32_t Zr, int32_t Dp, uint64_t seed, int32_t attempt, double* out, int64_t n);
 
 /*
  * A state that lives on the device as its seven CSR arrays, and the solver handle built from it there: the way in for a graph

@@ -34,6 +34,7 @@ BATCH_MAX_HEAD_PARTS = 64  # MMW_BATCH_MAX_HEAD_PARTS: head parts per instance a
 BATCH_EPILOGUE_MAX_K = 1024  # MMW_BATCH_EPILOGUE_MAX_K: the largest instance mmw_batch_factor / mmw_batch_round take
 KERNEL_CLASSES = ["spmm", "sddmm", "dual", "loss", "krylov_vec", "sketch", "project", "greedy", "factor"]
 I_L_INDPTR, I_L_INDICES, I_ST_INDPTR, I_ST_INDICES, I_GAIN_X, I_GAIN_Y, I_ASSO_X, I_ASSO_Y, I_DIAG_POS, I_ASSO_POS = range(10)
+I_ROUND_LIST_BUILDS = 11  # solver handles: how often the rounding's second list set was built [1]
 I_PATTERN = 10  # batches: the int32 arena of an instance [2 K + 1 + 3 nnzL + E_asso]: indptr, col, row, pair id, diag pos, pair pos
 
 EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "mmw_destroy", "mmw_sizes", "mmw_set_expm",
@@ -48,7 +49,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_factor_random", "mmw_batch_factor_spectral", "mmw_batch_set_split", "mmw_batch_set_factor_split", "mmw_batch_set_row_split",
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
-           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map"]
+           "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map",
+           "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv"]
 
 
 class MMWError(RuntimeError):
@@ -109,6 +111,9 @@ def lib():
     L.mmw_env_bounds.argtypes = [C.c_void_p, p_i32]
     L.mmw_env_move.argtypes = [C.c_void_p, p_f64]
     L.mmw_round_env.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_int32, p_f64, p_i32, p_i32]
+    L.mmw_round_attempts.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_int32, C.c_uint64, C.c_int, p_i32, p_i32, p_i32, p_i32]
+    L.mmw_round_env_attempts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_int32, C.c_uint64, C.c_int, p_i32, p_i32, p_i32, p_i32]
+    L.mmw_round_randv.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, p_f64, C.c_int64]
     L.mmw_gm_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
     L.mmw_gm_key.argtypes = [C.c_void_p, C.c_int, p_f64]
     for fn in (L.mmw_csr_upload, L.mmw_csr_wrap):  # (wrap's seven are device addresses: plain integers here)
@@ -479,13 +484,13 @@ class Solver(_Handle):
         self._keep_resident_factor()
         if resident:
             check(lib().mmw_factor(self._h, int(rank), None, C.c_uint64(int(seed))))
-            self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+            self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, int(rank)
             df = DeviceFactor(self, int(rank), self._factor_serial)
             self._resident = weakref.ref(df)
             return df
         out = np.empty((self.K, int(rank)), dtype=np.float64)
         check(lib().mmw_factor(self._h, int(rank), _pd(out), C.c_uint64(int(seed))))
-        self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+        self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, int(rank)
         return out
 
     def factor_spectral(self, Z, seed=0, resident=False, index_order=False):
@@ -498,13 +503,13 @@ class Solver(_Handle):
         Z, io = int(Z), 1 if index_order else 0
         if resident:
             check(lib().mmw_factor_spectral(self._h, Z, io, None, C.c_uint64(int(seed))))
-            self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+            self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, Z
             df = DeviceFactor(self, Z, self._factor_serial, index_ordered=bool(io))
             self._resident = weakref.ref(df)
             return df
         out = np.empty((self.K, max(Z, 0)), dtype=np.float64)  # (a Z out of range is the library's to refuse)
         check(lib().mmw_factor_spectral(self._h, Z, io, _pd(out), C.c_uint64(int(seed))))
-        self._factor_serial = getattr(self, "_factor_serial", 0) + 1
+        self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, Z
         return out
 
     def laplacian(self):
@@ -563,6 +568,61 @@ class Solver(_Handle):
         else:
             check(lib().mmw_round_env(self._h, env._h, *args))
         return z, rem
+
+    PICK_RULES = {"first": 0, "fewest": 1}
+
+    def round_attempts(self, Z, gX, nattempt, seed, pick="first", all_attempts=False):
+        """All `nattempt` attempts of one `sdp_solver.rounding` call (sdp_solver.py:18-25) in one device call (mmw_round_attempts):
+        attempt a rounds with the Z x D' directions drawn on the device from Philox keyed by (seed, a) -- `round_randv(Z, D', seed,
+        a)`, whatever nattempt is -- and the device picks one.  pick="first", the reference's rule: the lowest attempt that leaves
+        nobody over, else the last, i.e. what the loop over single attempts with stop-at-first returns; "fewest" (not the
+        reference's): the attempt with the fewest users left over, ties to the lower attempt.  gX: an array, a resident
+        `DeviceFactor` of this handle, or None for the factor the handle computed last (read where it lies; D' is its rank).
+        Returns (z int32[K] with -1 = left over, rem int32[nattempt], pick), plus z_all int32[nattempt, K] with all_attempts=True."""
+        return self._round_attempts(None, Z, gX, nattempt, seed, pick, all_attempts)
+
+    def round_env_attempts(self, env, Z, gX, nattempt, seed, pick="first", all_attempts=False):
+        """`round_attempts` against the state the DeviceEnv `env` holds now (mmw_round_env_attempts), with `round_env`'s list cache."""
+        return self._round_attempts(env, Z, gX, nattempt, seed, pick, all_attempts)
+
+    def _round_attempts(self, env, Z, gX, nattempt, seed, pick, all_attempts):
+        if pick not in self.PICK_RULES:
+            raise MMWError("round_attempts: pick must be 'first' or 'fewest', got %r" % (pick,))
+        on_device = gX is None or (isinstance(gX, DeviceFactor) and gX.on_device_of(self))
+        if gX is None:  # the factor this handle computed last, of the rank it was asked for (none yet: the library refuses)
+            Dp = getattr(self, "_last_rank", 1)
+        else:
+            if not on_device:
+                gX = _f64(gX)
+            if len(gX.shape) != 2 or gX.shape[0] != self.K:
+                raise MMWError("round_attempts: gX must be (K, D')")
+            Dp = int(gX.shape[1])
+        nattempt = int(nattempt)
+        z = np.empty(self.K, dtype=np.int32)
+        rem = np.empty(max(nattempt, 1), dtype=np.int32)
+        z_all = np.empty((max(nattempt, 1), self.K), dtype=np.int32) if all_attempts else None
+        picked = C.c_int32(-1)
+        args = (int(Z), Dp, None if on_device else _pd(gX), nattempt, C.c_uint64(int(seed)), self.PICK_RULES[pick], _pi(z), _pi(rem), C.byref(picked),
+                _opt_pi(z_all))
+        if env is None:
+            check(lib().mmw_round_attempts(self._h, *args))
+        else:
+            check(lib().mmw_round_env_attempts(self._h, env._h, *args))
+        return (z, rem, int(picked.value)) + ((z_all,) if all_attempts else ())
+
+    def round_list_builds(self):
+        """How often `round_env` / `round_env_attempts` built this handle's second list set (MMW_I_ROUND_LIST_BUILDS): once per
+        (environment, generation) they met in turn."""
+        out = np.empty(1, dtype=np.int32)
+        check(lib().mmw_read_i32(self._h, I_ROUND_LIST_BUILDS, _pi(out), 1))
+        return int(out[0])
+
+    def round_randv(self, Z, Dp, seed, attempt):
+        """The Z x D' row-normalised directions attempt `attempt` of a `round_attempts(..., seed)` call rounds with (mmw_round_randv):
+        the same kernel run for that one attempt, float64."""
+        out = np.empty((max(int(Z), 0), max(int(Dp), 0)), dtype=np.float64)
+        check(lib().mmw_round_randv(self._h, int(Z), int(Dp), C.c_uint64(int(seed)), int(attempt), _pd(out), int(out.size)))
+        return out
 
 
 class BatchSolver(_Handle):

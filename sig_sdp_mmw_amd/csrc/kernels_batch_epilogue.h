@@ -26,6 +26,7 @@
 #include "../../include/mmw_hip.h"
 #include "kernels_batch.h"
 #include "kernels_batch_spectral.h"
+#include "kernels_round_draw.h"
 
 namespace mmw {
 
@@ -243,33 +244,11 @@ struct RoundDesc {
     int64_t r_order, r_pref, r_z, r_rem;                 // int32 round work: K, K x Z, nattempt x K, nattempt + 1 (the last: attempts run)
 };
 
-// randv of (seed, attempt): Philox normals, one wave per row, lane l draws the column pairs l + 64 i; the squared norm in that order
-// and the fixed-order wave reduction; every lane scales what it drew (sdp_solver.py:48-49)
+// randv of (seed, attempt): Philox normals, one wave per row after the other; the row itself is randv_row's (kernels_round_draw.h), the
+// one statement of the draw, which the handle's k_round_randv calls too (sdp_solver.py:48-49)
 __device__ __forceinline__ void epi_randv_rows(int Z, int Dp, uint64_t seed, uint32_t attempt, double* R) {
     const int lane = (int)threadIdx.x & 63, wib = (int)threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
-    const int ngroups = (Dp + 1) >> 1;
-    for (int row = wib; row < Z; row += nw) {
-        double* r = R + (size_t)row * Dp;
-        double ssl = 0.0;
-        for (int p = lane; p < ngroups; p += WAVE) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)row, (uint32_t)p, attempt, 0x524e4456u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-            double n0, n1;
-            box_muller(w, n0, n1);
-            ssl += n0 * n0;
-            r[2 * p] = n0;
-            if (2 * p + 1 < Dp) {
-                ssl += n1 * n1;
-                r[2 * p + 1] = n1;
-            }
-        }
-        const double ss = wave_sum(ssl);
-        const double inv = ss > 0.0 ? 1.0 / sqrt(ss) : 0.0;
-        for (int p = lane; p < ngroups; p += WAVE) {
-            r[2 * p] *= inv;
-            if (2 * p + 1 < Dp) r[2 * p + 1] *= inv;
-        }
-    }
+    for (int row = wib; row < Z; row += nw) randv_row(row, Dp, seed, attempt, lane, R + (size_t)row * Dp);
 }
 __global__ __launch_bounds__(BATCH_THREADS) void k_batch_randv(int Z, int Dp, uint64_t seed, uint32_t attempt, double* __restrict__ R) {
     epi_randv_rows(Z, Dp, seed, attempt, R);

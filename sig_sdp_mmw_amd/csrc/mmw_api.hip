@@ -200,6 +200,18 @@ int mmw_env_move(mmw_env* e, const double* sta_xy) { return entry("mmw_env_move"
 int mmw_round_env(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) {
     return entry("mmw_round_env", !s, "null solver handle", [&] { return s->round_env(e, Zr, Dp, gX, nbatch, randv, z_out, rem_out); });
 }
+// ---- all attempts of one rounding() call drawn, run and chosen among on the device (solver_extras.h, kernels_round_draw.h)
+int mmw_round_attempts(mmw_solver* s, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out, int32_t* rem_out,
+                       int32_t* pick_out, int32_t* z_all) {
+    return entry("mmw_round_attempts", !s, "null solver handle", [&] { return s->round_attempts(nullptr, false, Zr, Dp, gX, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all); });
+}
+int mmw_round_env_attempts(mmw_solver* s, mmw_env* e, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out,
+                           int32_t* rem_out, int32_t* pick_out, int32_t* z_all) {
+    return entry("mmw_round_env_attempts", !s, "null solver handle", [&] { return s->round_attempts(e, true, Zr, Dp, gX, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all); });
+}
+int mmw_round_randv(mmw_solver* s, int32_t Zr, int32_t Dp, uint64_t seed, int32_t attempt, double* out, int64_t n) {
+    return entry("mmw_round_randv", !s, "null solver handle", [&] { return s->round_randv(Zr, Dp, seed, attempt, out, n); });
+}
 int mmw_gm_create(mmw_gm** out, int device, int32_t K, const int32_t* S_indptr, const int32_t* S_indices, const double* S_data,
                   const int32_t* Q_indptr, const int32_t* Q_indices, const double* Q_data, const double* h_max) {
     return guarded("mmw_gm_create", [&]() -> int {

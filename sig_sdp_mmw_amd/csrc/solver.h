@@ -44,6 +44,9 @@ struct mmw_solver {
                       int32_t* rem_out) = 0;
     virtual int round_env(mmw_env* env, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
                           int32_t* rem_out) = 0;
+    virtual int round_attempts(mmw_env* env, bool with_env, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule,
+                               int32_t* z_out, int32_t* rem_out, int32_t* pick_out, int32_t* z_all) = 0;
+    virtual int round_randv(int32_t Zr, int32_t Dp, uint64_t seed, int32_t attempt, double* out, int64_t n) = 0;
 };
 namespace {
 // the two refusals of a handle made with device -1
@@ -317,6 +320,11 @@ template <typename T> struct Solver final : mmw_solver {
         return reads.read_f64(core, loop, emax, extras, which, out, n);
     }
     int read_i32(int which, int32_t* out, int64_t n) override {
+        if (which == MMW_I_ROUND_LIST_BUILDS) {  // a counter, not a list: nothing is fetched for it
+            if (n != 1) return fail(MMW_ERR_ARG, "mmw_read_i32(ROUND_LIST_BUILDS): wrong length");
+            out[0] = extras.env_builds;
+            return MMW_OK;
+        }
         MMW_TRY(envl.ensure_host(core));
         const std::vector<int32_t>* v = host_list_i32(core.H, which);
         return v ? export_vec(*v, out, n, "mmw_read_i32") : fail(MMW_ERR_ARG, "mmw_read_i32: unknown field");
@@ -365,6 +373,35 @@ template <typename T> struct Solver final : mmw_solver {
             return fail(MMW_ERR_ARG, "mmw_round_env: the environment lies on device " + std::to_string(E.device) + ", the handle on device " + std::to_string(core.device));
         MMW_HIP(hipSetDevice(core.device));
         return extras.round_env(E.list_source(), Zr, Dp, gX, nbatch, randv, z_out, rem_out);
+    }
+    // mmw_round_attempts (with_env = false) and mmw_round_env_attempts: all attempts of one rounding() call, drawn and chosen among on the
+    // device (solver_extras.h, round_attempts_on).  The refusals come first, those that read the arguments only before the handle's own.
+    int round_attempts(mmw_env* env, bool with_env, int32_t Zr, int32_t Dp, const double* gX, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out,
+                       int32_t* rem_out, int32_t* pick_out, int32_t* z_all) override {
+        const std::string who = with_env ? "mmw_round_env_attempts" : "mmw_round_attempts";
+        MMW_TRY(Extras<T>::attempts_check(who, Zr, Dp, nattempt, pick_rule, z_out, rem_out, pick_out));
+        if (core.K > ROUND_PICK_MAX_K) return fail(MMW_ERR_ARG, who + ": K = " + std::to_string(core.K) + " exceeds " + std::to_string(ROUND_PICK_MAX_K) + ", the most users the pick's key holds");
+        if (core.host_only) return host_only_handle();
+        if (!with_env) {
+            MMW_HIP(hipSetDevice(core.device));
+            return extras.round_attempts(Zr, Dp, gX, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all);
+        }
+        if (!env) return fail(MMW_ERR_ARG, who + ": null environment");
+        const EnvDevice& E = env->e;
+        if (E.K != core.K)
+            return fail(MMW_ERR_ARG, who + ": the environment has K = " + std::to_string(E.K) + " stations, the handle K = " + std::to_string(core.K));
+        if (E.device != core.device)
+            return fail(MMW_ERR_ARG, who + ": the environment lies on device " + std::to_string(E.device) + ", the handle on device " + std::to_string(core.device));
+        MMW_HIP(hipSetDevice(core.device));
+        return extras.round_env_attempts(E.list_source(), Zr, Dp, gX, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all);
+    }
+    int round_randv(int32_t Zr, int32_t Dp, uint64_t seed, int32_t attempt, double* out, int64_t n) override {
+        if (Zr < 1 || Dp < 1) return fail(MMW_ERR_ARG, "mmw_round_randv: Z and D' must be positive");
+        if (attempt < 0) return fail(MMW_ERR_ARG, "mmw_round_randv: attempt must be >= 0");
+        if (!out || n != (int64_t)Zr * Dp) return fail(MMW_ERR_ARG, "mmw_round_randv: out must hold Z x D' values");
+        if (core.host_only) return host_only_handle();
+        MMW_HIP(hipSetDevice(core.device));
+        return extras.round_randv(Zr, Dp, seed, attempt, out);
     }
 };
 template <typename T>

@@ -2,6 +2,7 @@
 #pragma once
 #include "factor.h"
 #include "kernels_round.h"
+#include "kernels_round_draw.h"
 #include "pattern.h"
 #include "pattern_device.h"
 #include "runtime.h"
@@ -256,22 +257,29 @@ template <typename T> struct Extras {
     // moved, build it once.  The handle's own lists, its iterate and its factor are not touched.
     RoundListSet env_lists;
     uint64_t env_uid = 0, env_gen = 0;  // uid 0: nothing cached
-    int round_env(const EnvListSource& E, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
-        MMW_TRY(round_check("mmw_round_env", Z, Dp, gX_h, nb, randv_h, z_out, rem_out));
+    int32_t env_builds = 0;             // how often the set was built (MMW_I_ROUND_LIST_BUILDS)
+    // the one statement of the cache rule: the view of `E`'s state, built when (uid, gen) is not the cached one
+    int env_view(const EnvListSource& E, RoundView& view) {
         if (env_uid != E.uid || env_gen != E.gen) {
             env_uid = 0;
             MMW_TRY(env_lists.build(st, E));
             env_uid = E.uid; env_gen = E.gen;
+            ++env_builds;
         }
         const RoundListSet& L = env_lists;
-        const RoundView view{L.so_indptr.p, L.so_indices.p, L.q_indptr.p, L.q_indices.p, L.so_data.p, L.so_hmax.p, L.h_max.p};
+        view = RoundView{L.so_indptr.p, L.so_indices.p, L.q_indptr.p, L.q_indices.p, L.so_data.p, L.so_hmax.p, L.h_max.p};
+        return MMW_OK;
+    }
+    int round_env(const EnvListSource& E, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
+        MMW_TRY(round_check("mmw_round_env", Z, Dp, gX_h, nb, randv_h, z_out, rem_out));
+        RoundView view;
+        MMW_TRY(env_view(E, view));
         return round_on(view, Z, Dp, gX_h, nb, randv_h, z_out, rem_out);
     }
-    int round_on(const RoundView& V, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
-        const size_t baseb = (size_t)GB_WAVES * Z * 4;
+    // the device buffers one call of nb attempts reads and writes
+    int round_buffers(int32_t Z, int32_t Dp, bool own_gX, int32_t nb) {
         const size_t nP = (size_t)nb * K * Z;
-        if (gX_h) MMW_TRY(ensure(gX, (size_t)K * Dp));
-        const double* gX_d = gX_h ? gX.p : fac.out64.p;
+        if (own_gX) MMW_TRY(ensure(gX, (size_t)K * Dp));
         MMW_TRY(ensure(randv, (size_t)nb * Z * Dp));
         MMW_TRY(ensure(P, nP));
         MMW_TRY(ensure(pref, nP));
@@ -281,6 +289,11 @@ template <typename T> struct Extras {
         MMW_TRY(ensure(order, K));
         MMW_TRY(ensure(rank_part, (size_t)RANK_SPLIT * K));
         MMW_TRY(ensure(rem, nb));
+        return MMW_OK;
+    }
+    int round_on(const RoundView& V, int32_t Z, int32_t Dp, const double* gX_h, int32_t nb, const double* randv_h, int32_t* z_out, int32_t* rem_out) {
+        MMW_TRY(round_buffers(Z, Dp, gX_h != nullptr, nb));
+        const double* gX_d = gX_h ? gX.p : fac.out64.p;
         // inputs and outputs cross through the handle's page-locked staging buffer (runtime.h, PinnedBuf)
         const size_t b_gx = gX_h ? (size_t)K * Dp * sizeof(double) : 0, b_rv = (size_t)nb * Z * Dp * sizeof(double);
         const size_t b_z = (((size_t)nb * K * sizeof(int)) + 7) & ~(size_t)7, b_rem = (size_t)nb * sizeof(int);
@@ -290,6 +303,19 @@ template <typename T> struct Extras {
         memcpy(sp + b_gx, randv_h, b_rv);
         if (gX_h) MMW_HIP(hipMemcpyAsync(gX.p, sp, b_gx, hipMemcpyHostToDevice, st));
         MMW_HIP(hipMemcpyAsync(randv.p, sp + b_gx, b_rv, hipMemcpyHostToDevice, st));
+        MMW_TRY(round_chain(V, Z, Dp, gX_d, nb));
+        MMW_HIP(hipMemcpyAsync(sp + b_gx + b_rv, slot.p, (size_t)nb * K * sizeof(int), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipMemcpyAsync(sp + b_gx + b_rv + b_z, rem.p, b_rem, hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        memcpy(z_out, sp + b_gx + b_rv, (size_t)nb * K * sizeof(int));
+        memcpy(rem_out, sp + b_gx + b_rv + b_z, b_rem);
+        return MMW_OK;
+    }
+    // from "gX_d and randv[nb][Z][D'] are on the device" to "slot[nb][K] and rem[nb] are on the device": the chain mmw_round and
+    // mmw_round_attempts share (round_buffers has sized what it touches)
+    int round_chain(const RoundView& V, int32_t Z, int32_t Dp, const double* gX_d, int32_t nb) {
+        const size_t baseb = (size_t)GB_WAVES * Z * 4;
+        const size_t nP = (size_t)nb * K * Z;
         MMW_HIP(hipMemsetAsync(gain.p, 0, nP * sizeof(double), st));
         MMW_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)nb * K * sizeof(int), st));
         if (kt) MMW_TRY(kt->begin(KT_PROJECT));
@@ -334,12 +360,88 @@ template <typename T> struct Extras {
         }
         if (kt) MMW_TRY(kt->end());
         MMW_HIP(hipGetLastError());
-        MMW_HIP(hipMemcpyAsync(sp + b_gx + b_rv, slot.p, (size_t)nb * K * sizeof(int), hipMemcpyDeviceToHost, st));
-        MMW_HIP(hipMemcpyAsync(sp + b_gx + b_rv + b_z, rem.p, b_rem, hipMemcpyDeviceToHost, st));
-        MMW_HIP(hipStreamSynchronize(st));
-        memcpy(z_out, sp + b_gx + b_rv, (size_t)nb * K * sizeof(int));
-        memcpy(rem_out, sp + b_gx + b_rv + b_z, b_rem);
         return MMW_OK;
+    }
+
+    // ---- mmw_round_attempts / mmw_round_env_attempts / mmw_round_randv: the attempts of one rounding() call (sdp_solver.py:18-25) drawn,
+    // run and chosen among on the device (kernels_round_draw.h).  Attempt a's directions depend on (seed, a) alone, so the call returns
+    // what the loop over single attempts with stop-at-first returns, however many attempts it ran side by side.
+    DevBuf<int> win, pick_info;  // the winner's K slots; {pick, rem[pick]}
+    // the refusals that read arguments only (`who`: the entry), before the handle is looked at
+    static int attempts_check(const std::string& who, int32_t Z, int32_t Dp, int32_t nattempt, int pick_rule, const int32_t* z_out, const int32_t* rem_out,
+                              const int32_t* pick_out) {
+        if (Z < 1 || Dp < 1) return fail(MMW_ERR_ARG, who + ": Z and D' must be positive");
+        if (nattempt < 1 || nattempt > ROUND_MAX_ATTEMPTS)
+            return fail(MMW_ERR_ARG, who + ": nattempt = " + std::to_string(nattempt) + " must be in [1, " + std::to_string(ROUND_MAX_ATTEMPTS) + "]");
+        if (pick_rule != 0 && pick_rule != 1) return fail(MMW_ERR_ARG, who + ": pick_rule must be 0 (the first feasible attempt, else the last) or 1 (the fewest users left over)");
+        if (!z_out || !rem_out || !pick_out) return fail(MMW_ERR_ARG, who + ": null pointer");
+        if ((size_t)GB_WAVES * Z * 4 > 150 * 1024) return fail(MMW_ERR_ARG, who + ": 32 Z bytes exceed the greedy kernel's LDS");
+        return MMW_OK;
+    }
+    int attempts_factor_check(const std::string& who, int32_t Dp, const double* gX_h) const {
+        if (!gX_h && ((size_t)K * Dp != fac.last_n || Dp != fac.last_rank || fac.last_n == 0))
+            return fail(MMW_ERR_STATE, who + ": gX is null and the handle holds no factor of K x D'");
+        return MMW_OK;
+    }
+    int round_attempts(int32_t Z, int32_t Dp, const double* gX_h, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out, int32_t* rem_out,
+                       int32_t* pick_out, int32_t* z_all) {
+        MMW_TRY(attempts_factor_check("mmw_round_attempts", Dp, gX_h));
+        const RoundView own{so_indptr.p, so_indices.p, q_indptr.p, q_indices.p, so_data.p, so_hmax.p, h_max.p};
+        return round_attempts_on(own, Z, Dp, gX_h, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all);
+    }
+    int round_env_attempts(const EnvListSource& E, int32_t Z, int32_t Dp, const double* gX_h, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out,
+                           int32_t* rem_out, int32_t* pick_out, int32_t* z_all) {
+        MMW_TRY(attempts_factor_check("mmw_round_env_attempts", Dp, gX_h));
+        RoundView view;
+        MMW_TRY(env_view(E, view));
+        return round_attempts_on(view, Z, Dp, gX_h, nattempt, seed, pick_rule, z_out, rem_out, pick_out, z_all);
+    }
+    void launch_randv(int32_t Z, int32_t Dp, int32_t nattempt, uint64_t seed, uint32_t attempt0) {
+        const size_t waves = (size_t)nattempt * Z;
+        hipLaunchKernelGGL(k_round_randv, dim3((unsigned)((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)), dim3(BLOCK), 0, st, Z, Dp, nattempt, seed, attempt0,
+                           randv.p);
+    }
+    int round_attempts_on(const RoundView& V, int32_t Z, int32_t Dp, const double* gX_h, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out,
+                          int32_t* rem_out, int32_t* pick_out, int32_t* z_all) {
+        MMW_TRY(round_buffers(Z, Dp, gX_h != nullptr, nattempt));
+        MMW_TRY(ensure(win, (size_t)K));
+        MMW_TRY(ensure(pick_info, 2));
+        const double* gX_d = gX_h ? gX.p : fac.out64.p;
+        // in: gX when the caller hands one.  out: the winner's K slots, {pick, rem[pick]}, the nattempt counts (and all slots when asked)
+        const size_t b_gx = gX_h ? (size_t)K * Dp * sizeof(double) : 0;
+        const size_t b_win = (size_t)K * sizeof(int), b_info = 2 * sizeof(int), b_rem = (size_t)nattempt * sizeof(int);
+        const size_t b_all = z_all ? (size_t)nattempt * K * sizeof(int) : 0;
+        MMW_TRY(stage.ensure(b_gx + b_win + b_info + b_rem + b_all));
+        char* sp = static_cast<char*>(stage.p);
+        if (gX_h) {
+            memcpy(sp, gX_h, b_gx);
+            MMW_HIP(hipMemcpyAsync(gX.p, sp, b_gx, hipMemcpyHostToDevice, st));
+        }
+        launch_randv(Z, Dp, nattempt, seed, 0u);
+        MMW_TRY(round_chain(V, Z, Dp, gX_d, nattempt));
+        hipLaunchKernelGGL(k_round_pick, dim3((unsigned)((K + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, nattempt, pick_rule, (const int*)rem.p, (const int*)slot.p,
+                           win.p, pick_info.p);
+        MMW_HIP(hipGetLastError());
+        char* so = sp + b_gx;
+        MMW_HIP(hipMemcpyAsync(so, win.p, b_win, hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipMemcpyAsync(so + b_win, pick_info.p, b_info, hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipMemcpyAsync(so + b_win + b_info, rem.p, b_rem, hipMemcpyDeviceToHost, st));
+        if (z_all) MMW_HIP(hipMemcpyAsync(so + b_win + b_info + b_rem, slot.p, b_all, hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        memcpy(z_out, so, b_win);
+        int info[2];
+        memcpy(info, so + b_win, b_info);
+        *pick_out = info[0];
+        memcpy(rem_out, so + b_win + b_info, b_rem);
+        if (z_all) memcpy(z_all, so + b_win + b_info + b_rem, b_all);
+        return MMW_OK;
+    }
+    // the seam for the tests: the directions of ONE attempt by the same kernel, copied out
+    int round_randv(int32_t Z, int32_t Dp, uint64_t seed, int32_t attempt, double* out) {
+        MMW_TRY(ensure(randv, (size_t)Z * Dp));
+        launch_randv(Z, Dp, 1, seed, (uint32_t)attempt);
+        MMW_HIP(hipGetLastError());
+        return copy_d2h(out, randv.p, (size_t)Z * Dp * sizeof(double), st);
     }
 };
 

@@ -24,6 +24,11 @@ defaults from the environment, so that a harness script that constructs `mmw(nit
   warm_start  False (default, the reference's behaviour: every run restarts from Y = 1/C, X = I, mmw.py:62-68) or True:
           a run on the state of the previous run continues from that run's (e_accu, L_accu, X, Y) and averages
           `warm_fraction * nit` iterations only -- the probes of one binary search solve neighbouring problems.  [$MMW_WARM_START]
+  round_draws  "host" (default: `rounding` draws its directions from the global NumPy stream, as above) or "device": `rounding` is
+          ONE `Solver.round_attempts` call -- all attempts' directions drawn on the device, the first feasible attempt chosen there
+          (sdp_solver.py:18-25) -- keyed `batch.probe_seed(seed, 0, 0x20000 | (n & 0x1FFFF))` for this object's n-th rounding
+          (n = 0, 1, ...: `sdp_solver.round_key`); the users left over come from `np.random.default_rng(key)`, so the rounding
+          does not touch the global NumPy stream.  No environment switch.
 """
 import math
 import os
@@ -46,7 +51,8 @@ def factor_rank_seed(K, Z, rank_radio, run_seed):
 
 class mmw(STATS_OBJECT, sdp_solver):
     def __init__(self, nit=100, rank_radio=2, alpha=1., eta=0.1, log_gap=False, *, dtype=None, rng=None,
-                 expm="lanczos", expm_tol=None, expm_max_order=12, device=None, seed=0, warm_start=None, warm_fraction=1.0 / 3.0):
+                 expm="lanczos", expm_tol=None, expm_max_order=12, device=None, seed=0, warm_start=None, warm_fraction=1.0 / 3.0,
+                 round_draws="host"):
         sdp_solver.__init__(self, nit=nit, rank_radio=rank_radio, alpha=alpha)
         self.eta = eta
         self.LOG_GAP = log_gap
@@ -69,13 +75,17 @@ class mmw(STATS_OBJECT, sdp_solver):
         self.round_batch = rng == "device"  # the fast path batches the rounding attempts too
         self.warm_start = bool(warm_start)
         self.warm_fraction = float(warm_fraction)
+        if round_draws not in ("host", "device"):
+            raise ValueError("round_draws in {host,device}")
+        self.round_draws = round_draws
+        self._round_calls = 0
 
     def sibling(self):
         """A second solver with the same settings and its own device handle, stream and sketch seeds (binary_search's opt-in
         speculative mode keeps one probe in flight on each)."""
         other = mmw(nit=self.nit, rank_radio=self.rank_radio, alpha=self.alpha, eta=self.eta, log_gap=self.LOG_GAP, dtype=self.dtype, rng=self.rng,
                     expm=self.expm, expm_tol=self.expm_tol, expm_max_order=self.expm_max_order, device=self._device_index, seed=self.seed + 7919,
-                    warm_start=self.warm_start, warm_fraction=self.warm_fraction)
+                    warm_start=self.warm_start, warm_fraction=self.warm_fraction, round_draws=self.round_draws)
         other.round_batch = self.round_batch
         return other
 

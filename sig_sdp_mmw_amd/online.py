@@ -6,7 +6,10 @@ moves (`mmw_env_move`), the solver handle's resident factor rounded against the 
 (`mmw_round_env`), the device scorer, and for the greedy arm a `GreedyHandle.from_env`.  The state never crosses to the host.
 `online_resolve_sweep` is `batch.online_resolve_many` on the same side: a re-solve at every time point on a handle built on the
 device from the moved environment, optionally continuing from the previous point's iterate (`Solver.carry_from`, `mmw_carry`).
+Opt-in (`online_sweep(draws="device")`, `online_resolve_sweep_device`): the attempts of a point's rounding as ONE device call,
+`round_point_device` -- directions drawn on the device per (key, attempt), the winner picked there (`mmw_round_env_attempts`).
 """
+import contextvars
 import time
 
 import numpy as np
@@ -66,8 +69,44 @@ def round_point(solver, env, Z, gX, nattempt, rng):
     return z_vec, int(un.sum())
 
 
+def round_point_device(solver, env, Z, gX, nattempt, key, pick="first"):
+    """`round_point` with the draws, the attempts and the choice among them on the device: ONE `Solver.round_env_attempts` call with
+    seed = `key`.  Attempt a rounds with `solver.round_randv(Z, D', key, a)` (Philox keyed by (key, a): the directions of an
+    attempt do not depend on how many attempts run), so with pick="first" the call returns what the sequential loop over those
+    attempts with stop-at-first returns: the first attempt that leaves nobody over, else the last.  pick="fewest" (not the
+    reference's rule): the attempt with the fewest users left over.  The users the winner left over are drawn from
+    `np.random.default_rng(key).integers(0, Z, n)`, the batch's convention (`batch._finish`).  gX: an array, a `DeviceFactor`
+    or None (the handle's resident factor).  Returns (z_vec float64[K], remainder)."""
+    z, _, _ = solver.round_env_attempts(env, Z, gX, max(1, int(nattempt)), key, pick=pick)
+    un = z < 0
+    z_vec = z.astype(np.float64)
+    if np.any(un):
+        z_vec[un] = np.random.default_rng(key).integers(0, Z, int(un.sum()))
+    return z_vec, int(un.sum())
+
+
+def _check_draws(draws, pick):
+    if draws not in ("host", "device"):
+        raise ValueError("draws must be 'host' or 'device', got %r" % (draws,))
+    if pick not in _lib.Solver.PICK_RULES:
+        raise ValueError("pick must be 'first' or 'fewest', got %r" % (pick,))
+    if draws == "host" and pick != "first":
+        raise ValueError("pick=%r needs draws='device': the host loop stops at the first feasible attempt" % (pick,))
+
+
+# (draws, pick) of `online_resolve_sweep`'s roundings: ("host", "first") unless `online_resolve_sweep_device` is the caller
+_RESOLVE_ROUTE = contextvars.ContextVar("online_resolve_route", default=("host", "first"))
+
+
+def _round_at(draws, pick, solver, env, Z, gX, nattempt, key):
+    """One point's rounding by either route; `key` = probe_seed(seed, 0, 0x80000 | p) seeds the host generator or is the device key."""
+    if draws == "device":
+        return round_point_device(solver, env, Z, gX, nattempt, key, pick)
+    return round_point(solver, env, Z, gX, nattempt, np.random.default_rng(key))
+
+
 def online_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2,
-                 device=0, dtype=_lib.F32, timings=None):
+                 device=0, dtype=_lib.F32, timings=None, draws="host", pick="first"):
     """sim_script/journal_version/sim_mmw_online.py:34-78 for one `graphs.mobile_drop` of any K, as `batch.online_many` runs it for
     many small ones.  Setup: a `DeviceEnv` at the drop's positions, `binary_search_relaxation` on `env.device_state()` with `mmw`
     (device sketches, cold probes: the reference's search), one more solve at the Z it ends at, the factor resident.  Then per
@@ -78,8 +117,15 @@ def online_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
     Randomness: point p draws everything from ONE generator, `np.random.default_rng(batch.probe_seed(seed, 0, 0x80000 | p))`: first
     the projection vectors of its attempts, attempt by attempt as each comes to run, then the slots of the users the chosen attempt
     left over (`round_point`).  The global NumPy stream is used by the search (the roundings of its probes) and not after it.
+    draws="device" (opt-in; "host" is the above): point p is ONE device call, `round_point_device` with the key
+    probe_seed(seed, 0, 0x80000 | p) -- the same number that seeds the host generator above.  Attempt a of the point rounds with the
+    directions the device draws from (key, a); `pick` chooses among the attempts ("first": the sequential rule above, to the integer
+    what the loop over those attempts returns; "fewest": the attempt with the fewest users left over, not the reference's); the
+    users the chosen attempt left over are drawn from `np.random.default_rng(key).integers(0, Z, n)`.  The colourings differ from
+    draws="host" because the directions do.  pick="fewest" needs draws="device".
     Returns {"Z", "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]}.  timings: a list that receives one
     {"device_s" (move + round + evaluate), "step_s" (the host's walk)} per point."""
+    _check_draws(draws, pick)
     env, alg, solver, Z, gX = _setup(drop, int(nit), float(eta), int(seed), int(rank_radio), int(device), dtype)
     try:
         K = drop.K
@@ -87,8 +133,7 @@ def online_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution
         for p in range(n_points):
             t0 = time.perf_counter()
             env.move(drop.sta_locs)
-            rng = np.random.default_rng(probe_seed(seed, 0, 0x80000 | p))
-            z_vec, rem = round_point(solver, env, Z, gX, nattempt, rng)
+            z_vec, rem = _round_at(draws, pick, solver, env, Z, gX, nattempt, probe_seed(seed, 0, 0x80000 | p))
             _, bler = env.evaluate(z_vec, Z)
             out["z_vec"][p], out["remainder"][p], out["bler"][p] = z_vec, rem, bler
             t1 = time.perf_counter()
@@ -113,10 +158,14 @@ def online_resolve_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
     probe_seed(seed, 0, 0x80000 | p), `env.evaluate`; the previous handle is closed and the drop walks `step_us` microseconds.
     Iterations per re-solve n_p: `resolve_nit`, or when that is None `batch.warm_iterations(nit, warm_fraction)` with carry=True and
     `nit` with carry=False (a cold re-solve from the initial point).  carry=False is the default, as in the batch.
+    The host draws the rounding's directions here, as `online_sweep(draws="host")`; `online_resolve_sweep_device` is this sweep
+    with draws="device": the point's rounding is one `round_point_device` call with the key probe_seed(seed, 0, 0x80000 | p)
+    instead of `round_point` with the generator seeded by it.
     The drop is moved in place.  Returns `online_sweep`'s dictionary plus "iters", the iterations behind every point's factor.
     timings: a list that receives per point {"create_s" (move and the new handle), "carry_s" (`carry_from`, which returns after the device's work), "iterate_s" (to the end of the
     device's work), "epilogue_s" (factor and round), "evaluate_s", "step_s"}."""
     _check_warm(warm_fraction)
+    draws, pick = _RESOLVE_ROUTE.get()
     if resolve_nit is not None and int(resolve_nit) < 1:
         raise ValueError("resolve_nit must be >= 1, got %r" % (resolve_nit,))
     n_p = int(resolve_nit) if resolve_nit is not None else warm_iterations(nit, warm_fraction) if carry else int(nit)
@@ -150,8 +199,7 @@ def online_resolve_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
                 if prev is not None:
                     prev.close()
                 prev = solver = s
-            rng = np.random.default_rng(probe_seed(seed, 0, 0x80000 | p))
-            z_vec, rem = round_point(solver, env, Z, gX, nattempt, rng)
+            z_vec, rem = _round_at(draws, pick, solver, env, Z, gX, nattempt, probe_seed(seed, 0, 0x80000 | p))
             t4 = time.perf_counter()
             _, bler = env.evaluate(z_vec, Z)
             out["z_vec"][p], out["remainder"][p], out["bler"][p] = z_vec, rem, bler
@@ -166,6 +214,23 @@ def online_resolve_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
             prev.close()
         alg.close()
         env.close()
+
+
+def online_resolve_sweep_device(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e5, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2,
+                                device=0, dtype=_lib.F32, resolve_nit=None, carry=False, warm_fraction=1.0 / 3.0, timings=None, pick="first"):
+    """`online_resolve_sweep` with draws="device" (see `online_sweep`): every point's rounding is ONE device call,
+    `round_point_device` with the key probe_seed(seed, 0, 0x80000 | p) -- the number that seeds the host generator of
+    `online_resolve_sweep` -- and `pick` ("first": the sequential rule; "fewest": the fewest users left over) chooses among the
+    attempts.  Everything else -- the setup, the re-solves and their keys probe_seed(seed, 0, 0xC0000 | p), the result, the timings
+    -- is `online_resolve_sweep`'s, which runs with the route set for this call (a context variable: other threads and tasks keep
+    theirs) and whose own arguments stay as they are."""
+    _check_draws("device", pick)
+    token = _RESOLVE_ROUTE.set(("device", pick))
+    try:
+        return online_resolve_sweep(drop, n_points, step_us, mob_spd_meter_s, resolution_us, nit, eta, seed, nattempt, rank_radio, device, dtype, resolve_nit,
+                                    carry, warm_fraction, timings)
+    finally:
+        _RESOLVE_ROUTE.reset(token)
 
 
 def online_greedy_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e4, seed=0, device=0, timings=None):

@@ -84,7 +84,37 @@ class sdp_solver:
 
     round_batch = False  # True: all attempts of one rounding() call in a single device launch
 
+    round_draws = "host"  # "device" (mmw's keyword): rounding() is one Solver.round_attempts call, the directions drawn on the device
+    seed = 0
+    _round_calls = 0
+
+    def round_key(self, call):
+        """The key of this object's `call`-th rounding() under round_draws="device" (call = 0, 1, ...):
+        batch.probe_seed(self.seed, 0, 0x20000 | (call & 0x1FFFF)).  It seeds the device's directions -- attempt a rounds with
+        `Solver.round_randv(Z, D', key, a)` -- and the generator that fills the users left over."""
+        from .batch import probe_seed
+        return probe_seed(self.seed, 0, 0x20000 | (int(call) & 0x1FFFF))
+
+    def _rounding_device(self, Z, gX, state, nattempt):
+        """sdp_solver.py:18-25 as ONE device call (`Solver.round_attempts`, key `round_key(n)` for the n-th such call of this
+        object): the attempts' directions are drawn on the device, the first attempt that leaves nobody over wins, else the last --
+        what the sequential loop over those attempts returns.  The users left over are drawn from `np.random.default_rng(key)`; the
+        global NumPy stream is not touched."""
+        if not isinstance(gX, _lib.DeviceFactor):
+            gX = np.ascontiguousarray(gX, dtype=np.float64)
+        key = self.round_key(self._round_calls)
+        self._round_calls += 1
+        solver = self._device_solver(Z, state)
+        z, _, _ = solver.round_attempts(int(Z), gX, max(1, int(nattempt)), key)
+        not_assigned = z < 0
+        z_vec = z.astype(np.float64)
+        if np.any(not_assigned):
+            z_vec[not_assigned] = np.random.default_rng(key).integers(0, Z, int(not_assigned.sum()))
+        return z_vec, Z, np.sum(not_assigned)
+
     def rounding(self, Z, gX, state, nattempt=10):
+        if self.round_draws == "device":
+            return self._rounding_device(Z, gX, state, nattempt)
         if self.round_batch and nattempt > 1:
             return self._rounding_batched(Z, gX, state, nattempt)
         z_vec = None
@@ -152,6 +182,9 @@ class rand_sdp_solver(sdp_solver):
 
     def _rounding_batched(self, Z, gX, state, nattempt):
         return super()._rounding_batched(Z, self.index_ordered(gX), state, nattempt)
+
+    def _rounding_device(self, Z, gX, state, nattempt):
+        return super()._rounding_device(Z, self.index_ordered(gX), state, nattempt)
 
     def run_with_state(self, bs_iteration, Z, state):
         K = self._state_K(state)
