@@ -253,6 +253,31 @@ int mmw_factor(mmw_solver* s, int32_t rank, double* out, uint64_t seed);
  */
 int mmw_factor_spectral(mmw_solver* s, int32_t Z, int32_t index_order, double* out, uint64_t seed);
 
+#define MMW_FACTOR_RANDOM_MAX_COLS 2147483583 /* 2^31 - 1 - 64: the widest block mmw_factor_random draws (see there) */
+/*
+ * mmw_factor_random: rand_sdp_solver.run_with_state (sim_src/alg/sdp_solver.py:109-114) on a handle, any K: a K x cols block of
+ * standard normals with its rows normalised, as the handle's RESIDENT FACTOR -- what mmw_batch_factor_random is for a batch.  The
+ * block is float64 whatever the handle's dtype and lies where mmw_factor and mmw_factor_spectral leave theirs: mmw_round,
+ * mmw_round_env, mmw_round_attempts and mmw_round_env_attempts take it with gX == NULL and Dp = cols, MMW_F_FACTOR copies it out.
+ * out: K*cols float64, or NULL: the block stays on the device.
+ * The draw is the sketch's: row r, column pair p (columns 2p and 2p + 1) from Philox4x32-10 with counter (r, p, 0, 0x4d4d5753) under
+ * the key (seed & 0xffffffff, seed >> 32), Box-Muller in float64; a column >= cols does not count towards the norm; lane l of the
+ * row's wavefront adds the squares of the pairs l + 64 i in ascending i and the 64 sums meet in the sketch's wave reduction.  So the
+ * block is the float64 sketch of (seed, iteration 0): for cols <= 512 bitwise what mmw_sketch(seed, 0) returns on a float64 handle
+ * whose D is cols, and bitwise what mmw_batch_factor_random leaves for seeds[b] = seed; wider blocks continue the same rule (i = 4,
+ * 5, ...).  A float32 and a float64 handle give the same bits.
+ * index_order = 1: row k is then multiplied by 1 - k 2^-32 (rand_sdp_solver.index_ordered of the index_order = 0 block, bit for bit),
+ * so that the rounding visits the unit rows in index order, as for mmw_factor_spectral.
+ * Nothing else moves: the iterate, its sums, a chunk in flight, the run history and MMW_F_EXPM_INFO stay as they are (the draw queues
+ * behind the chunk; no iteration needs to have run), and a held mmw_factor / mmw_factor_spectral result is replaced as those replace
+ * each other.  MMW_F_FACTOR_ROWNORM answers MMW_ERR_STATE afterwards.
+ * Refused before anything is written, each with a message that names the value: cols < 1, index_order outside {0, 1}, cols >
+ * MMW_FACTOR_RANDOM_MAX_COLS (MMW_ERR_ARG; mmw_round itself asks nothing of D' but D' >= 1 -- this is the widest D' for which the 64-column slab
+ * counter of its projection, an int, does not wrap); a device -1 handle (MMW_ERR_STATE); a block of K x cols doubles that does not fit
+ * on the device (MMW_ERR_HIP; the last factor stands).
+ */
+int mmw_factor_random(mmw_solver* s, int32_t cols, int32_t index_order, double* out, uint64_t seed);
+
 /*
  * mmw_expm_apply: the stand-alone seam mmw.expm_half_randsk (mmw.py:224-229) minus the draw:
  * out[K,D] = exp(A) B for a symmetric CSR matrix A (pattern arbitrary) and a dense block B.
@@ -277,7 +302,7 @@ int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t 
  * entry: inprod = randv gX^T on the fp64 matrix cores, per-user slot preference order, the greedy
  * feasibility assignment in descending ||gX_k|| order.  z_out[nbatch,K] gets the slot or -1 for a user
  * left unassigned (the caller draws those, sdp_solver.py:104-105); rem_out[nbatch] the count.
- * gX == NULL: the K x Dp factor mmw_factor (or the block mmw_factor_spectral) computed last on this handle, read where it lies on the device.
+ * gX == NULL: the K x Dp factor mmw_factor (or the block mmw_factor_spectral or mmw_factor_random) computed last on this handle, read where it lies on the device.
  * Ties: equal norms are visited by lower user index, equal inner products prefer the lower slot.  Zr > 4800 (32 Zr bytes
  * of flags beyond the greedy kernel's LDS) is refused with MMW_ERR_ARG before anything is allocated, copied, launched or timed.
  */

@@ -50,7 +50,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
            "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map",
-           "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv"]
+           "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv", "mmw_factor_random"]
 
 
 class MMWError(RuntimeError):
@@ -97,6 +97,7 @@ def lib():
     L.mmw_gap.argtypes = [C.c_void_p, p_f64]
     L.mmw_factor.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_uint64]
     L.mmw_factor_spectral.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
+    L.mmw_factor_random.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
     L.mmw_sym_eig.argtypes = [C.c_int, C.c_int32, p_f64, C.c_double, C.c_int32, p_f64, p_f64, C.POINTER(C.c_int32)]
     L.mmw_expm_apply.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int32, C.c_int32, p_i32, p_i32, p_f64,
                                  p_f64, p_f64, p_f64, C.c_int32, p_f64]
@@ -510,6 +511,25 @@ class Solver(_Handle):
         out = np.empty((self.K, max(Z, 0)), dtype=np.float64)  # (a Z out of range is the library's to refuse)
         check(lib().mmw_factor_spectral(self._h, Z, io, _pd(out), C.c_uint64(int(seed))))
         self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, Z
+        return out
+
+    def factor_random(self, cols, seed, resident=False, index_order=False):
+        """rand_sdp_solver.run_with_state (sdp_solver.py:109-114) on this handle, any K (mmw_factor_random): a K x cols float64 block of
+        standard normals with its rows normalised, drawn on the device -- the fp64 sketch of (seed, iteration 0), bitwise what
+        `BatchSolver.factor_random` leaves for that seed, whatever this handle's dtype.  index_order=True:
+        `rand_sdp_solver.index_ordered` of that block, bit for bit.  resident=True: a `DeviceFactor` (its `index_ordered` says which of
+        the two it is) that `round` reads where it lies.  The iterate, its sums and a chunk in flight are not touched."""
+        self._keep_resident_factor()
+        cols, io = int(cols), 1 if index_order else 0
+        if resident:
+            check(lib().mmw_factor_random(self._h, cols, io, None, C.c_uint64(int(seed))))
+            self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, cols
+            df = DeviceFactor(self, cols, self._factor_serial, index_ordered=bool(io))
+            self._resident = weakref.ref(df)
+            return df
+        out = np.empty((self.K, max(cols, 0)), dtype=np.float64)  # (a width out of range is the library's to refuse)
+        check(lib().mmw_factor_random(self._h, cols, io, _pd(out), C.c_uint64(int(seed))))
+        self._factor_serial, self._last_rank = getattr(self, "_factor_serial", 0) + 1, cols
         return out
 
     def laplacian(self):

@@ -125,6 +125,9 @@ int mmw_factor(mmw_solver* s, int32_t rank, double* out, uint64_t seed) { return
 int mmw_factor_spectral(mmw_solver* s, int32_t Z, int32_t index_order, double* out, uint64_t seed) {
     return entry("mmw_factor_spectral", !s, "null solver handle", [&] { return s->factor_spectral(Z, index_order, out, seed); });
 }
+int mmw_factor_random(mmw_solver* s, int32_t cols, int32_t index_order, double* out, uint64_t seed) {
+    return entry("mmw_factor_random", !s, "mmw_factor_random: null solver handle", [&] { return s->factor_random(cols, index_order, out, seed); });
+}
 int mmw_round(mmw_solver* s, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) {
     return entry("mmw_round", !s, "null solver handle", [&] { return s->round(Zr, Dp, gX, nbatch, randv, z_out, rem_out); });
 }

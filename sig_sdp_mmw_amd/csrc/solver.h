@@ -40,6 +40,7 @@ struct mmw_solver {
     virtual int gap(double out[3]) = 0;
     virtual int factor(int32_t rank, double* out, uint64_t seed) = 0;
     virtual int factor_spectral(int32_t Z, int32_t index_order, double* out, uint64_t seed) = 0;
+    virtual int factor_random(int32_t cols, int32_t index_order, double* out, uint64_t seed) = 0;
     virtual int round(int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
                       int32_t* rem_out) = 0;
     virtual int round_env(mmw_env* env, int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out,
@@ -356,6 +357,18 @@ template <typename T> struct Solver final : mmw_solver {
         MMW_HIP(hipSetDevice(core.device));
         MMW_TRY(settle());
         return extras.factor_spectral(core.d_indptr.p, core.d_col.p, core.d_diag.p, (size_t)core.H.nnzL(), Z, index_order, out, seed);
+    }
+    // rand_sdp_solver.run_with_state as the handle's resident factor (solver_extras.h, factor_random).  The iterate, its sums and a chunk in
+    // flight play no part: nothing is settled, the draw queues behind the chunk on the handle's stream.
+    int factor_random(int32_t cols, int32_t index_order, double* out, uint64_t seed) override {
+        if (cols < 1) return fail(MMW_ERR_ARG, "mmw_factor_random: cols = " + std::to_string(cols) + " must be >= 1");
+        if (index_order != 0 && index_order != 1) return fail(MMW_ERR_ARG, "mmw_factor_random: index_order = " + std::to_string(index_order) + " must be 0 or 1");
+        if (cols > MMW_FACTOR_RANDOM_MAX_COLS)
+            return fail(MMW_ERR_ARG, "mmw_factor_random: cols = " + std::to_string(cols) + " exceeds " + std::to_string(MMW_FACTOR_RANDOM_MAX_COLS) +
+                                         ", the widest D' the rounding's projection walks in its 64-column slabs");
+        if (core.host_only) return host_only_handle();
+        MMW_HIP(hipSetDevice(core.device));
+        return extras.factor_random(cols, index_order, out, seed);
     }
     int round(int32_t Zr, int32_t Dp, const double* gX, int32_t nbatch, const double* randv, int32_t* z_out, int32_t* rem_out) override {
         if (core.host_only) return host_only_handle();

@@ -1,6 +1,7 @@
 // Rounding, epilogue factor and duality-gap routines that hang off a solver handle.
 #pragma once
 #include "factor.h"
+#include "kernels_factor_random.h"
 #include "kernels_round.h"
 #include "kernels_round_draw.h"
 #include "pattern.h"
@@ -200,6 +201,38 @@ template <typename T> struct Extras {
         spec_eig = eig.eig;
         const double rec[8] = {(double)fac.outer_done, fac.last_resid, (double)Z, (double)eig.block, eig.eig[0], eig.theta_next, (double)eig.mf_passes, 0.0};
         std::copy(rec, rec + 8, spec_info);
+        return MMW_OK;
+    }
+    // ---- the random embedding (sdp_solver.py:109-114; kernels_factor_random.h): K x cols row-normalised Philox normals of (seed, 0) into
+    // the buffer the factors live in, on the handle's stream behind whatever is in flight there.  Nothing of the iterate is read or
+    // written, so the caller does not settle a pending chunk for it.  A block that needs a larger buffer gets it BEFORE the old one is
+    // let go: a refused call leaves the last factor where it was.
+    int factor_random(int32_t cols, int index_order, double* out, uint64_t seed) {
+        const size_t n = (size_t)K * (size_t)cols;
+        if (fac.out64.cap < n || !fac.out64.p) {
+            size_t free_b = 0, total_b = 0;
+            MMW_HIP(hipMemGetInfo(&free_b, &total_b));
+            if (n > free_b / sizeof(double))
+                return fail(MMW_ERR_HIP, "mmw_factor_random: the block of K x cols = " + std::to_string(K) + " x " + std::to_string(cols) + " doubles (" +
+                                             std::to_string(n) + " x 8 bytes) does not fit: " + std::to_string(free_b) + " bytes are free on the device");
+            DevBuf<double> grown;
+            if (grown.alloc(n) != MMW_OK) {
+                (void)hipGetLastError();
+                return fail(MMW_ERR_HIP, "mmw_factor_random: the block of K x cols = " + std::to_string(K) + " x " + std::to_string(cols) + " doubles (" +
+                                             std::to_string(n) + " x 8 bytes) could not be allocated");
+            }
+            fac.out64.swap(grown);  // (the old buffer goes with `grown`: hipFree waits for the launches that still read it)
+        }
+        fac.out64.n = std::max(fac.out64.n, n);
+        fac.last_n = 0;
+        fac.last_on_host = false;
+        hipLaunchKernelGGL(k_factor_random, dim3(grid_rows(K)), dim3(BLOCK), 0, st, K, (int)cols, seed, index_order, fac.out64.p);
+        MMW_HIP(hipGetLastError());
+        if (out) MMW_TRY(fac.fetch_last(n));  // (out == nullptr: the block stays on the device until somebody reads it)
+        fac.last_n = n;
+        fac.last_rank = cols;
+        spec_live = false;  // (MMW_F_FACTOR_ROWNORM belongs to a spectral factor)
+        if (out) memcpy(out, fac.last_host.p, n * sizeof(double));
         return MMW_OK;
     }
     int read_rownorm(double* out, int64_t n) {

@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .batch import _check_warm, _fill, probe_seed, warm_iterations
+from .batch import METHODS, OPT_IN_METHODS, _check_warm, _fill, probe_seed, warm_iterations
 from .binary_search import binary_search_relaxation
 from .graphs import _NOISE_FLOOR_DBM, min_sinr_dec
 from .mmw import factor_rank_seed, mmw
@@ -33,18 +33,30 @@ def _setup(drop, nit, eta, seed, rank_radio, device, dtype):
     alg = None
     try:
         state = env.device_state()
-        alg = mmw(nit=nit, rank_radio=rank_radio, eta=eta, dtype="f32" if dtype == _lib.F32 else "f64", rng="device", device=device, seed=seed)
-        bs = binary_search_relaxation()
-        bs.verbose = False
-        bs.feasibility_check_alg = alg
-        _, Z, _ = bs.run(state)
-        Z = int(Z)
+        alg, _, Z, _, _ = _search(state, nit, eta, seed, rank_radio, device, dtype)
         _, gX = alg.run_with_state(0, Z, state)
         return env, alg, alg._device_solver(Z, state), Z, gX
     except BaseException:
         if alg is not None:
             alg.close()
         env.close()
+        raise
+
+
+def _search(state, nit, eta, seed, rank_radio, device, dtype):
+    """`_setup`'s search by itself: `binary_search_relaxation` on the device-resident `state` with `mmw` (device sketches, cold
+    probes, one at a time).  Returns (alg, z_vec, Z, remainder, probes): the colouring, slot count and leftover count of the probe
+    the search ends at, and the slot counts probed, in order.  `alg` (open, the caller's to close) holds the handle of `state`."""
+    alg = mmw(nit=nit, rank_radio=rank_radio, eta=eta, dtype="f32" if dtype == _lib.F32 else "f64", rng="device", device=device, seed=seed)
+    try:
+        bs = binary_search_relaxation()
+        bs.verbose = False
+        bs.feasibility_check_alg = alg
+        z_vec, Z, rem = bs.run(state)
+        probes = [int(m) for m in bs.LOGGED_NP_DATA["bs_search_per_it"][:, 5]]  # (rows: [g_step, step, time, left, right, mid, ...])
+        return alg, z_vec, int(Z), int(rem), probes
+    except BaseException:
+        alg.close()
         raise
 
 
@@ -264,4 +276,81 @@ def online_greedy_sweep(drop, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, res
                 timings.append({"device_s": t1 - t0, "step_s": time.perf_counter() - t1})
         return out
     finally:
+        env.close()
+
+
+def _geometry_drop(d):
+    """What `_env` reads of a drop, for a `graphs.mobile_drop` or a (sta_locs, ap_locs) pair."""
+    if hasattr(d, "sta_locs"):
+        return d
+    import types
+    return types.SimpleNamespace(sta_locs=np.asarray(d[0], dtype=np.float64), ap_locs=np.asarray(d[1], dtype=np.float64))
+
+
+def _embedding_arm(solver, Z, gX, nattempt, key):
+    """One `sdp_solver.rounding` of a resident, index-ordered block on the handle's own state, all attempts in ONE device call with the
+    directions drawn there from (key, attempt); the users the winner left over come from `np.random.default_rng(key)`
+    (`batch._finish`'s convention).  Returns (z_vec float64[K], remainder)."""
+    z, _, _ = solver.round_attempts(Z, gX, max(1, int(nattempt)), key)
+    return _fill(z, int((z < 0).sum()), Z, key)
+
+
+def compare(drop_or_geometry, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, dtype=_lib.F32, methods=METHODS, timings=None):
+    """sim_script/journal_version/sim_all_bler.py:30-72 for ONE instance of any K (a `graphs.mobile_drop` or a (sta_locs, ap_locs)
+    pair), as `batch.compare_many` runs it for many small ones: one MMW search, then every baseline at the slot count Z it ends at,
+    scored by BLER -- on one `DeviceEnv`, one solver handle for the embedding arms and one `GreedyHandle.from_env`; the state and the
+    embeddings never cross to the host.  (The script's `lrp_solver` arm needs cvxpy and SCS and is not run.)
+    "mmw" (always): `_search` on `env.device_state()` -- `binary_search_relaxation` with `mmw`, device sketches, cold probes; its
+    colouring is the one the search ends with.  Then the `methods`, in the order given:
+    "rand": `Solver.factor_random(Z * rank_radio, key, resident=True, index_order=True)` on the search's handle, then
+    `Solver.round_attempts(Z, block, nattempt, key)`; "spectral" (only when named): `Solver.factor_spectral(Z, resident=True,
+    index_order=True)` and the same rounding; "mgain" / "masso": `GreedyHandle.key(0 / 1)` then `run(key, Z, 1)`.  Users left over are
+    drawn from `np.random.default_rng(key).integers(0, Z, n)`.  key = batch.probe_seed(seed, 0, 0x40000 | m), m the method's index in
+    batch.METHODS + OPT_IN_METHODS: `batch.baselines_many`'s keys at instance 0.  One `env.evaluate` per method.
+    Returns {"Z", "probes", "z_vec": {method: float64[K]}, "remainder": {method: int}, "bler": {method: float64[K]}}, "mmw"
+    included.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"} and "arm_s": {method: seconds}.  A method
+    that is not one of METHODS + OPT_IN_METHODS raises ValueError by name before any device work."""
+    names = METHODS + OPT_IN_METHODS
+    methods = tuple(methods)
+    for name in methods:
+        if name not in names:
+            raise ValueError("compare: method must be one of %s, got %r" % (names, name))
+    drop = _geometry_drop(drop_or_geometry)
+    env = _env(drop, int(device))
+    alg = greedy = None
+    try:
+        state = env.device_state()
+        t0 = time.perf_counter()
+        alg, z_mmw, Z, rem_mmw, probes = _search(state, int(nit), float(eta), int(seed), int(rank_radio), int(device), dtype)
+        solver = alg._device_solver(Z, state)
+        t1 = time.perf_counter()
+        z_vec, remainder, arm_s = {"mmw": np.asarray(z_mmw, dtype=np.float64)}, {"mmw": rem_mmw}, {}
+        for name in methods:
+            ta = time.perf_counter()
+            m = names.index(name)
+            key = probe_seed(seed, 0, 0x40000 | m)
+            if name == "rand":
+                block = solver.factor_random(Z * int(rank_radio), key, resident=True, index_order=True)
+                z_vec[name], remainder[name] = _embedding_arm(solver, Z, block, nattempt, key)
+            elif name == "spectral":
+                block = solver.factor_spectral(Z, resident=True, index_order=True)
+                z_vec[name], remainder[name] = _embedding_arm(solver, Z, block, nattempt, key)
+            else:
+                if greedy is None:
+                    greedy = _lib.GreedyHandle.from_env(env)
+                slot, _, rem = greedy.run(greedy.key(m - 1), Z, 1)
+                z_vec[name], remainder[name] = _fill(slot, rem, Z, key)
+            arm_s[name] = time.perf_counter() - ta
+        t2 = time.perf_counter()
+        bler = {}
+        for name in ("mmw",) + methods:
+            _, bler[name] = env.evaluate(z_vec[name], Z)
+        if timings is not None:
+            timings.update(search_s=t1 - t0, baselines_s=t2 - t1, evaluate_s=time.perf_counter() - t2, arm_s=arm_s)
+        return {"Z": Z, "probes": probes, "z_vec": z_vec, "remainder": remainder, "bler": bler}
+    finally:
+        if greedy is not None:
+            greedy.close()
+        if alg is not None:
+            alg.close()
         env.close()

@@ -170,12 +170,34 @@ class rand_sdp_solver(sdp_solver):
     users: sorting the norms as computed sorts their last-bit noise, which changes with the summation order.  `rounding_one_attempt`
     therefore visits the users in index order, the tie rule taken literally (and what the batch does, `BatchSolver.factor_random`):
     it hands the device `index_ordered(gX)`, whose norms fall with the index by steps far above the noise.  Scaling a row by a
-    positive number leaves its user's slot preferences as they are."""
+    positive number leaves its user's slot preferences as they are.
+
+    draws="device" (opt-in; "host", the default, is everything above, on the same NumPy stream): `run_with_state` draws the embedding
+    on the device instead, `Solver.factor_random(Z * rank_radio, key, resident=True, index_order=True)` on the cached handle the
+    rounding uses afterwards (built for a `DeviceState` without a host copy of the state), with
+    key = batch.probe_seed(seed, 0, 0x40000 | 0) -- `batch.baselines_many`'s key for "rand" at instance 0, so a batch of one and the
+    handle agree on the draw.  It returns the block resident and already index-ordered (a `DeviceFactor`), which the rounding
+    reads where it lies; the global NumPy stream is not touched by the draw."""
+
+    def __init__(self, nit=100, rank_radio=2, alpha=1., *, draws="host", seed=0, device=0):
+        if draws not in ("host", "device"):
+            raise ValueError("draws must be 'host' or 'device', got %r" % (draws,))
+        sdp_solver.__init__(self, nit=nit, rank_radio=rank_radio, alpha=alpha)
+        self.draws = draws
+        self.seed = int(seed)  # (0 and device 0 are the base class's own)
+        self._device_index = int(device)
 
     @staticmethod
     def index_ordered(gX):
+        if isinstance(gX, _lib.DeviceFactor) and gX.index_ordered:  # scaled on the device already: a second pass would copy it out
+            return gX
         K = gX.shape[0]
         return np.asarray(gX, dtype=np.float64) * (1.0 - np.arange(K) * 2.0 ** -32)[:, None]
+
+    def embedding_key(self):
+        """The seed of the device's draw: batch.probe_seed(self.seed, 0, 0x40000 | 0)."""
+        from .batch import probe_seed
+        return probe_seed(self.seed, 0, 0x40000 | 0)
 
     def rounding_one_attempt(self, Z, gX, state):
         return super().rounding_one_attempt(Z, self.index_ordered(gX), state)
@@ -186,7 +208,12 @@ class rand_sdp_solver(sdp_solver):
     def _rounding_device(self, Z, gX, state, nattempt):
         return super()._rounding_device(Z, self.index_ordered(gX), state, nattempt)
 
+    draws = "host"
+
     def run_with_state(self, bs_iteration, Z, state):
+        if self.draws == "device":
+            solver = self._device_solver(Z, state)
+            return True, solver.factor_random(int(Z) * self.rank_radio, self.embedding_key(), resident=True, index_order=True)
         K = self._state_K(state)
         randv = np.random.randn(K, Z * self.rank_radio)
         randv = randv / np.linalg.norm(randv, axis=1, keepdims=True)
