@@ -97,6 +97,9 @@ enum mmw_field {
                              relative residual, Z, block width b, theta_Z, theta_Z+1 (0 when b = Z), filter passes that ran on the matrix
                              cores, 0}; zeros before the first call; solver handles only */
     MMW_F_SPECTRAL_EIG = 29,  /* [Z]  the Ritz values the last mmw_factor_spectral kept, ascending (the block's column order) */
+    MMW_F_GAP_INFO = 30,  /* [6]      mmw_set_gap's record since mmw_create: {rows logged, rows continued at a settle, rows enqueued through the
+                             cap (no slot of the ring was free, or no guess at hand: such a row is never continued), launches of the phase, largest |steps|, bytes of the phase's work space};
+                             solver handles only */
     MMW_F_KERNEL_US = 15  /* [2*9]    per kernel class {total device us, launches} since mmw_set_profile(1):
                              spmm, sddmm, dual, loss, krylov vector ops, sketch, projection, greedy, factor */
 };
@@ -228,6 +231,37 @@ int mmw_read_i32(mmw_solver* s, int which, int32_t* out, int64_t n);
  * i+1 terms accumulated): out = { max_c e_c(Xbar), K*lambda_min(L(Ybar)), difference }.
  */
 int mmw_gap(mmw_solver* s, double out[3]);
+
+/*
+ * The duality gap inside the loop of a solver handle, at any K: the LOG_GAP branch mmw.py:79-117 as launches of the handle's own
+ * stream between the iterations (csrc/kernels_gap.h), so a logged run stays on the chunked path mmw_iterate(n) takes without it.
+ *
+ * mmw_set_gap: from the next mmw_iterate on, iteration i logs one row when it starts, from the i + 1 terms of the running sums
+ * (Xbar = (xavg + the X still waiting for its LOSS pass) / (i + 1), Ybar = yavg / (i + 1); mmw.py:77-81): {e_max by the DUAL
+ * formulas, K * theta with theta = lambda_min(L(Ybar)), e_max - K * theta, steps} -- LOGGED_NP_DATA["gap"][:, 3:6] of the reference
+ * and the Lanczos steps taken -- by mmw_batch_set_gap's definitions: L(Ybar) by the LOSS formulas with coefficient +1, plain Lanczos
+ * from the Philox start vector keyed by (row, K, nnzL), theta_min(T_m) and the last eigenvector component solved at the checks
+ * mmw_gap_checks lists, stop at |beta_m s_m| <= 1e-11 * scale, on beta_m <= 1e-11 * scale, or at m = min(K, m_cap); `steps` is
+ * NEGATIVE when the cap cut a Krylov space short.  m_cap <= 0 takes 600, m_cap > 1024 is MMW_ERR_ARG.  The phase works in float64 on
+ * both dtypes (an fp32 handle's sums are widened as they are read, the pattern's constants are the host's doubles; an fp32 handle
+ * built on the device holds its gains as floats only and widens those) and only reads the iterate: with the same sequence of calls every
+ * field, counter and plan of the handle is bitwise what it is with the gap off, and the chunk lengths are the same.  A row is a
+ * function of the sums it reads and of m_cap only: not of first_steps, of the split of the iterations into calls, or of where a chunk
+ * ended.  first_steps: how far a row is enqueued while no earlier row of the run has been read back (<= 0: the cap); later rows go
+ * through the first check at or after the largest |steps| read back so far.  Rows are read back where the loop synchronises anyway;
+ * one that is not done by then is continued from its slot of a ring (at most 33 slots under a byte limit, MMW_F_GAP_INFO).  A
+ * discarded chunk's rows are rewritten by its replay.  Rows of iterations that ran with the gap off are NaN (steps 0); mmw_reset,
+ * mmw_set_slots and mmw_set_slots_warm clear the log and keep the setting; mmw_carry leaves the destination's log alone; mmw_gap is
+ * unchanged.  MMW_ERR_STATE on a device -1 handle.
+ * mmw_read_gap: 4 doubles per iteration done (n must be 4 x that count, else MMW_ERR_ARG); MMW_ERR_STATE if the gap was never
+ * enabled.
+ * mmw_gap_checks: the steps at which a row of (K, m_cap) is checked -- 10, 20, ... with the interval growing by a quarter, the last
+ * at min(K, m_cap): for K >= 600 and the default cap 10 20 30 40 50 62 77 96 120 150 187 233 291 363 453 566 600.  *n gets their
+ * count; `out` (room entries, or NULL to ask for the count) gets them.  A host function: no device is needed.
+ */
+int mmw_set_gap(mmw_solver* s, int enabled, int32_t m_cap, int32_t first_steps);
+int mmw_read_gap(mmw_solver* s, double* out, int64_t n);
+int mmw_gap_checks(int32_t K, int32_t m_cap, int32_t* out, int32_t room, int32_t* n);
 
 /*
  * mmw_factor: the epilogue mmw.py:202-216.  Xbar = (sum of X)/nit on the pattern, top-`rank`

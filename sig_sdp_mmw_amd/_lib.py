@@ -28,6 +28,7 @@ BATCH_F_BUILD_INFO = 26  # batches, per instance: {0 built from host arrays / 1 
 SOLVER_F_LAPLACIAN = 27  # solver handles: the Laplacian of S_gain + S_gain^T on the L pattern [nnzL]
 SOLVER_F_SPECTRAL_INFO = 28  # solver handles: the last mmw_factor_spectral's record [8]
 SOLVER_F_SPECTRAL_EIG = 29  # solver handles: the Ritz values it kept, ascending [Z]
+SOLVER_F_GAP_INFO = 30  # solver handles: mmw_set_gap's record [6]
 BATCH_MAX_PARTS = 32  # MMW_BATCH_MAX_PARTS: workgroups per instance at most (mmw_batch_set_split, mmw_batch_set_factor_split)
 BATCH_MAX_ROW_PARTS = 64  # MMW_BATCH_MAX_ROW_PARTS: row parts per instance at most (mmw_batch_set_row_split)
 BATCH_MAX_HEAD_PARTS = 64  # MMW_BATCH_MAX_HEAD_PARTS: head parts per instance at most (mmw_batch_set_head_split)
@@ -50,7 +51,8 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_row_ranges", "mmw_batch_carry", "mmw_batch_carry_map", "mmw_batch_set_head_split", "mmw_batch_head_ranges",
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
            "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map",
-           "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv", "mmw_factor_random"]
+           "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv", "mmw_factor_random",
+           "mmw_set_gap", "mmw_read_gap", "mmw_gap_checks"]
 
 
 class MMWError(RuntimeError):
@@ -95,6 +97,9 @@ def lib():
     L.mmw_read_f64.argtypes = [C.c_void_p, C.c_int, p_f64, C.c_int64]
     L.mmw_read_i32.argtypes = [C.c_void_p, C.c_int, p_i32, C.c_int64]
     L.mmw_gap.argtypes = [C.c_void_p, p_f64]
+    L.mmw_set_gap.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32]
+    L.mmw_read_gap.argtypes = [C.c_void_p, p_f64, C.c_int64]
+    L.mmw_gap_checks.argtypes = [C.c_int32, C.c_int32, p_i32, C.c_int32, p_i32]
     L.mmw_factor.argtypes = [C.c_void_p, C.c_int32, p_f64, C.c_uint64]
     L.mmw_factor_spectral.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
     L.mmw_factor_random.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
@@ -274,6 +279,15 @@ _LEN = {F_Y: "C", F_E_ACCU: "C", F_E_THIS: "C", F_LVAL: "nnzL", F_XVAL: "nnzL", 
         F_S_SUM: "K", F_NORM_H: "K", F_ST_DATA: "nnzST", SOLVER_F_LAPLACIAN: "nnzL", F_FACTOR_ROWNORM: "K"}
 _ILEN = {I_L_INDPTR: ("K", 1), I_L_INDICES: ("nnzL", 0), I_ST_INDPTR: ("K", 1), I_ST_INDICES: ("nnzST", 0), I_GAIN_X: ("E_gain", 0),
          I_GAIN_Y: ("E_gain", 0), I_ASSO_X: ("E_asso", 0), I_ASSO_Y: ("E_asso", 0), I_DIAG_POS: ("K", 0), I_ASSO_POS: ("E_asso", 0)}
+
+
+def gap_checks(K, m_cap=0):
+    """The Lanczos steps at which a logged gap row of (K, m_cap) is checked (mmw_gap_checks; needs no device)."""
+    n = C.c_int32(0)
+    check(lib().mmw_gap_checks(int(K), int(m_cap), None, 0, C.byref(n)))
+    out = np.empty(n.value, dtype=np.int32)
+    check(lib().mmw_gap_checks(int(K), int(m_cap), _pi(out), int(out.size), C.byref(n)))
+    return [int(x) for x in out]
 
 
 class _Handle:
@@ -478,6 +492,25 @@ class Solver(_Handle):
         out = np.empty(3, dtype=np.float64)
         check(lib().mmw_gap(self._h, _pd(out)))
         return out
+
+    def set_gap(self, on=True, m_cap=0, first_steps=0):
+        """Log the duality gap (mmw.py:79-117) of every iteration that follows, inside the loop (mmw_set_gap); m_cap <= 0: 600 steps.
+        first_steps: how far a row is enqueued before any row of the run has been read back (<= 0: the cap); it changes no row."""
+        check(lib().mmw_set_gap(self._h, 1 if on else 0, int(m_cap), int(first_steps)))
+
+    def gap_log(self):
+        """(rows[n, 3], steps[n]) of the n iterations done, like `BatchSolver.gap_log`: {e_max, K lambda_min(L(Ybar)), difference} --
+        columns 3:6 of the reference's LOGGED_NP_DATA["gap"] -- and the Lanczos steps taken (negative: the cap was reached first).
+        Rows of iterations that ran with the gap off are NaN (steps 0)."""
+        n = self.iterations_done
+        out = np.empty((n, 4), dtype=np.float64)
+        check(lib().mmw_read_gap(self._h, _pd(out), int(out.size)))
+        return out[:, :3].copy(), out[:, 3].astype(np.int64)
+
+    def gap_info(self):
+        """MMW_F_GAP_INFO: what the logged gap has cost since the handle was made."""
+        v = self.read(SOLVER_F_GAP_INFO, 6)
+        return {"rows": int(v[0]), "continued": int(v[1]), "capped": int(v[2]), "launches": int(v[3]), "max_steps": int(v[4]), "bytes": int(v[5])}
 
     def factor(self, rank, seed=0, resident=False):
         """X_half (K, rank) float64.  resident=True: a `DeviceFactor` -- the factor stays on the device, `round` takes it from there,

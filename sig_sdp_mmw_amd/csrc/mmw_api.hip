@@ -121,6 +121,19 @@ int mmw_sketch(mmw_solver* s, uint64_t seed, int32_t iteration, double* out, int
 int mmw_read_f64(mmw_solver* s, int which, double* out, int64_t n) { return entry("mmw_read_f64", !s, "null solver handle", [&] { return !out && n ? fail(MMW_ERR_ARG, "null output") : s->read_f64(which, out, n); }); }
 int mmw_read_i32(mmw_solver* s, int which, int32_t* out, int64_t n) { return entry("mmw_read_i32", !s, "null solver handle", [&] { return !out && n ? fail(MMW_ERR_ARG, "null output") : s->read_i32(which, out, n); }); }
 int mmw_gap(mmw_solver* s, double out[3]) { return entry("mmw_gap", !s, "null solver handle", [&] { return s->gap(out); }); }
+int mmw_set_gap(mmw_solver* s, int enabled, int32_t m_cap, int32_t first_steps) { return entry("mmw_set_gap", !s, "null solver handle", [&] { return s->set_gap(enabled, m_cap, first_steps); }); }
+int mmw_read_gap(mmw_solver* s, double* out, int64_t n) { return entry("mmw_read_gap", !s || (!out && n), "null pointer", [&] { return s->read_gap(out, n); }); }
+int mmw_gap_checks(int32_t K, int32_t m_cap, int32_t* out, int32_t room, int32_t* n) {
+    return entry("mmw_gap_checks", !n, "null pointer", [&] {
+        if (K < 1) return fail(MMW_ERR_ARG, "mmw_gap_checks: K must be >= 1");
+        if (m_cap > GAP_MAX_M) return fail(MMW_ERR_ARG, "mmw_gap_checks: m_cap = " + std::to_string(m_cap) + " exceeds " + std::to_string(GAP_MAX_M));
+        const std::vector<int> c = gap_check_list(K, m_cap <= 0 ? GAP_DEFAULT_M : m_cap);
+        *n = (int32_t)c.size();
+        if (out && room < (int32_t)c.size()) return fail(MMW_ERR_ARG, "mmw_gap_checks: room for " + std::to_string(room) + " of " + std::to_string(c.size()) + " checks");
+        if (out) std::copy(c.begin(), c.end(), out);
+        return MMW_OK;
+    });
+}
 int mmw_factor(mmw_solver* s, int32_t rank, double* out, uint64_t seed) { return entry("mmw_factor", !s, "null solver handle", [&] { return s->factor(rank, out, seed); }); }
 int mmw_factor_spectral(mmw_solver* s, int32_t Z, int32_t index_order, double* out, uint64_t seed) {
     return entry("mmw_factor_spectral", !s, "null solver handle", [&] { return s->factor_spectral(Z, index_order, out, seed); });

@@ -38,6 +38,8 @@ struct mmw_solver {
     virtual int read_f64(int which, double* out, int64_t n) = 0;
     virtual int read_i32(int which, int32_t* out, int64_t n) = 0;
     virtual int gap(double out[3]) = 0;
+    virtual int set_gap(int enabled, int32_t m_cap, int32_t first_steps) = 0;
+    virtual int read_gap(double* out, int64_t n) = 0;
     virtual int factor(int32_t rank, double* out, uint64_t seed) = 0;
     virtual int factor_spectral(int32_t Z, int32_t index_order, double* out, uint64_t seed) = 0;
     virtual int factor_random(int32_t cols, int32_t index_order, double* out, uint64_t seed) = 0;
@@ -146,7 +148,7 @@ template <typename T> struct Solver final : mmw_solver {
     int on_restart(int32_t nit_, bool warm) {
         if (nit_ < 1) return fail(MMW_ERR_ARG, "nit must be >= 1");
         core.nit = nit_;
-        loop.on_restart(warm, core.iter);
+        loop.on_restart(warm, core.iter, nit_);
         core.iter = 0;
         emax.drop();
         pending.clear();
@@ -172,6 +174,7 @@ template <typename T> struct Solver final : mmw_solver {
         emax.drop();  // (the reduction enqueued behind the discarded chunk saw its e_this)
         MMW_TRY(core.eng.clear_violation());
         MMW_TRY(pending.restore(core));
+        loop.gap.drop_pending();  // the discarded chunk's gap rows: the replay enqueues them again
         core.iter = pending.iter0;
         return core.pt.drop_since(pending.events0, core.st);  // the timers of the discarded chunk (earlier chunks keep theirs)
     }
@@ -190,7 +193,12 @@ template <typename T> struct Solver final : mmw_solver {
         pol.note_plan(core.eng.last, core.iter);
         pol.m_guess = pol.next_launch_order(core.eng.last, core.eng.max_order, core.iter);
     }
+    // the pending chunk, then the gap rows that rode with it (solver_gap.h): read back behind the synchronisation the chunk's plan took
     int settle() {
+        MMW_TRY(settle_chunk());
+        return loop.gap.collect(core.st, core.d_indptr.p, core.d_col.p);
+    }
+    int settle_chunk() {
         if (!pending.live) return MMW_OK;
         pending.clear();
         ChunkPolicy& pol = loop.pol;
@@ -339,6 +347,19 @@ template <typename T> struct Solver final : mmw_solver {
         PatternDev<T> Pc = core.pat();  // the gap's kernels walk the CSR copy
         Pc.e2w = nullptr; Pc.xasso = nullptr; Pc.xdiag_base = -1;
         return extras.gap(Pc, core.d_lrow.p, core.xavg.p, core.yavg.p, core.iter + 1, out);
+    }
+    // ---- mmw_set_gap / mmw_read_gap: the gap row of every iteration, logged inside the loop (solver_gap.h, kernels_gap.h)
+    int set_gap(int enabled, int32_t m_cap, int32_t first_steps) override {
+        if (core.host_only) return host_only_handle();
+        MMW_HIP(hipSetDevice(core.device));
+        MMW_TRY(settle());  // rows in flight belong to the old setting
+        return loop.gap.configure(enabled, m_cap, first_steps, core.K, (size_t)core.H.nnzL(), core.nit);
+    }
+    int read_gap(double* out, int64_t n) override {
+        if (core.host_only) return host_only_handle();
+        MMW_HIP(hipSetDevice(core.device));
+        MMW_TRY(settle());
+        return loop.gap.read(core.iter, out, n);
     }
     int factor(int32_t rank, double* out, uint64_t seed) override {
         if (core.host_only) return host_only_handle();

@@ -1,10 +1,12 @@
 // The loop of the solver handle (solver.h): one call of iterate_impl enqueues `n` iterations -- per call a ChunkRun, per iteration the
 // phases DUAL, LOSS, sketch + exponential, X on the pattern -- on the iterate the core holds (solver_core.h).  SolverLoop owns what only
 // the phases touch: their scratch, the chunk policy, the sketch an earlier launch drew, the counters of MMW_F_DUAL_INFO.
+// While mmw_set_gap is on, every iteration is preceded by its LOG_GAP row (solver_gap.h), enqueued in front of the phase timers' events.
 //   discard of a chunk   nothing here is restored: the scratch is rewritten by the replay, `carry` is forgotten by every iterate_impl
 //   reset / warm restart on_restart: the policy's history (chunk_policy.h says what each kind keeps); the counters run on
 #pragma once
 #include "solver_core.h"
+#include "solver_gap.h"
 
 namespace {
 // The sketch that rode in an earlier launch (a LOSS pass or the previous SDDMM launch drew it into the start block), and where the last
@@ -45,6 +47,7 @@ template <typename T> struct SolverLoop {
     bool rs_last = false;    // the last iteration enqueued left rsfx for the X the next one starts from
     const bool rs_enabled;
     long long n_rs_iters = 0, n_fused_iters = 0, n_first_iters = 0, n_first16_iters = 0;  // MMW_F_DUAL_INFO
+    GapPhase<T> gap;  // the logged duality gap (mmw_set_gap; solver_gap.h): reads the iterate, writes its own buffers
     // init_common (solver_create.h), in its order of allocation
     int alloc_scratch(const Core& co) {
         const int K = co.K;
@@ -54,9 +57,10 @@ template <typename T> struct SolverLoop {
         return MMW_OK;
     }
     int resize(const Core& co) { return stage64.alloc((size_t)co.K * co.D); }  // the uploaded sketch's staging block follows K x D
-    void on_restart(bool warm, int iter) {
+    void on_restart(bool warm, int iter, int nit) {
         if (warm) pol.on_warm_restart(iter);
         else pol.on_reset();
+        if (gap.ever) gap.clear_log(nit);
     }
     int sketch_slabs(const Core& co) const { return std::min(grid_rows(co.K), co.sw.sk_slabs); }  // few slabs for the start-norm reduction
     int launch_sketch(Core& co, hipStream_t s, uint64_t seed, uint32_t it, bool planes_f16 = false) {
@@ -142,14 +146,18 @@ template <typename T> struct SolverLoop {
             IterRun s;
             s.it = it;
             s.acc = (co.iter + 1 < co.nit) ? 1 : 0;  // the last X / Y are not averaged (mmw.py:77-78,203)
+            // LOG_GAP (mmw.py:79-117): the row of the iteration that starts, in front of the phase timers' first event
+            if (gap.on) MMW_TRY(gap.enqueue_row(co.st, co.H, c.P, co.d_lrow.p, co.x.live(co).avg->p, c.xavg_deferred ? c.xcur : (const T*)nullptr, co.yavg.p, co.iter));
             MMW_TRY(co.pt.record(0, co.iter, co.st));
             MMW_TRY(phase_dual(co, c, s));
             MMW_TRY(phase_loss(co, c, s));
             MMW_TRY(phase_expm(co, c, s));
             MMW_TRY(phase_x(co, c, s));
             ++co.iter;
+            if (!optimistic) MMW_TRY(gap.collect(co.st, co.d_indptr.p, co.d_col.p));  // (this path reads its plans back every iteration)
         }
-        return chunk_tail(co, c);
+        MMW_TRY(chunk_tail(co, c));
+        return gap.queue_copy(co.st);
     }
     // ---- DUAL: the violations of the current X, their softmax, and (lagged) the plan of this iteration's exponential
     int phase_dual(Core& co, ChunkRun& c, IterRun& s) {

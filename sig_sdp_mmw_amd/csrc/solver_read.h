@@ -68,6 +68,7 @@ template <typename T> struct SolverReads {
                 return export_vals({!co.eng.use_blk ? 0.0 : (co.eng.use_mfma ? 3.0 : (co.eng.blk.half_tile ? 2.0 : 1.0)), co.eng.use_mfma && co.eng.last_mfma_ok ? 1.0 : 0.0}, out, n, "spmm kind has 2 entries");
             case MMW_F_DUAL_INFO:
                 return export_vals({(double)lp.n_rs_iters, (double)lp.n_fused_iters, (double)lp.n_first_iters, (double)lp.n_first16_iters}, out, n, "dual info has 4 entries");
+            case MMW_F_GAP_INFO: return lp.gap.info(out, n);
             case MMW_F_FACTOR: return extras.read_factor(out, n);
             case MMW_F_FACTOR_ROWNORM: return extras.read_rownorm(out, n);
             case MMW_F_SPECTRAL_INFO: {

@@ -29,6 +29,9 @@ defaults from the environment, so that a harness script that constructs `mmw(nit
           (sdp_solver.py:18-25) -- keyed `batch.probe_seed(seed, 0, 0x20000 | (n & 0x1FFFF))` for this object's n-th rounding
           (n = 0, 1, ...: `sdp_solver.round_key`); the users left over come from `np.random.default_rng(key)`, so the rounding
           does not touch the global NumPy stream.  No environment switch.
+  gap_log  with log_gap=True: "call" (default) takes every gap row by one `Solver.gap()` call in front of a one-iteration
+          `iterate`, as before; "loop" logs the rows inside the loop (`Solver.set_gap`), keeps `iterate(nit)` whole -- the chunked path
+          an unlogged run takes -- and fills LOGGED_NP_DATA["gap"] afterwards from `Solver.gap_log()`, same shape and columns.
 """
 import math
 import os
@@ -52,7 +55,7 @@ def factor_rank_seed(K, Z, rank_radio, run_seed):
 class mmw(STATS_OBJECT, sdp_solver):
     def __init__(self, nit=100, rank_radio=2, alpha=1., eta=0.1, log_gap=False, *, dtype=None, rng=None,
                  expm="lanczos", expm_tol=None, expm_max_order=12, device=None, seed=0, warm_start=None, warm_fraction=1.0 / 3.0,
-                 round_draws="host"):
+                 round_draws="host", gap_log="call"):
         sdp_solver.__init__(self, nit=nit, rank_radio=rank_radio, alpha=alpha)
         self.eta = eta
         self.LOG_GAP = log_gap
@@ -79,13 +82,16 @@ class mmw(STATS_OBJECT, sdp_solver):
             raise ValueError("round_draws in {host,device}")
         self.round_draws = round_draws
         self._round_calls = 0
+        if gap_log not in ("call", "loop"):
+            raise ValueError("gap_log in {call,loop}")
+        self.gap_log = gap_log
 
     def sibling(self):
         """A second solver with the same settings and its own device handle, stream and sketch seeds (binary_search's opt-in
         speculative mode keeps one probe in flight on each)."""
         other = mmw(nit=self.nit, rank_radio=self.rank_radio, alpha=self.alpha, eta=self.eta, log_gap=self.LOG_GAP, dtype=self.dtype, rng=self.rng,
                     expm=self.expm, expm_tol=self.expm_tol, expm_max_order=self.expm_max_order, device=self._device_index, seed=self.seed + 7919,
-                    warm_start=self.warm_start, warm_fraction=self.warm_fraction, round_draws=self.round_draws)
+                    warm_start=self.warm_start, warm_fraction=self.warm_fraction, round_draws=self.round_draws, gap_log=self.gap_log)
         other.round_batch = self.round_batch
         return other
 
@@ -120,14 +126,17 @@ class mmw(STATS_OBJECT, sdp_solver):
 
         self._runs += 1
         dev_seed = (self.seed << 20) + self._runs
-        per_call = 1 if self.LOG_GAP else nit
+        in_loop = self.LOG_GAP and self.gap_log == "loop"
+        if in_loop:
+            solver.set_gap(True)
+        per_call = 1 if self.LOG_GAP and not in_loop else nit
         if self.rng == "host":
             per_call = min(per_call, max(1, _SKETCH_CHUNK_BYTES // (K * D * 8)))
         done = 0
         self.N_STEP = 0
         while done < nit:
             n = min(per_call, nit - done)
-            if self.LOG_GAP:
+            if self.LOG_GAP and not in_loop:
                 self._add_np_log("gap", done, solver.gap())  # [max violation at Xbar, K lambda_min(L(Ybar)), gap], mmw.py:116
             if self.rng == "host":
                 randv = np.random.randn(n * K, D) / math.sqrt(float(D))  # the draws of mmw.py:226, n iterations at once
@@ -138,6 +147,9 @@ class mmw(STATS_OBJECT, sdp_solver):
             done += n
             self.N_STEP = done
         solver.sync()
+        if in_loop:
+            self._add_np_log_rows("gap", np.arange(nit), solver.gap_log()[0])
+            solver.set_gap(False)  # the handle is kept for later runs: they log only if they ask
         us = solver.read(_lib.F_PHASE_US).reshape(nit, 4) if stride > 0 else np.zeros((nit, 4))
         steps = np.arange(nit)
         zk = np.tile(np.array([Z, K], dtype=np.float64), (nit, 1))
