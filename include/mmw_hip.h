@@ -331,6 +331,28 @@ int mmw_expm_apply(int device, int dtype, int method, int max_order, double tol,
 int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t max_sweeps, double* theta, double* Q, int32_t* sweeps);
 
 /*
+ * The factor's dense building blocks, each as the one operation it is (csrc/kernels_dense.h through DenseWork / Factorizer of
+ * csrc/factor.h), handle-less like mmw_sym_eig.  Blocks are K x ld row-major float64 host arrays, ld >= b their row stride; dtype
+ * (MMW_F32 / MMW_F64) is the type T the block is stored in on the device -- the call rounds to T on the host before the upload and
+ * widens what it reads back.  The caller fills the padding columns [b, ld) of an input; they influence no result.  MMW_CHOL_LDS and
+ * MMW_FACTOR_NO_NS are read at the call.  MMW_ERR_ARG before the device is touched: a null pointer, K < 1, b < 1, b > 2048,
+ * ld < b, n < 1, ldq < n, n > ld, an unknown dtype.
+ *
+ * mmw_dense_gram: G_out[b x b] = V[:, :b]^T W[:, :b] (k_gram_tiles + k_gram_reduce), sym != 0: (G + G^T) / 2.
+ * mmw_dense_gemm: C_out[K x ld], columns < n = V[:, :b] Q[:b, :n] (k_gemm_tall; Q float64 with row stride ldq), the other columns 0.
+ * mmw_dense_chol: the Cholesky-QR's factorisation of a b x b Gram matrix G: dscale_out[b] = 1 / sqrt(diag G) (0 where the diagonal
+ *   is not positive), L_out[b x b] the lower-triangular factor of G' = diag(dscale) G diag(dscale) with zeros above the diagonal,
+ *   dinv_out[ceil(b / 32)][32 x 32] the inverses of L's 32 x 32 diagonal blocks (identity-padded in the last one), *ok = 0 when a
+ *   pivot was not positive (L_out and dinv_out then hold no result).
+ * mmw_dense_orth: Q_out[K x ld] = Factorizer::orthonormalise of V (two passes; eps is the eigen fallback's relative floor, 1e-14 in
+ *   the factor); path_out[pass] = 0 Cholesky-QR, 1 Newton-Schulz step, 2 eigen fallback.  Columns [b, ld) of Q_out are 0.
+ */
+int mmw_dense_gram(int device, int dtype, int32_t K, int32_t b, int32_t ld, const double* V, const double* W, int sym, double* G_out);
+int mmw_dense_gemm(int device, int dtype, int32_t K, int32_t b, int32_t n, int32_t ld, const double* V, int32_t ldq, const double* Q, double* C_out);
+int mmw_dense_chol(int device, int32_t b, const double* G, double* L_out, double* dscale_out, double* dinv_out, int32_t* ok);
+int mmw_dense_orth(int device, int dtype, int32_t K, int32_t b, int32_t ld, const double* V, double eps, double* Q_out, int32_t path_out[2]);
+
+/*
  * mmw_round: one sdp_solver.rounding_one_attempt (sdp_solver.py:27-107) per projection batch entry.
  * gX[K,Dp] and randv[nbatch,Z,Dp] (row-normalised, sdp_solver.py:48-49) in float64.  For every batch
  * entry: inprod = randv gX^T on the fp64 matrix cores, per-user slot preference order, the greedy

@@ -52,7 +52,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
            "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map",
            "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv", "mmw_factor_random",
-           "mmw_set_gap", "mmw_read_gap", "mmw_gap_checks"]
+           "mmw_set_gap", "mmw_read_gap", "mmw_gap_checks", "mmw_dense_gram", "mmw_dense_gemm", "mmw_dense_chol", "mmw_dense_orth"]
 
 
 class MMWError(RuntimeError):
@@ -104,6 +104,10 @@ def lib():
     L.mmw_factor_spectral.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
     L.mmw_factor_random.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_uint64]
     L.mmw_sym_eig.argtypes = [C.c_int, C.c_int32, p_f64, C.c_double, C.c_int32, p_f64, p_f64, C.POINTER(C.c_int32)]
+    L.mmw_dense_gram.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, p_f64, p_f64, C.c_int, p_f64]
+    L.mmw_dense_gemm.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, p_f64, C.c_int32, p_f64, p_f64]
+    L.mmw_dense_chol.argtypes = [C.c_int, C.c_int32, p_f64, p_f64, p_f64, p_f64, p_i32]
+    L.mmw_dense_orth.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, p_f64, C.c_double, p_f64, p_i32]
     L.mmw_expm_apply.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int32, C.c_int32, p_i32, p_i32, p_f64,
                                  p_f64, p_f64, p_f64, C.c_int32, p_f64]
     L.mmw_round.argtypes = [C.c_void_p, C.c_int32, C.c_int32, p_f64, C.c_int32, p_f64, p_i32, p_i32]
@@ -1612,6 +1616,56 @@ def sym_eig(G, rel_tol=1e-13, max_sweeps=30, device=0):
     sw = C.c_int32(0)
     check(lib().mmw_sym_eig(int(device), b, _pd(G), float(rel_tol), int(max_sweeps), _pd(theta), _pd(Q), C.byref(sw)))
     return theta, Q, sw.value
+
+
+def dense_gram(V, W, b, sym, dtype=F64, device=0):
+    """V[:, :b]^T W[:, :b] by the factor's Gram kernels (mmw_dense_gram); V, W are K x ld blocks, `sym` symmetrises."""
+    V, W = _f64(V), _f64(W)
+    if V.ndim != 2 or V.shape != W.shape:
+        raise ValueError("dense_gram: two K x ld blocks expected")
+    K, ld = V.shape
+    G = np.empty((max(int(b), 0), max(int(b), 0)), dtype=np.float64)
+    check(lib().mmw_dense_gram(int(device), int(dtype), K, int(b), ld, _pd(V), _pd(W), int(bool(sym)), _pd(G)))
+    return G
+
+
+def dense_gemm(V, Q, b, n, dtype=F64, device=0):
+    """V[:, :b] Q[:b, :n] by the factor's tall GEMM (mmw_dense_gemm), as a K x ld block whose other columns are zero."""
+    V, Q = _f64(V), _f64(Q)
+    if V.ndim != 2 or Q.ndim != 2 or Q.shape[0] != b:
+        raise ValueError("dense_gemm: a K x ld block and a b x ldq matrix expected")
+    K, ld = V.shape
+    out = np.empty((K, ld), dtype=np.float64)
+    check(lib().mmw_dense_gemm(int(device), int(dtype), K, int(b), int(n), ld, _pd(V), Q.shape[1], _pd(Q), _pd(out)))
+    return out
+
+
+def dense_chol(G, device=0):
+    """The Cholesky-QR's factorisation of a Gram matrix (mmw_dense_chol): (L of the unit-diagonal-scaled matrix, dscale, the
+    inverses of L's 32 x 32 diagonal blocks [ceil(b / 32), 32, 32], ok)."""
+    G = _f64(G)
+    b = G.shape[0]
+    if G.shape != (b, b):
+        raise ValueError("dense_chol: square matrix expected")
+    L = np.empty((b, b), dtype=np.float64)
+    dscale = np.empty(b, dtype=np.float64)
+    dinv = np.empty(((b + 31) // 32, 32, 32), dtype=np.float64)
+    ok = C.c_int32(0)
+    check(lib().mmw_dense_chol(int(device), b, _pd(G), _pd(L), _pd(dscale), _pd(dinv), C.byref(ok)))
+    return L, dscale, dinv, bool(ok.value)
+
+
+def dense_orth(V, b, dtype=F64, eps=1e-14, device=0):
+    """The factor's orthonormalisation of a K x ld block (mmw_dense_orth): (Q as a K x ld block, [what pass 1 did, what pass 2
+    did] with 0 Cholesky-QR, 1 Newton-Schulz, 2 eigen fallback)."""
+    V = _f64(V)
+    if V.ndim != 2:
+        raise ValueError("dense_orth: a K x ld block expected")
+    K, ld = V.shape
+    out = np.empty((K, ld), dtype=np.float64)
+    path = (C.c_int32 * 2)()
+    check(lib().mmw_dense_orth(int(device), int(dtype), K, int(b), ld, _pd(V), float(eps), _pd(out), path))
+    return out, [int(path[0]), int(path[1])]
 
 
 def expm_apply(A_csr, B, dtype=F64, method=EXPM_LANCZOS, max_order=12, tol=1e-9, device=0, reps=1):

@@ -271,7 +271,8 @@ template <typename T> struct Factorizer {
 
     // V <- V * F twice with F from the Gram matrix: Cholesky-QR (cheap) and, when the block is too
     // ill-conditioned for it, the eigen-based factor D Q Lambda^{-1/2}; columns orthonormal to rounding
-    int orthonormalise(int b, int ld, DevBuf<T>& A, DevBuf<T>& B, double eps) {
+    // path (may be null; a record only, mmw_dense_orth reads it): what each pass did -- 0 Cholesky-QR, 1 Newton-Schulz, 2 eigen fallback
+    int orthonormalise(int b, int ld, DevBuf<T>& A, DevBuf<T>& B, double eps, int* path = nullptr) {
         // tolerated deviation from the identity for the one-term form of the second pass: its result is off by 3/8 ||E||^2
         const double ns_max = sizeof(T) == 4 ? 1.6e-3 : 5e-7;
         for (int pass = 0; pass < 2; ++pass) {
@@ -288,16 +289,22 @@ template <typename T> struct Factorizer {
                     MMW_HIP(hipMemsetAsync(B.p, 0, (size_t)K * ld * sizeof(T), st));
                     MMW_TRY(dw.gemm(K, b, b, ld, A.p, dw.Q2.p, b, B.p));
                     std::swap(A.p, B.p);
+                    if (path) path[pass] = 1;
                     continue;
                 }
             }
             bool ok = false;
             MMW_TRY(dw.chol_factor(b, &ok));
+            if (path) path[pass] = ok ? 0 : 2;
             if (!ok) {
                 MMW_TRY(dw.gram(K, b, ld, A.p, A.p, true));  // the failed factorisation overwrote G
                 hipLaunchKernelGGL(k_scale_sym, dim3(grid_elems(b)), dim3(BLOCK), 0, st, b, dw.G.p, dw.dscale.p);
                 hipLaunchKernelGGL(k_apply_scale_sym, dim3(grid_elems((size_t)b * b)), dim3(BLOCK), 0, st, b, dw.G.p, dw.dscale.p);
-                MMW_TRY(dw.jacobi(b, 1e-14, 30));
+                // The eigensolve runs to rounding level, not to 1e-14: what it leaves off the diagonal is divided by the floor eps * b below,
+                // and a residual of the floor's own order (1e-14 sqrt(b) against 1e-14 b) left the directions under the floor coupled --
+                // max|Q^T Q - I| after the second pass was 10 to 130 times that of a LAPACK eigensolve on 32- and 33-column blocks of
+                // condition number 1e10 ... 1e14, and is within 2 times with this tolerance (test_hip_dense_blocks.py).
+                MMW_TRY(dw.jacobi(b, 1e-16, 30));
                 hipLaunchKernelGGL(k_orth_factor, dim3(grid_elems((size_t)b * b)), dim3(BLOCK), 0, st, b, dw.Q.p, dw.dscale.p, dw.diag.p, eps,
                                    (double)b, dw.Q2.p);
                 MMW_HIP(hipMemsetAsync(B.p, 0, (size_t)K * ld * sizeof(T), st));

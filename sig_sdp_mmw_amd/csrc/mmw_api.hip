@@ -4,6 +4,7 @@
 #include "batch_from_csr.h"
 #include "batch_from_env.h"
 #include "batch_handle.h"
+#include "dense_seams.h"
 #include "gm_handle.h"
 
 using namespace mmw;
@@ -179,6 +180,41 @@ int mmw_sym_eig(int device, int32_t b, const double* G, double rel_tol, int32_t 
         MMW_TRY(copy_d2h(Q, dw.Q.p, (size_t)b * b * sizeof(double), stream.s));
         if (sweeps) *sweeps = sw;
         return MMW_OK;
+    });
+}
+// ---- the factor's dense building blocks, one operation per call (dense_seams.h)
+int mmw_dense_gram(int device, int dtype, int32_t K, int32_t b, int32_t ld, const double* V, const double* W, int sym, double* G_out) {
+    return guarded("mmw_dense_gram", [&]() -> int {
+        if (!V || !W || !G_out) return fail(MMW_ERR_ARG, "mmw_dense_gram: null pointer");
+        MMW_TRY(dense_shape("mmw_dense_gram", K, b, ld));
+        return dense_call("mmw_dense_gram", device, dtype, [&](hipStream_t st) { return dense_gram_impl<float>(st, K, b, ld, V, W, sym != 0, G_out); },
+                          [&](hipStream_t st) { return dense_gram_impl<double>(st, K, b, ld, V, W, sym != 0, G_out); });
+    });
+}
+int mmw_dense_gemm(int device, int dtype, int32_t K, int32_t b, int32_t n, int32_t ld, const double* V, int32_t ldq, const double* Q, double* C_out) {
+    return guarded("mmw_dense_gemm", [&]() -> int {
+        if (!V || !Q || !C_out) return fail(MMW_ERR_ARG, "mmw_dense_gemm: null pointer");
+        MMW_TRY(dense_shape("mmw_dense_gemm", K, b, ld));
+        if (n < 1 || ldq < n) return fail(MMW_ERR_ARG, "mmw_dense_gemm: n must be >= 1 and ldq >= n");
+        if (n > ld) return fail(MMW_ERR_ARG, "mmw_dense_gemm: n must be <= ld (the product is stored with the block's row stride)");
+        return dense_call("mmw_dense_gemm", device, dtype, [&](hipStream_t st) { return dense_gemm_impl<float>(st, K, b, n, ld, V, ldq, Q, C_out); },
+                          [&](hipStream_t st) { return dense_gemm_impl<double>(st, K, b, n, ld, V, ldq, Q, C_out); });
+    });
+}
+int mmw_dense_chol(int device, int32_t b, const double* G, double* L_out, double* dscale_out, double* dinv_out, int32_t* ok) {
+    return guarded("mmw_dense_chol", [&]() -> int {
+        if (!G || !L_out || !dscale_out || !dinv_out || !ok) return fail(MMW_ERR_ARG, "mmw_dense_chol: null pointer");
+        if (b < 1 || b > 2048) return fail(MMW_ERR_ARG, "mmw_dense_chol: b must be in [1, 2048]");
+        auto run = [&](hipStream_t st) { return dense_chol_impl(st, b, G, L_out, dscale_out, dinv_out, ok); };
+        return dense_call("mmw_dense_chol", device, MMW_F64, run, run);
+    });
+}
+int mmw_dense_orth(int device, int dtype, int32_t K, int32_t b, int32_t ld, const double* V, double eps, double* Q_out, int32_t path_out[2]) {
+    return guarded("mmw_dense_orth", [&]() -> int {
+        if (!V || !Q_out || !path_out) return fail(MMW_ERR_ARG, "mmw_dense_orth: null pointer");
+        MMW_TRY(dense_shape("mmw_dense_orth", K, b, ld));
+        return dense_call("mmw_dense_orth", device, dtype, [&](hipStream_t st) { return dense_orth_impl<float>(st, K, b, ld, V, eps, Q_out, path_out); },
+                          [&](hipStream_t st) { return dense_orth_impl<double>(st, K, b, ld, V, eps, Q_out, path_out); });
     });
 }
 // ---- problem generator and scorer on the device (include/mmw_hip.h) ----------------------------------------

@@ -1,7 +1,7 @@
 // The library's MMW_* environment switches: one table, one lifetime.
 //
 // A switch is read ONCE, when its handle is created (mmw_create / mmw_create_from_env, before the blocking thread starts), or at the
-// entry of a handle-less call (mmw_expm_apply, mmw_sym_eig); the Switches value travels down by const reference and nothing re-reads
+// entry of a handle-less call (mmw_expm_apply, mmw_sym_eig, mmw_dense_*); the Switches value travels down by const reference and nothing re-reads
 // the environment afterwards.  The exceptions are the developer aids of `LiveSwitch` below, which act on a handle that already
 // exists and are read at the call.  No other file of csrc/ touches the environment.  (INTEGRATION.md documents every name.)
 #pragma once
