@@ -483,7 +483,10 @@ __global__ __launch_bounds__(BLOCK) void k_rownorm2(int K, int Dpad, const T* __
 }
 
 // ---- SDDMM on the edges: X[a,b] = <y_a, y_b> / tr for b > a, mirrored; diagonal d/tr; xavg += X ----
-template <typename T, int NCH>
+// POW2: LPR is a power of two (every row of at most 32 lanes, and 64).  Only then may a one-chunk row take the transposed
+// reduction below: lane_xor and group_sum take powers of two.  A row of 40, 48 or 56 lanes (G = 1, the lanes past LPR hold
+// zeros) is launched with POW2 = false and takes the wave sums; as an instantiation of its own it leaves the others' code alone
+template <typename T, int NCH, bool POW2 = true>
 __global__ __launch_bounds__(BLOCK) void k_sddmm(PatternDev<T> P, int Dpad, int LPR, int G, const T* __restrict__ Yb,
                                                  const T* __restrict__ d, const double* __restrict__ tr_part, int ntr,
                                                  T* __restrict__ xval, T* __restrict__ xavg, int accumulate) {
@@ -537,7 +540,7 @@ __global__ __launch_bounds__(BLOCK) void k_sddmm(PatternDev<T> P, int Dpad, int 
                 for (int c = 0; c < NCH; ++c)
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) s[u] += (double)ya[c][v] * (double)yb[u][c][v];
-            if (NCH == 1 && LPR >= 4) {
+            if (POW2 && NCH == 1 && LPR >= 4) {
                 // transposed reduction of the 4 partial sums over the LPR lanes of a group: two halving steps leave
                 // one edge per lane quarter (5 shuffles instead of 16), then the quarter is summed; the lane quarter
                 // (lig / (LPR/4)) of edge u ends up holding its total, so one store serves 4 edges per group

@@ -98,8 +98,8 @@ template <typename T> struct SolverLoop {
         PlanArgs pa;
         int ntr1 = 0;
     };
-    template <int NCH> void launch_sddmm(Core& co, const ChunkRun& c, int acc) {
-        hipLaunchKernelGGL((k_sddmm<T, NCH>), dim3(c.gr), dim3(BLOCK), 0, co.st, c.P, c.Dpad, co.eng.lay.LPR, co.eng.lay.G, co.Xh.p, drow.p, tr_part.p, c.gr, co.xval.p, co.xavg.p, acc);
+    template <int NCH, bool POW2 = true> void launch_sddmm(Core& co, const ChunkRun& c, int acc) {
+        hipLaunchKernelGGL((k_sddmm<T, NCH, POW2>), dim3(c.gr), dim3(BLOCK), 0, co.st, c.P, c.Dpad, co.eng.lay.LPR, co.eng.lay.G, co.Xh.p, drow.p, tr_part.p, c.gr, co.xval.p, co.xavg.p, acc);
     }
     template <int MT, int NB>
     int launch_sddmm_mfma(Core& co, const ChunkRun& c, dim3 grid, const SdMfmaDev& SM, const double* trp, int ntr, int acc, long long* rs_out, const long long* dfx,
@@ -365,7 +365,10 @@ template <typename T> struct SolverLoop {
                                ntiles, co.Xh.p, drow.p, tr_part.p, c.gr, co.xval.p, co.xavg.p, s.acc);
         } else
             switch (co.eng.lay.NCH) {
-                case 1: launch_sddmm<1>(co, c, s.acc); break;
+                case 1:
+                    if ((co.eng.lay.LPR & (co.eng.lay.LPR - 1)) == 0) launch_sddmm<1>(co, c, s.acc);
+                    else launch_sddmm<1, false>(co, c, s.acc);  // 40, 48, 56 lanes: no transposed reduction
+                    break;
                 case 2: launch_sddmm<2>(co, c, s.acc); break;
                 case 3: launch_sddmm<3>(co, c, s.acc); break;
                 default: launch_sddmm<4>(co, c, s.acc); break;
