@@ -547,6 +547,41 @@ int mmw_gm_run(mmw_gm* g, const double* key, int32_t Z, int32_t nattempt, int32_
  * greedy kernels.  z_out[K]: slot or -1 (the caller draws those, :197-198); *rem_out: users left over.
  */
 int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pref, int32_t* z_out, int32_t* rem_out);
+/*
+ * MAX_RAND.run (gm.py:131-200) with its random part made where the state lies (csrc/kernels_gm_rand.h): nothing is drawn, sorted or
+ * uploaded by the host.
+ *
+ * The draw, stated once.  For (seed, attempt) and the sizes (K, Z):
+ *   pref_val[k][z]  a standard normal per user k and slot z -- the reference's inprod[z, k] (gm.py:148) --, a K x Z block, user-major;
+ *   order_key[k]    a standard normal per user -- the argument of argsort(randn(K)) (gm.py:150) --, a K x 1 block.
+ * Both are Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) with the counter (row, column pair, attempt, TAG): row = k, a
+ * pair of pref_val holds the slots 2p and 2p + 1 (an odd Z discards the second normal of the last pair), order_key is the first
+ * normal of pair 0; TAG = 0x47525046 ("GRPF") for pref_val and 0x47524b59 ("GRKY") for order_key, apart from the sketch's 0x4d4d5753
+ * and the rounding's 0x524e4456.  The four words give the sketch's two uniforms u1 = ((w0 << 21 ^ w1 >> 11) + 1) 2^-53 in (0, 1] and
+ * u2 = (w2 + w3 2^-32) 2^-32 in [0, 1) and Box-Muller's pair sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).  Because these normals decide
+ * integers that a device -1 handle has to give too, ln, cos and sin are not a math library's but one fixed sequence of IEEE double
+ * additions, multiplications, one division and one square root, without contraction (gmr_normals, csrc/kernels_gm_rand.h): the same
+ * bits on the device and on the host, some 2 ulp from the exact functions.  A value depends on (seed, attempt, K, Z, k, z) and on
+ * nothing else: not on launch geometry, not on the batch's composition, not on `take`.
+ *   User order: ascending order_key, ties to the lower user index.
+ *   Preference of user k: descending pref_val[k][.], ties to the lower slot (the rule of the rounding's preference rows).
+ *
+ * mmw_gm_rand: attempts 0 ... nattempt - 1 of that draw, each through mmw_gm_assign's greedy (gm.py:152-193) for its own order and
+ * preference table, formed on the device by the rounding's rank and preference kernels; then one of them is picked on the device by
+ * mmw_round_attempts' two rules.  pick_rule 0: the first attempt that leaves nobody over, else the last.  pick_rule 1: the attempt
+ * with the fewest users left over, ties to the lower attempt.  z_out[K]: the picked attempt's slots, -1 for a user left over (the
+ * caller draws those, gm.py:196-198); rem_out[nattempt]: every attempt's count; *pick_out: the picked attempt.  The reference runs a
+ * single attempt: nattempt = 1 is the drop-in case.  K + nattempt + 1 integers cross to the host, nothing crosses to the device.
+ * Refused with MMW_ERR_ARG before anything is allocated or launched, each naming the value: Z < 1, nattempt outside [1, 256],
+ * pick_rule outside {0, 1}, a null output, Z > 4800 (mmw_round's bound: 32 Z bytes of LDS in the greedy kernel).
+ * device == -1: the same procedure as plain host C++, the draw through the host form of the same functions -- equal bit for bit.
+ * A handle built by mmw_gm_create_from_env answers exactly like one built from the host state.
+ *
+ * mmw_gm_rand_draw: the draw of ONE attempt copied out, pref_val_out[K*Z] (user-major) and order_key_out[K], either may be NULL: the
+ * seam for tests and for a host comparator, the counterpart of mmw_round_randv.  attempt >= 0; Z as above.
+ */
+int mmw_gm_rand(mmw_gm* g, int32_t Z, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out, int32_t* rem_out, int32_t* pick_out);
+int mmw_gm_rand_draw(mmw_gm* g, int32_t Z, uint64_t seed, int32_t attempt, double* pref_val_out, double* order_key_out);
 
 /*
  * Batched solver: B small independent fp64 instances, ONE workgroup per instance and `n` MMW iterations per launch
@@ -829,6 +864,26 @@ int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, 
                  int32_t* rem_out, double* key_out);
 int mmw_batch_factor_random(mmw_batch* b, const int32_t* take, const uint64_t* seeds);
 int mmw_batch_factor_spectral(mmw_batch* b, const int32_t* take, const int32_t* Z);
+/*
+ * mmw_batch_gm_rand: gm.MAX_RAND.run (gm.py:131-200) of every taking instance on the state the batch was built from, one launch, one
+ * workgroup per instance (csrc/kernels_batch_gm.h, k_batch_gm_rand).  Attempt a of instance b is the draw of mmw_gm_rand for
+ * (seeds[b], a) with the instance's (K, Z[b]) -- order keys, preference values, ascending order, descending preference, ties as stated
+ * there -- followed by the greedy pass mmw_batch_round runs (the same three checks, the same accumulation order): the slots and counts
+ * are bitwise those of mmw_gm_rand(seed = seeds[b]) on a handle of the same state, alone, among neighbours and under any `take`.
+ * take[B]: as in mmw_batch_round.  Z[B]: the slot count per instance; an instance with Z[b] <= 0 is left out like one with take[b] = 0
+ * (MAX_RAND has no not_Z_bound).  Attempts run one after another; stop_at_first != 0 ends an instance after its first attempt that
+ * leaves nobody over.  Outputs in mmw_batch_round's shapes: z_out, nattempt * K slots per instance that ran, instance after instance,
+ * attempt-major, -1 = left over (the caller draws those, gm.py:196-198), -2 = attempt not run; rem_out[B * nattempt] (-1: not run or
+ * left out); used_out[B]: attempts run.  The greedy pass reads the columns of Q_asso themselves, so mmw_batch_gm's
+ * clique condition is NOT needed here; the limits are K <= MMW_BATCH_EPILOGUE_MAX_K and Z[b] <= MMW_BATCH_EPILOGUE_MAX_K (one flag per
+ * slot in LDS).
+ * Refused by name with MMW_ERR_ARG before anything runs (outputs untouched): a null Z, seeds or output, nattempt outside [1, 4096],
+ * a running instance over either limit, a call in which no instance runs.  The arenas, the resident MMW fields and the resident
+ * factors stay bitwise as they were.  A host-only batch (device -1) answers with the same procedure as plain host C++.
+ * mmw_batch_env_gm_rand (declared with the environment below): the same on the state of the environment's last move.
+ */
+int mmw_batch_gm_rand(mmw_batch* b, const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
+                      int32_t* z_out, int32_t* rem_out, int32_t* used_out);
 
 /*
  * The generator and the scorer for many small instances (csrc/kernels_batch_env.h), one workgroup per instance: the state of
@@ -911,6 +966,9 @@ int mmw_batch_create_from_csr(mmw_batch** out, int32_t B, mmw_csr* const* csr, c
 /* mmw_batch_gm on the state of the environment's last move: see there */
 int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out,
                      int32_t* zz_out, int32_t* rem_out, double* key_out);
+/* mmw_batch_gm_rand on the state of the environment's last move: see there (MMW_ERR_STATE before the first move) */
+int mmw_batch_env_gm_rand(mmw_batch_env* e, const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first,
+                          const uint64_t* seeds, int32_t* z_out, int32_t* rem_out, int32_t* used_out);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ EXPORTS = ["mmw_last_error", "mmw_version", "mmw_device_count", "mmw_create", "m
            "mmw_batch_create_from_env", "mmw_batch_create_from_csr", "mmw_csr_upload", "mmw_csr_wrap", "mmw_csr_destroy", "mmw_csr_sizes", "mmw_csr_pointers", "mmw_csr_state",
            "mmw_csr_bounds", "mmw_create_from_csr", "mmw_factor_spectral", "mmw_env_move", "mmw_round_env", "mmw_gm_create_from_env", "mmw_gm_key", "mmw_carry", "mmw_carry_map",
            "mmw_round_attempts", "mmw_round_env_attempts", "mmw_round_randv", "mmw_factor_random",
+           "mmw_gm_rand", "mmw_gm_rand_draw", "mmw_batch_gm_rand", "mmw_batch_env_gm_rand",
            "mmw_set_gap", "mmw_read_gap", "mmw_gap_checks", "mmw_dense_gram", "mmw_dense_gemm", "mmw_dense_chol", "mmw_dense_orth"]
 
 
@@ -140,6 +141,8 @@ def lib():
     L.mmw_gm_pass.argtypes = [C.c_void_p, p_i32, C.c_int32, C.c_int32, p_i32, p_i32]
     L.mmw_gm_run.argtypes = [C.c_void_p, p_f64, C.c_int32, C.c_int32, p_i32, p_i32, p_i32]
     L.mmw_gm_assign.argtypes = [C.c_void_p, C.c_int32, p_i32, p_i32, p_i32, p_i32]
+    L.mmw_gm_rand.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int, p_i32, p_i32, p_i32]
+    L.mmw_gm_rand_draw.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, p_f64, p_f64]
     pp_i32 = C.POINTER(p_i32)
     pp_f64 = C.POINTER(p_f64)
     L.mmw_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, p_i32, p_i32, C.c_int32, C.c_double, p_i32,
@@ -179,6 +182,8 @@ def lib():
     L.mmw_batch_round_env.argtypes = [C.c_void_p, C.c_void_p, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
     L.mmw_batch_env_gm.argtypes = [C.c_void_p, C.c_int, p_i32, p_i32, C.c_int32, p_i32, p_i32, p_i32, p_f64]
+    L.mmw_batch_gm_rand.argtypes = [C.c_void_p, p_i32, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
+    L.mmw_batch_env_gm_rand.argtypes = [C.c_void_p, p_i32, p_i32, C.c_int32, C.c_int, C.POINTER(C.c_uint64), p_i32, p_i32, p_i32]
     L.mmw_batch_factor_random.argtypes = [C.c_void_p, p_i32, C.POINTER(C.c_uint64)]
     L.mmw_batch_factor_spectral.argtypes = [C.c_void_p, p_i32, p_i32]
     L.mmw_batch_create_from_env.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, p_i32, C.c_int32, C.c_double, p_i32]
@@ -240,6 +245,23 @@ def _gm_call(fn, handle, B, Ks, who, kind, Zs, nattempt, t, keys):
             ks[i] = kflat[o:o + Ks[i]]
         o += Ks[i]
     return (z, zz, rem, ks) if keys else (z, zz, rem)
+
+
+def _gm_rand_call(fn, handle, B, Ks, who, Zs, seeds, nattempt, t, stop_at_first):
+    """mmw_batch_gm_rand / mmw_batch_env_gm_rand in `BatchSolver.round`'s shapes: (z, rem, used) with z[i] None for an instance left
+    out (by `take` or by Z <= 0) or int32 (nattempt, K) with -1 = left over and -2 = attempt not run."""
+    Z = _i32(np.broadcast_to(np.asarray(Zs, dtype=np.int32), (B,)))
+    nattempt = int(nattempt)
+    ran = [i for i in who if Z[i] > 0]
+    zflat = np.empty(max(1, nattempt * sum(Ks[i] for i in ran)), dtype=np.int32)
+    rem = np.empty((B, max(1, nattempt)), dtype=np.int32)
+    used = np.empty(B, dtype=np.int32)
+    check(fn(handle, _opt_pi(t), _pi(Z), nattempt, 1 if stop_at_first else 0, _pu(_u64(seeds, B)), _pi(zflat), _pi(rem), _pi(used)))
+    z, o = [None] * B, 0
+    for i in ran:
+        z[i] = zflat[o:o + nattempt * Ks[i]].reshape(nattempt, Ks[i])
+        o += nattempt * Ks[i]
+    return z, rem, used
 
 
 def device_count():
@@ -1171,6 +1193,13 @@ class BatchSolver(_Handle):
         t, who = self._take(take)
         return _gm_call(lib().mmw_batch_gm, self._h, self.B, [s["K"] for s in self.sizes], who, kind, Zs, nattempt, t, keys)
 
+    def gm_rand(self, Zs, seeds, nattempt=1, take=None, stop_at_first=True):
+        """gm.MAX_RAND.run with its draws on the device for every taking instance's own state, one launch (mmw_batch_gm_rand):
+        attempt a of instance i is `GreedyHandle.rand`'s draw of (seeds[i], a).  Zs: the slot count, one for all or one per
+        instance; Z <= 0 leaves the instance out.  Returns (z, rem, used) in `round`'s shapes."""
+        t, who = self._take(take)
+        return _gm_rand_call(lib().mmw_batch_gm_rand, self._h, self.B, [s["K"] for s in self.sizes], who, Zs, seeds, nattempt, t, stop_at_first)
+
     def round_env(self, env, nattempt, seeds, take=None, stop_at_first=True):
         """`round` against the state a `BatchEnv` holds (the stations as they have moved) instead of the one the batch was built
         from: same factors, same draws, same greedy pass (mmw_batch_round_env).  Nothing of the batch changes."""
@@ -1343,6 +1372,14 @@ class BatchEnv(_Handle):
             raise MMWError("take: one flag per instance")
         who = [i for i in range(self.B) if t is None or t[i]]
         return _gm_call(lib().mmw_batch_env_gm, self._h, self.B, self.Ks, who, kind, Zs, nattempt, t, keys)
+
+    def gm_rand(self, Zs, seeds, nattempt=1, take=None, stop_at_first=True):
+        """`BatchSolver.gm_rand` on the states of the last `move` (mmw_batch_env_gm_rand); take: one flag per instance, None = all."""
+        t = None if take is None else _i32([1 if x else 0 for x in take])
+        if t is not None and t.size != self.B:
+            raise MMWError("take: one flag per instance")
+        who = [i for i in range(self.B) if t is None or t[i]]
+        return _gm_rand_call(lib().mmw_batch_env_gm_rand, self._h, self.B, self.Ks, who, Zs, seeds, nattempt, t, stop_at_first)
 
 
 _CSR_NAMES = ("S_indptr", "S_indices", "S_data", "Q_indptr", "Q_indices", "Q_data", "h_max")
@@ -1603,6 +1640,25 @@ class GreedyHandle(_Handle):
         rem = C.c_int32(0)
         check(lib().mmw_gm_assign(self._h, int(p.shape[1]), _pi(o), _pi(p), _pi(z), C.byref(rem)))
         return z, rem.value
+
+    def rand(self, Z, nattempt=1, seed=0, pick="first"):
+        """MAX_RAND with its draws made where the state lies (mmw_gm_rand): attempts 0 ... nattempt - 1 of the draw of `seed`
+        (include/mmw_hip.h states it), one picked on the device.  pick: "first" (the first attempt that leaves nobody over, else the
+        last) or "fewest" (the fewest users left over).  Returns (slot int32[K] with -1 = left over, rem int32[nattempt], picked)."""
+        if pick not in ("first", "fewest"):
+            raise ValueError("pick must be 'first' or 'fewest', got %r" % (pick,))
+        z = np.empty(self.K, dtype=np.int32)
+        rem = np.empty(max(1, int(nattempt)), dtype=np.int32)
+        got = C.c_int32(0)
+        check(lib().mmw_gm_rand(self._h, int(Z), int(nattempt), int(seed), 0 if pick == "first" else 1, _pi(z), _pi(rem), C.byref(got)))
+        return z, rem, got.value
+
+    def rand_draw(self, Z, seed, attempt):
+        """The draw of one attempt copied out (mmw_gm_rand_draw): (pref_val float64 (K, Z), order_key float64 (K,))."""
+        pv = np.empty((self.K, max(0, int(Z))), dtype=np.float64)
+        key = np.empty(self.K, dtype=np.float64)
+        check(lib().mmw_gm_rand_draw(self._h, int(Z), int(seed), int(attempt), _pd(pv), _pd(key)))
+        return pv, key
 
 
 def sym_eig(G, rel_tol=1e-13, max_sweeps=30, device=0):

@@ -466,6 +466,8 @@ def online_resolve_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, re
 
 METHODS = ("rand", "mgain", "masso")  # the baselines of sim_all_bler.py:42-72 that run inside the batch, in its order
 OPT_IN_METHODS = ("spectral",)  # what baselines_many also takes when it is named: spectral_sdp_solver (sdp_solver.py:165-185)
+DEVICE_DRAW_METHODS = ("mrand",)  # likewise: gm.MAX_RAND (gm.py:131-200) with its draws on the device (`gm_rand`); index 4 in the key scheme
+ALL_METHODS = METHODS + OPT_IN_METHODS + DEVICE_DRAW_METHODS
 
 
 def _fill(slot, rem, high, seed):
@@ -486,7 +488,9 @@ def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, natte
     left over are drawn from a generator keyed by the same seed.  The resident factors are replaced by "rand".
     methods may also name "spectral" (OPT_IN_METHODS; spectral_sdp_solver: `factor_spectral(Zs)` then `round`, keyed by
     probe_seed(seed, i, 0x40000 | 3)): the embedding is that of the states the batch was built from, also when the rounding goes
-    against an environment; it replaces the resident factors too.
+    against an environment; it replaces the resident factors too.  "mrand" (DEVICE_DRAW_METHODS; gm.MAX_RAND with its draws on the
+    device: `gm_rand`, one launch, `nattempt_gm` attempts of which the first that leaves nobody over counts, else the last, keyed by
+    probe_seed(seed, i, 0x40000 | 4)) touches no factor.
     Returns per instance {method: (z_vec float64[K], Z, remainder)}."""
     b, env = source if isinstance(source, tuple) else (source, None)
     B = b.B
@@ -495,9 +499,9 @@ def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, natte
         raise ValueError("baselines_many: one slot count per instance")
     out = [{} for _ in range(B)]
     for name in methods:
-        if name not in METHODS + OPT_IN_METHODS:
-            raise ValueError("baselines_many: method must be one of %s, got %r" % (METHODS + OPT_IN_METHODS, name))
-        m = (METHODS + OPT_IN_METHODS).index(name)
+        if name not in ALL_METHODS:
+            raise ValueError("baselines_many: method must be one of %s, got %r" % (ALL_METHODS, name))
+        m = ALL_METHODS.index(name)
         seeds = np.array([probe_seed(seed, i, 0x40000 | m) for i in range(B)], dtype=np.uint64)
         if name in ("rand", "spectral"):
             if any(b.sizes[i]["Z"] != Zs[i] for i in range(B)):
@@ -507,6 +511,10 @@ def baselines_many(source, Zs, methods=METHODS, seed=0, nattempt_round=10, natte
             else:
                 b.factor_spectral(Zs)
             z, rem, used = b.round(nattempt_round, seeds) if env is None else b.round_env(env, nattempt_round, seeds)
+            for i in range(B):
+                out[i][name] = _finish(z, rem, used, i, Zs[i], int(seeds[i]))
+        elif name == "mrand":
+            z, rem, used = (b if env is None else env).gm_rand(Zs, seeds, nattempt_gm)
             for i in range(B):
                 out[i][name] = _finish(z, rem, used, i, Zs[i], int(seeds[i]))
         else:
@@ -521,12 +529,17 @@ def _geometry(d):
 
 
 def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio=2, device=0, timings=None, split=None, factor_split=None, row_split=None, head_split=None,
-                 warm_start=False, warm_fraction=1.0 / 3.0):
+                 warm_start=False, warm_fraction=1.0 / 3.0, methods=METHODS):
     """sim_all_bler.py:30-72 for many instances (`graphs.mobile_drop`s or (sta_locs, ap_locs) pairs): the MMW search
     (`search_many(..., epilogue="batch")`) on the states a `BatchEnv` generates, the three baselines at each instance's Z_fin
     (`baselines_many`) and one `BatchEnv.evaluate` per method.  Returns per instance {"Z", "probes", "bler": {"mmw", "rand",
     "mgain", "masso"}}.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"}.  factor_split: workgroups per instance
-    for the search's factors (`BatchSolver.set_factor_split`).  warm_start / warm_fraction go to the search and nowhere else."""
+    for the search's factors (`BatchSolver.set_factor_split`).  warm_start / warm_fraction go to the search and nowhere else.  methods:
+    the baselines to run, METHODS or any of `baselines_many`'s names ("spectral", "mrand"); "bler" then holds "mmw" and these."""
+    methods = tuple(methods)
+    for name in methods:
+        if name not in ALL_METHODS:
+            raise ValueError("compare_many: method must be one of %s, got %r" % (ALL_METHODS, name))
     geo = [_geometry(d) for d in drops_or_geometries]
     B = len(geo)
     env = _lib.BatchEnv([g[1] for g in geo], [g[0].shape[0] for g in geo], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
@@ -540,10 +553,10 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         t1 = time.perf_counter()
         Zs = [int(r["Z"]) for r in found]
         b = _lib.BatchSolver(Zs, states, nit, eta, rank_radio=rank_radio, device=device)
-        base = baselines_many((b, env), Zs, seed=seed, nattempt_round=nattempt)
+        base = baselines_many((b, env), Zs, methods=methods, seed=seed, nattempt_round=nattempt)
         t2 = time.perf_counter()
         out = [{"Z": Zs[i], "probes": found[i]["probes"], "bler": {}} for i in range(B)]
-        for name, zs in [("mmw", [r["z_vec"] for r in found])] + [(m, [base[i][m][0] for i in range(B)]) for m in METHODS]:
+        for name, zs in [("mmw", [r["z_vec"] for r in found])] + [(m, [base[i][m][0] for i in range(B)]) for m in methods]:
             _, bler = env.evaluate(zs, Zs)
             for i in range(B):
                 out[i]["bler"][name] = bler[i]
@@ -556,14 +569,23 @@ def compare_many(drops_or_geometries, nit=150, eta=0.04, seed=0, nattempt=10, ra
         env.close()
 
 
-def online_greedy_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e4, seed=0, device=0, timings=None):
+def online_greedy_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, resolution_us=1e4, seed=0, device=0, timings=None, methods=("mgain",)):
     """The greedy arm of the reference's online comparison (sim_mmw_online_cmp_methods.py:79-88) for many `graphs.mobile_drop`s:
     MAX_GAIN.run(-1, not_Z_bound=True) once on the drops' states (`BatchEnv.move`, `BatchEnv.gm(0, Z <= 0)`; users left over drawn
     from [0, ZZ), keyed by probe_seed(seed, i, 0x40000 | 1)), then per time point the state where the stations are now (`move`),
     `evaluate` of that ONE colouring with Z = ZZ, and every drop walks `step_us` microseconds (one value or one per instance) in
     `resolution_us` steps.  The drops are moved in place.
     Returns per instance {"Z", "probes": [], "z_vec": [n_points, K], "remainder": [n_points], "bler": [n_points, K]} (the colouring
-    repeated per point: `online_many`'s shape); timings as there."""
+    repeated per point: `online_many`'s shape); timings as there.
+    methods: ("mgain",) is that arm alone.  Naming "mrand" beside it adds gm.MAX_RAND with its draws on the device
+    (`BatchEnv.gm_rand`, one attempt, keyed by probe_seed(seed, i, 0x40000 | 4)) once on the drops' states at the greedy's slot count
+    ZZ, scored at every point like the greedy's colouring: out[i]["mrand"] = {"z_vec", "remainder", "bler"} in the same shapes."""
+    methods = tuple(methods)
+    for name in methods:
+        if name not in ("mgain", "mrand"):
+            raise ValueError("online_greedy_many: method must be one of %s, got %r" % (("mgain", "mrand"), name))
+    if "mgain" not in methods:
+        raise ValueError("online_greedy_many: methods must name 'mgain' (its slot count is the one 'mrand' colours with), got %r" % (methods,))
     B = len(drops)
     steps = [float(x) for x in np.broadcast_to(np.asarray(step_us, dtype=np.float64), (B,))]
     env = _lib.BatchEnv([d.ap_locs for d in drops], [d.K for d in drops], min_sinr=min_sinr_dec(), noise_floor_dbm=_NOISE_FLOOR_DBM, device=device)
@@ -574,12 +596,25 @@ def online_greedy_many(drops, n_points=11, step_us=1e6, mob_spd_meter_s=0.1, res
         zv = [_fill(slot[i], rem[i], Zs[i], probe_seed(seed, i, 0x40000 | 1))[0] for i in range(B)]
         out = [{"Z": Zs[i], "probes": [], "z_vec": np.tile(zv[i], (n_points, 1)), "remainder": np.full(n_points, int(rem[i]), dtype=np.int64),
                 "bler": np.empty((n_points, drops[i].K))} for i in range(B)]
+        zr = None
+        if "mrand" in methods:
+            keys = np.array([probe_seed(seed, i, 0x40000 | ALL_METHODS.index("mrand")) for i in range(B)], dtype=np.uint64)
+            got = env.gm_rand(Zs, keys, 1)
+            fin = [_finish(*got, i, Zs[i], int(keys[i])) for i in range(B)]
+            zr = [f[0] for f in fin]
+            for i in range(B):
+                out[i]["mrand"] = {"z_vec": np.tile(zr[i], (n_points, 1)), "remainder": np.full(n_points, fin[i][2], dtype=np.int64),
+                                   "bler": np.empty((n_points, drops[i].K))}
         for p in range(n_points):
             t0 = time.perf_counter()
             env.move([d.sta_locs for d in drops])
             _, bler = env.evaluate(zv, Zs)
             for i in range(B):
                 out[i]["bler"][p] = bler[i]
+            if zr is not None:
+                _, bler = env.evaluate(zr, Zs)
+                for i in range(B):
+                    out[i]["mrand"]["bler"][p] = bler[i]
             t1 = time.perf_counter()
             for d, t in zip(drops, steps):
                 d.step_time(t, mob_spd_meter_s, resolution_us)

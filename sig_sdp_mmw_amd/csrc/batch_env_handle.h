@@ -190,6 +190,27 @@ struct mmw_batch_env {
         MMW_HIP(hipSetDevice(device));
         return gmw.run(st, B, tk, gd, ia.p, fa.p, ia.p, fa.p, z_out, zz_out, rem_out, key_out);
     }
+    // MAX_RAND with its draws on the device (k_batch_gm_rand) on the state of the last move
+    GmRandWork grw;
+    int gm_rand(const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out,
+                int32_t* used_out) {
+        const std::string who = "mmw_batch_env_gm_rand";
+        if (!moved) return fail(MMW_ERR_STATE, who + ": no positions yet (mmw_batch_env_move)");
+        MMW_TRY(batch_gm_rand_args(who, nattempt, Z, seeds, z_out, rem_out, used_out));
+        std::vector<int> tk, run;
+        MMW_TRY(batch_takers(who.c_str(), B, take, nullptr, tk));
+        MMW_TRY(batch_gm_rand_takers(who, tk, K.data(), Z, run));
+        std::vector<GmRandDesc> gd;
+        for (int b : run) {
+            GmRandDesc g{};
+            g.K = K[b]; g.Z = Z[b]; g.nattempt = nattempt; g.stop_first = stop_at_first != 0; g.seed = seeds[b];
+            set_lists(g, rlists[b]);
+            g.s_qidx = rlists[b].qidx;
+            gd.push_back(g);
+        }
+        MMW_HIP(hipSetDevice(device));
+        return grw.run(st, B, run, gd, nattempt, ia.p, fa.p, z_out, rem_out, used_out);
+    }
 };
 // mmw_batch_round_env: mmw_batch_round of the batch's resident factors against the state the environment holds
 inline int batch_round_env(mmw_batch* bt, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds,

@@ -107,4 +107,38 @@ struct BatchGm {
         }
         return gmw.run(c.st, c.B, tk, gd, epi.lists_i(c), epi.lists_f(c), gm_i.p, gm_f.p, z_out, zz_out, rem_out, key_out);
     }
+    // mmw_batch_gm_rand: MAX_RAND with its draws on the device (k_batch_gm_rand) on the state the batch was built from.  It reads the
+    // rounding's lists and works in buffers of its own: the arenas, the resident fields and the factors are not touched.
+    GmRandWork grw;
+    int rand(const BatchCore& c, BatchEpilogue& epi, const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
+             int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+        const std::string who = "mmw_batch_gm_rand";
+        MMW_TRY(batch_gm_rand_args(who, nattempt, Z, seeds, z_out, rem_out, used_out));
+        std::vector<int> tk, run, Ks(c.B);
+        MMW_TRY(c.takers(who.c_str(), take, tk));
+        for (int b = 0; b < c.B; ++b) Ks[b] = c.pat(b).K;
+        MMW_TRY(batch_gm_rand_takers(who, tk, Ks.data(), Z, run));
+        if (c.host_only) {
+            batch_gm_rand_blank(c.B, nattempt, rem_out, used_out);
+            for (int b : run) {
+                const GmState g = state(c, b);
+                std::vector<int32_t> rem(nattempt, -1);
+                used_out[b] = batch_gm_rand_host(g, Z[b], nattempt, stop_at_first, seeds[b], z_out, rem.data());
+                std::copy(rem.begin(), rem.end(), rem_out + (size_t)b * nattempt);
+                z_out += (size_t)nattempt * g.K;
+            }
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(c.device));
+        MMW_TRY(epi.round_lists(c));
+        std::vector<GmRandDesc> gd;
+        for (int b : run) {
+            GmRandDesc g{};
+            g.K = Ks[b]; g.Z = Z[b]; g.nattempt = nattempt; g.stop_first = stop_at_first != 0; g.seed = seeds[b];
+            set_lists(g, epi.rlists[b]);
+            g.s_qidx = epi.rlists[b].qidx;
+            gd.push_back(g);
+        }
+        return grw.run(c.st, c.B, run, gd, nattempt, epi.lists_i(c), epi.lists_f(c), z_out, rem_out, used_out);
+    }
 };

@@ -270,6 +270,10 @@ struct mmw_batch {
     int gm(int kind, const int32_t* take, const int32_t* Z, int32_t nattempt, int32_t* z_out, int32_t* zz_out, int32_t* rem_out, double* key_out) {
         return greedy.run(core, epi, kind, take, Z, nattempt, z_out, zz_out, rem_out, key_out);
     }
+    int gm_rand(const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds, int32_t* z_out, int32_t* rem_out,
+                int32_t* used_out) {
+        return greedy.rand(core, epi, take, Z, nattempt, stop_at_first, seeds, z_out, rem_out, used_out);
+    }
 };
 // mmw_batch_export: the instance's iterate into an fp64 handle of the same (state, Z), as if the handle had run those iterations.
 inline int batch_export_into(mmw_batch* bt, int b, Solver<double>* s) {

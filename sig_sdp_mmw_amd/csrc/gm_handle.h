@@ -1,5 +1,7 @@
 #pragma once
 #include "kernels_gm.h"
+#include "kernels_gm_rand.h"
+#include "kernels_round_draw.h"
 #include "pattern_device.h"
 #include "runtime.h"
 
@@ -16,6 +18,10 @@ struct mmw_gm {
     DevBuf<int> mark, owner;
     // MAX_RAND (the rounding's scheduled greedy, kernels_round.h)
     DevBuf<int> pref, gsched, gnsteps;
+    // MAX_RAND with its draws on the device (kernels_gm_rand.h): pref_val, {order_key, -order_key}, every attempt's slots and counts,
+    // the winner's slots, {pick, rem[pick]}
+    DevBuf<double> rpval, rkey;
+    DevBuf<int> rslot, rrem, rwin, rpick;
     DevBuf<unsigned> gmask;
     DevBuf<GreedyHdr> ghdr, ghdr_s;
     DevBuf<double> ggain;
@@ -184,27 +190,20 @@ struct mmw_gm {
         *rem_out = K - total;
         return MMW_OK;
     }
-    int assign(int32_t Z, const int32_t* order, const int32_t* pref_h, int32_t* z_out, int32_t* rem_out) {
+    // the launches of mmw_gm_assign from "ord[K] and pref[K][Z] are on the device" on: the rounding's scheduled greedy (solver_extras.h,
+    // Extras::round_chain) with this order and preference, one workgroup; slots to slot_d[K] (-1 = left over), the count to rem_d[0]
+    int greedy_buffers(int32_t Z) {
+        const size_t K = (size_t)S.K;
+        MMW_TRY(pref.alloc(K * Z)); MMW_TRY(ggain.alloc(K * Z)); MMW_TRY(ghdr.alloc(K));
+        MMW_TRY(gmask.alloc(K)); MMW_TRY(gsched.alloc(K * GB_WAVES)); MMW_TRY(gnsteps.alloc(1)); MMW_TRY(ghdr_s.alloc(K * GB_WAVES));
+        return MMW_OK;
+    }
+    int greedy_chain(int32_t Z, int* slot_d, int* rem_d) {
         const int K = S.K;
-        if (Z < 1) return fail(MMW_ERR_ARG, "gm: Z must be >= 1");
-        MMW_TRY(check_order(order, K, true));
-        for (size_t i = 0; i < (size_t)K * Z; ++i)
-            if (pref_h[i] < 0 || pref_h[i] >= Z) return fail(MMW_ERR_ARG, "gm: slot preference entry out of range");
-        if (device < 0) {
-            S.assign_host(Z, order, pref_h, z_out, rem_out);
-            return MMW_OK;
-        }
-        MMW_HIP(hipSetDevice(device));
         const size_t baseb = (size_t)GB_WAVES * Z * 4;
-        if (baseb > 150 * 1024) return fail(MMW_ERR_ARG, "gm: 32 Z bytes exceed the greedy kernel's LDS");
-        MMW_TRY(pref.alloc((size_t)K * Z)); MMW_TRY(ggain.alloc((size_t)K * Z)); MMW_TRY(ghdr.alloc(K));
-        MMW_TRY(gmask.alloc(K)); MMW_TRY(gsched.alloc((size_t)K * GB_WAVES)); MMW_TRY(gnsteps.alloc(1)); MMW_TRY(ghdr_s.alloc((size_t)K * GB_WAVES));
-        MMW_TRY(copy_h2d(ord.p, order, (size_t)K * sizeof(int), st));
-        MMW_TRY(copy_h2d(pref.p, pref_h, (size_t)K * Z * sizeof(int), st));
         MMW_HIP(hipMemsetAsync(ggain.p, 0, (size_t)K * Z * sizeof(double), st));
-        MMW_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)K * sizeof(int), st));
+        MMW_HIP(hipMemsetAsync(slot_d, 0xFF, (size_t)K * sizeof(int), st));
         MMW_HIP(hipMemsetAsync(gmask.p, 0, (size_t)K * sizeof(unsigned), st));
-        // the rounding's scheduled greedy (solver_extras.h, Extras::round) with this order and preference
         hipLaunchKernelGGL(k_greedy_headers, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, (const int*)ord.p, (const int*)so_indptr.p,
                            (const int*)q_indptr.p, (const double*)h_max.p, ghdr.p);
         const size_t pairs = (size_t)K * GS_W;
@@ -219,18 +218,122 @@ struct mmw_gm {
             MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_greedy_b<true, true>), (int)sh));
             hipLaunchKernelGGL((k_greedy_b<true, true>), dim3(1), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr,
                                (const int*)pref.p, (const int*)so_indices.p, (const double*)so_data.p, (const double*)so_hmax.p, (const int*)q_indices.p,
-                               ggain.p, slot.p, info.p, (const int*)gnsteps.p);
+                               ggain.p, slot_d, rem_d, (const int*)gnsteps.p);
         } else {
             MMW_TRY(set_max_lds(reinterpret_cast<const void*>(&k_greedy_b<false, true>), (int)sh));
             hipLaunchKernelGGL((k_greedy_b<false, true>), dim3(1), dim3(GB_WAVES * 64), sh, st, K, Z, (const GreedyHdr*)ghdr_s.p, (const int*)nullptr,
                                (const int*)pref.p, (const int*)so_indices.p, (const double*)so_data.p, (const double*)so_hmax.p, (const int*)q_indices.p,
-                               ggain.p, slot.p, info.p, (const int*)gnsteps.p);
+                               ggain.p, slot_d, rem_d, (const int*)gnsteps.p);
         }
         MMW_HIP(hipGetLastError());
+        return MMW_OK;
+    }
+    int assign(int32_t Z, const int32_t* order, const int32_t* pref_h, int32_t* z_out, int32_t* rem_out) {
+        const int K = S.K;
+        if (Z < 1) return fail(MMW_ERR_ARG, "gm: Z must be >= 1");
+        MMW_TRY(check_order(order, K, true));
+        for (size_t i = 0; i < (size_t)K * Z; ++i)
+            if (pref_h[i] < 0 || pref_h[i] >= Z) return fail(MMW_ERR_ARG, "gm: slot preference entry out of range");
+        if (device < 0) {
+            S.assign_host(Z, order, pref_h, z_out, rem_out);
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        if ((size_t)GB_WAVES * Z * 4 > 150 * 1024) return fail(MMW_ERR_ARG, "gm: 32 Z bytes exceed the greedy kernel's LDS");
+        MMW_TRY(greedy_buffers(Z));
+        MMW_TRY(copy_h2d(ord.p, order, (size_t)K * sizeof(int), st));
+        MMW_TRY(copy_h2d(pref.p, pref_h, (size_t)K * Z * sizeof(int), st));
+        MMW_TRY(greedy_chain(Z, slot.p, info.p));
         MMW_TRY(copy_d2h(z_out, slot.p, (size_t)K * sizeof(int), st));
         int rem = 0;
         MMW_TRY(copy_d2h(&rem, info.p, sizeof(int), st));
         *rem_out = rem;
+        return MMW_OK;
+    }
+    // ---- mmw_gm_rand / mmw_gm_rand_draw: MAX_RAND with the draws of kernels_gm_rand.h made where the state lies.  Every attempt has its
+    // own user order, hence its own schedule: the attempts run one after another on the stream, each as draw -> rank -> preference ->
+    // mmw_gm_assign's chain, and k_round_pick chooses among their counts.  Nothing crosses to the device; K + nattempt + 1 integers cross back.
+    static int rand_check(const std::string& who, int32_t Z, int32_t nattempt, int pick_rule, const void* z_out, const void* rem_out, const void* pick_out) {
+        if (Z < 1) return fail(MMW_ERR_ARG, who + ": Z = " + std::to_string(Z) + " must be >= 1");
+        if (nattempt < 1 || nattempt > ROUND_MAX_ATTEMPTS)
+            return fail(MMW_ERR_ARG, who + ": nattempt = " + std::to_string(nattempt) + " must be in [1, " + std::to_string(ROUND_MAX_ATTEMPTS) + "]");
+        if (pick_rule != 0 && pick_rule != 1)
+            return fail(MMW_ERR_ARG, who + ": pick_rule = " + std::to_string(pick_rule) + " must be 0 (the first feasible attempt, else the last) or 1 (the fewest users left over)");
+        if (!z_out || !rem_out || !pick_out) return fail(MMW_ERR_ARG, who + ": null pointer");
+        if ((size_t)GB_WAVES * Z * 4 > 150 * 1024) return fail(MMW_ERR_ARG, who + ": Z = " + std::to_string(Z) + ": 32 Z bytes exceed the greedy kernel's LDS");
+        return MMW_OK;
+    }
+    // attempt `a`'s draw, order and preference table on the device: rpval, rkey, ord and pref hold them afterwards
+    int rand_tables(int32_t Z, uint64_t seed, uint32_t a) {
+        const int K = S.K;
+        hipLaunchKernelGGL(k_gm_rand_key, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, seed, a, rkey.p, rkey.p + K);
+        hipLaunchKernelGGL(k_rank_count, dim3((K + BLOCK - 1) / BLOCK, RANK_SPLIT), dim3(BLOCK), 0, st, K, (const double*)(rkey.p + K), rank_part.p);
+        hipLaunchKernelGGL(k_rank_scatter, dim3((K + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, K, (const int*)rank_part.p, ord.p);
+        hipLaunchKernelGGL(k_gm_rand_pref, dim3(grid_elems((size_t)K * ((Z + 1) / 2))), dim3(BLOCK), 0, st, K, Z, seed, a, rpval.p);
+        hipLaunchKernelGGL(k_slot_pref, dim3(K, 1), dim3(BLOCK), (size_t)Z * sizeof(double), st, K, Z, (const double*)rpval.p, pref.p);
+        MMW_HIP(hipGetLastError());
+        return MMW_OK;
+    }
+    int rand(int32_t Z, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out, int32_t* rem_out, int32_t* pick_out) {
+        MMW_TRY(rand_check("mmw_gm_rand", Z, nattempt, pick_rule, z_out, rem_out, pick_out));
+        const int K = S.K;
+        if (K > ROUND_PICK_MAX_K) return fail(MMW_ERR_ARG, "mmw_gm_rand: K = " + std::to_string(K) + " exceeds the pick's limit " + std::to_string(ROUND_PICK_MAX_K));
+        if (device < 0) {
+            std::vector<double> pv((size_t)K * Z), key(K);
+            std::vector<int32_t> order(K), prf((size_t)K * Z), slots((size_t)nattempt * K);
+            for (int a = 0; a < nattempt; ++a) {
+                gm_rand_draw_host(K, Z, seed, (uint32_t)a, pv.data(), key.data());
+                gm_rand_order_host(K, Z, pv.data(), key.data(), order.data(), prf.data());
+                S.assign_host(Z, order.data(), prf.data(), slots.data() + (size_t)a * K, rem_out + a);
+            }
+            const int pick = gm_rand_pick_host(rem_out, nattempt, pick_rule);
+            std::copy(slots.begin() + (size_t)pick * K, slots.begin() + (size_t)(pick + 1) * K, z_out);
+            *pick_out = pick;
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        MMW_TRY(greedy_buffers(Z));
+        MMW_TRY(rpval.alloc((size_t)K * Z)); MMW_TRY(rkey.alloc((size_t)2 * K)); MMW_TRY(rank_part.alloc((size_t)RANK_SPLIT * K));
+        MMW_TRY(rslot.alloc((size_t)nattempt * K)); MMW_TRY(rrem.alloc(nattempt)); MMW_TRY(rwin.alloc(K)); MMW_TRY(rpick.alloc(2));
+        for (int a = 0; a < nattempt; ++a) {
+            MMW_TRY(rand_tables(Z, seed, (uint32_t)a));
+            MMW_TRY(greedy_chain(Z, rslot.p + (size_t)a * K, rrem.p + a));
+        }
+        hipLaunchKernelGGL(k_round_pick, dim3((unsigned)((K + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, K, nattempt, pick_rule, (const int*)rrem.p, (const int*)rslot.p,
+                           rwin.p, rpick.p);
+        MMW_HIP(hipGetLastError());
+        std::vector<int32_t> back((size_t)K + nattempt + 1);
+        MMW_HIP(hipMemcpyAsync(back.data(), rwin.p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipMemcpyAsync(back.data() + K, rrem.p, (size_t)nattempt * sizeof(int), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipMemcpyAsync(back.data() + K + nattempt, rpick.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        MMW_HIP(hipStreamSynchronize(st));
+        std::copy(back.begin(), back.begin() + K, z_out);
+        std::copy(back.begin() + K, back.begin() + K + nattempt, rem_out);
+        *pick_out = back[(size_t)K + nattempt];
+        return MMW_OK;
+    }
+    int rand_draw(int32_t Z, uint64_t seed, int32_t attempt, double* pref_val_out, double* order_key_out) {
+        if (Z < 1) return fail(MMW_ERR_ARG, "mmw_gm_rand_draw: Z = " + std::to_string(Z) + " must be >= 1");
+        if (attempt < 0) return fail(MMW_ERR_ARG, "mmw_gm_rand_draw: attempt = " + std::to_string(attempt) + " must be >= 0");
+        if ((size_t)GB_WAVES * Z * 4 > 150 * 1024) return fail(MMW_ERR_ARG, "mmw_gm_rand_draw: Z = " + std::to_string(Z) + ": 32 Z bytes exceed the greedy kernel's LDS");
+        const int K = S.K;
+        if (device < 0) {
+            gm_rand_draw_host(K, Z, seed, (uint32_t)attempt, pref_val_out, order_key_out);
+            return MMW_OK;
+        }
+        MMW_HIP(hipSetDevice(device));
+        if (order_key_out) {
+            MMW_TRY(rkey.alloc((size_t)2 * K));
+            hipLaunchKernelGGL(k_gm_rand_key, dim3(grid_elems((size_t)K)), dim3(BLOCK), 0, st, K, seed, (uint32_t)attempt, rkey.p, rkey.p + K);
+            MMW_HIP(hipGetLastError());
+            MMW_TRY(copy_d2h(order_key_out, rkey.p, (size_t)K * sizeof(double), st));
+        }
+        if (pref_val_out) {
+            MMW_TRY(rpval.alloc((size_t)K * Z));
+            hipLaunchKernelGGL(k_gm_rand_pref, dim3(grid_elems((size_t)K * ((Z + 1) / 2))), dim3(BLOCK), 0, st, K, Z, seed, (uint32_t)attempt, rpval.p);
+            MMW_HIP(hipGetLastError());
+            MMW_TRY(copy_d2h(pref_val_out, rpval.p, (size_t)K * Z * sizeof(double), st));
+        }
         return MMW_OK;
     }
 };

@@ -29,6 +29,7 @@
 #pragma once
 #include "kernels_batch_epilogue.h"
 #include "kernels_gm.h"
+#include "kernels_gm_rand.h"
 
 namespace mmw {
 
@@ -243,5 +244,214 @@ struct GmWork {
         return MMW_OK;
     }
 };
+
+// ---- MAX_RAND.run (gm.py:131-200) with its draws on the device, for many instances in one launch (mmw_batch_gm_rand) -----------------
+// One workgroup per taking instance; per attempt a: the users' order keys of (seed, a) into LDS and their ascending rank (ties to the
+// lower user), the K x Z preference values into the work arena (kernels_gm_rand.h: the draw mmw_gm_rand makes, value by value), the
+// preference rows by k_slot_pref's rule, then the rounding's greedy pass -- a COPY of k_batch_round's (kernels_batch_epilogue.h), which
+// stays as it is: the first wave, one user per step, the same three checks (a) the sum accumulated at k within h_max[k], (b) k's row
+// keeps every member of the slot that k reaches within its h_max, (c) no member of the slot in k's Q row, and one add per address and
+// user in assignment order.  (c) reads the columns of Q themselves: nothing assumes that Q is a union of cliques, so mmw_batch_gm's
+// clique condition does not apply here.  Limits: K <= MMW_BATCH_EPILOGUE_MAX_K, Z <= BGMR_MAX_Z (one flag per slot in LDS).
+constexpr int BGMR_MAX_Z = EPI_MAX_K;
+
+struct GmRandDesc {
+    int K, Z, nattempt, stop_first;
+    uint64_t seed;
+    int64_t s_soptr, s_soidx, s_qptr, s_qidx;  // int32 lists of the state: S_gain without its diagonal, Q_asso
+    int64_t s_sodata, s_sohmax, s_hmax;        // fp64 lists: the gains, h_max of the receiving user, h_max
+    int64_t r_pval, r_gain;                    // fp64 work: K x Z each
+    int64_t r_pref, r_z, r_rem;                // int32 work: K x Z; results: nattempt x K, nattempt + 1 (the last: attempts run)
+};
+
+__global__ __launch_bounds__(BATCH_THREADS) void k_batch_gm_rand(const GmRandDesc* __restrict__ descs, const int* __restrict__ si,
+                                                                 const double* __restrict__ sf, double* rw, int* ri) {
+    const GmRandDesc d = descs[blockIdx.x];
+    __shared__ double key[EPI_MAX_K];
+    __shared__ int order[EPI_MAX_K], slot_l[EPI_MAX_K], bad[BGMR_MAX_Z];
+    __shared__ int s_rem;
+    const int tid = (int)threadIdx.x, NT = (int)blockDim.x, lane = tid & 63, wv = tid >> 6;
+    const int K = d.K, Z = d.Z, npair = (Z + 1) >> 1;
+    const int* __restrict__ soptr = si + d.s_soptr;
+    const int* __restrict__ soidx = si + d.s_soidx;
+    const int* __restrict__ qptr = si + d.s_qptr;
+    const int* __restrict__ qidx = si + d.s_qidx;
+    const double* __restrict__ sodata = sf + d.s_sodata;
+    const double* __restrict__ sohmax = sf + d.s_sohmax;
+    const double* __restrict__ hmax = sf + d.s_hmax;
+    double* pv = rw + d.r_pval;
+    double* gain = rw + d.r_gain;
+    int* pref = ri + d.r_pref;
+    int* zout = ri + d.r_z;
+    int* rem = ri + d.r_rem;
+    const size_t KZ = (size_t)K * Z;
+    for (size_t i = tid; i < (size_t)d.nattempt * K; i += NT) zout[i] = -2;  // attempts not run
+    for (int a = tid; a < d.nattempt; a += NT) rem[a] = -1;
+    int used = 0;
+    for (int a = 0; a < d.nattempt; ++a) {
+        // ---- the draw of (seed, a); the sums start empty
+        for (int k = tid; k < K; k += NT) {
+            key[k] = gmr_order_key(k, d.seed, (uint32_t)a);
+            slot_l[k] = -1;
+        }
+        for (size_t i = tid; i < (size_t)K * npair; i += NT) {
+            const int k = (int)(i / npair), p = (int)(i % npair);
+            double v0, v1;
+            gmr_pref_pair(k, p, d.seed, (uint32_t)a, v0, v1);
+            pv[(size_t)k * Z + 2 * p] = v0;
+            if (2 * p + 1 < Z) pv[(size_t)k * Z + 2 * p + 1] = v1;
+        }
+        for (size_t idx = tid; idx < KZ; idx += NT) gain[idx] = 0.0;
+        __syncthreads();  // (also: the last attempt's slots are copied out)
+        // ---- the visiting order: ascending order key (argsort(randn(K)), gm.py:150), ties to the lower user
+        for (int k = tid; k < K; k += NT) {
+            const double mine = key[k];
+            int r = 0;
+            for (int j = 0; j < K; ++j) {
+                const double o = key[j];
+                r += (o < mine) || (o == mine && j < k);
+            }
+            order[r] = k;
+        }
+        // ---- preference order per user (gm.py:149): descending value, ties to the lower slot
+        for (size_t idx = tid; idx < KZ; idx += NT) {
+            const int k = (int)(idx / Z), z = (int)(idx % Z);
+            const double* row = pv + (size_t)k * Z;
+            const double mine = row[z];
+            int r = 0;
+            for (int j = 0; j < Z; ++j) r += (row[j] > mine) || (row[j] == mine && j < z);
+            pref[(size_t)k * Z + r] = z;
+        }
+        __syncthreads();
+        // ---- the greedy pass (gm.py:158-193 = sdp_solver.py:70-101), as k_batch_round runs it
+        if (wv == 0) {
+            int un = 0;
+            for (int kk = 0; kk < K; ++kk) {
+                const int k = order[kk];
+                const int sb = soptr[k], deg = soptr[k + 1] - sb, qb = qptr[k], qdeg = qptr[k + 1] - qb;
+                const double hk = hmax[k];
+                for (int z = lane; z < Z; z += WAVE) bad[z] = gain[(size_t)k * Z + z] > hk ? 1 : 0;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                for (int e = lane; e < deg; e += WAVE) {
+                    const int nb = soidx[sb + e];
+                    const int zn = slot_l[nb];
+                    if (zn >= 0 && gain[(size_t)nb * Z + zn] + sodata[sb + e] > sohmax[sb + e]) bad[zn] = 1;
+                }
+                for (int e = lane; e < qdeg; e += WAVE) {
+                    const int zn = slot_l[qidx[qb + e]];
+                    if (zn >= 0) bad[zn] = 1;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                int z_take = -1;
+                for (int z0 = 0; z0 < Z && z_take < 0; z0 += WAVE) {
+                    const int zz = z0 + lane;
+                    const int pz = zz < Z ? pref[(size_t)k * Z + zz] : 0;
+                    const bool ok = zz < Z && !bad[pz];
+                    const unsigned long long mk = __ballot(ok);
+                    if (mk) z_take = __shfl(pz, (int)__builtin_ctzll(mk));
+                }
+                if (z_take >= 0) {
+                    for (int e = lane; e < deg; e += WAVE) gain[(size_t)soidx[sb + e] * Z + z_take] += sodata[sb + e];
+                    if (lane == 0) slot_l[k] = z_take;
+                } else {
+                    ++un;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the sums and the slot are written before the next user reads them
+                __builtin_amdgcn_wave_barrier();
+            }
+            if (lane == 0) { s_rem = un; rem[a] = un; }
+        }
+        __syncthreads();
+        for (int k = tid; k < K; k += NT) zout[(size_t)a * K + k] = slot_l[k];
+        used = a + 1;
+        const bool done = d.stop_first && s_rem == 0;  // (workgroup-uniform: read from LDS after the barrier)
+        __syncthreads();                               // everybody has read s_rem and slot_l before the next attempt writes them
+        if (done) break;
+    }
+    if (tid == 0) rem[d.nattempt] = used;
+}
+
+// ---- the host side both handles share, in mmw_batch_round's output shapes: z_out nattempt * K slots per taking instance, attempt-major
+// (-1 left over, -2 attempt not run), rem_out[B * nattempt] (-1: not run), used_out[B]
+inline int batch_gm_rand_args(const std::string& who, int32_t nattempt, const void* Z, const void* seeds, const void* z_out, const void* rem_out, const void* used_out) {
+    if (!Z || !seeds || !z_out || !rem_out || !used_out) return fail(MMW_ERR_ARG, who + ": null pointer");
+    if (nattempt < 1 || nattempt > 4096) return fail(MMW_ERR_ARG, who + ": nattempt = " + std::to_string(nattempt) + " must be in [1, 4096]");
+    return MMW_OK;
+}
+// the instances of `tk` that run: Z[b] > 0 (Z[b] <= 0 leaves an instance out, as a zero in `take` does); K and Z are refused by name
+inline int batch_gm_rand_takers(const std::string& who, const std::vector<int>& tk, const int* K, const int32_t* Z, std::vector<int>& run) {
+    run.clear();
+    for (int b : tk) {
+        if (Z[b] <= 0) continue;
+        const std::string inst = who + ": instance " + std::to_string(b);
+        if (K[b] > EPI_MAX_K) return fail(MMW_ERR_ARG, inst + ": K = " + std::to_string(K[b]) + " exceeds the limit " + std::to_string(EPI_MAX_K) + " (it stays on a GreedyHandle)");
+        if (Z[b] > BGMR_MAX_Z) return fail(MMW_ERR_ARG, inst + ": Z = " + std::to_string(Z[b]) + " exceeds the limit " + std::to_string(BGMR_MAX_Z) + " (it stays on a GreedyHandle)");
+        run.push_back(b);
+    }
+    if (run.empty()) return fail(MMW_ERR_ARG, who + ": no instance takes part");
+    return MMW_OK;
+}
+inline void batch_gm_rand_blank(int B, int32_t nattempt, int32_t* rem_out, int32_t* used_out) {
+    for (int b = 0; b < B; ++b) {
+        used_out[b] = 0;
+        for (int a = 0; a < nattempt; ++a) rem_out[(size_t)b * nattempt + a] = -1;
+    }
+}
+struct GmRandWork {
+    DevBuf<GmRandDesc> d_desc;
+    DevBuf<double> rw;
+    DevBuf<int> ri;
+    // gd: one descriptor per running instance run[t] with its sizes, seed and list offsets set; the work offsets are laid out here
+    int run(hipStream_t st, int B, const std::vector<int>& run, std::vector<GmRandDesc>& gd, int32_t nattempt, const int* si, const double* sf,
+            int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+        int64_t of = 0, oz = 0;
+        for (GmRandDesc& g : gd) { g.r_z = oz; oz += (int64_t)nattempt * g.K; g.r_rem = oz; oz += nattempt + 1; }  // what goes back, in front
+        const int64_t nback = oz;
+        int64_t oi = a32(oz);
+        for (GmRandDesc& g : gd) {
+            const int64_t KZ = (int64_t)g.K * g.Z;
+            g.r_pval = of; of = a32(of + KZ);
+            g.r_gain = of; of = a32(of + KZ);
+            g.r_pref = oi; oi = a32(oi + KZ);
+        }
+        MMW_TRY(rw.alloc((size_t)of));
+        MMW_TRY(ri.alloc((size_t)oi));
+        MMW_TRY(d_desc.alloc(gd.size()));
+        MMW_TRY(copy_h2d(d_desc.p, gd.data(), gd.size() * sizeof(GmRandDesc), st));
+        hipLaunchKernelGGL(k_batch_gm_rand, dim3((unsigned)gd.size()), dim3(BATCH_THREADS), 0, st, d_desc.p, si, sf, rw.p, ri.p);
+        MMW_HIP(hipGetLastError());
+        std::vector<int> host((size_t)nback);
+        MMW_TRY(copy_d2h(host.data(), ri.p, host.size() * sizeof(int), st));
+        batch_gm_rand_blank(B, nattempt, rem_out, used_out);
+        int32_t* z = z_out;
+        for (size_t t = 0; t < run.size(); ++t) {
+            const GmRandDesc& g = gd[t];
+            const size_t nz = (size_t)nattempt * g.K;
+            std::copy(host.begin() + g.r_z, host.begin() + g.r_z + nz, z);
+            z += nz;
+            std::copy(host.begin() + g.r_rem, host.begin() + g.r_rem + nattempt, rem_out + (size_t)run[t] * nattempt);
+            used_out[run[t]] = host[g.r_rem + nattempt];
+        }
+        return MMW_OK;
+    }
+};
+// the plain C++ form of one instance (a host-only batch): z[nattempt * K], rem[nattempt], returns the attempts run
+inline int batch_gm_rand_host(const GmState& g, int32_t Z, int32_t nattempt, int stop_first, uint64_t seed, int32_t* z, int32_t* rem) {
+    const int K = g.K;
+    std::vector<double> pv((size_t)K * Z), key(K);
+    std::vector<int32_t> order(K), prf((size_t)K * Z);
+    std::fill(z, z + (size_t)nattempt * K, -2);
+    int used = 0;
+    for (int a = 0; a < nattempt; ++a) {
+        gm_rand_draw_host(K, Z, seed, (uint32_t)a, pv.data(), key.data());
+        gm_rand_order_host(K, Z, pv.data(), key.data(), order.data(), prf.data());
+        g.assign_host(Z, order.data(), prf.data(), z + (size_t)a * K, rem + a);
+        used = a + 1;
+        if (stop_first && rem[a] == 0) break;
+    }
+    return used;
+}
 
 }  // namespace mmw

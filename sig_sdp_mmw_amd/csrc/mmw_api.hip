@@ -307,6 +307,12 @@ int mmw_gm_run(mmw_gm* g, const double* key, int32_t Z, int32_t nattempt, int32_
 int mmw_gm_assign(mmw_gm* g, int32_t Z, const int32_t* order, const int32_t* pref, int32_t* z_out, int32_t* rem_out) {
     return entry("mmw_gm_assign", !g || !order || !pref || !z_out || !rem_out, "mmw_gm_assign: null pointer", [&] { return g->assign(Z, order, pref, z_out, rem_out); });
 }
+int mmw_gm_rand(mmw_gm* g, int32_t Z, int32_t nattempt, uint64_t seed, int pick_rule, int32_t* z_out, int32_t* rem_out, int32_t* pick_out) {
+    return entry("mmw_gm_rand", !g, "mmw_gm_rand: null pointer", [&] { return g->rand(Z, nattempt, seed, pick_rule, z_out, rem_out, pick_out); });
+}
+int mmw_gm_rand_draw(mmw_gm* g, int32_t Z, uint64_t seed, int32_t attempt, double* pref_val_out, double* order_key_out) {
+    return entry("mmw_gm_rand_draw", !g, "mmw_gm_rand_draw: null pointer", [&] { return g->rand_draw(Z, seed, attempt, pref_val_out, order_key_out); });
+}
 // ---- the batched solver (batch_handle.h): its entries report an exception under the handle's name, "mmw_batch"
 int mmw_batch_create(mmw_batch** out, int device, int32_t B, const int32_t* K, const int32_t* Z, int32_t rank_radio, double eta,
                      const int32_t* nit, const int32_t* const* S_indptr, const int32_t* const* S_indices, const double* const* S_data,
@@ -379,6 +385,10 @@ int mmw_batch_gm(mmw_batch* b, int kind, const int32_t* take, const int32_t* Z, 
     return entry("mmw_batch", !b || !Z || !z_out || !zz_out || !rem_out, "null pointer",
                  [&] { return b->gm(kind, take, Z, nattempt, z_out, zz_out, rem_out, key_out); });
 }
+int mmw_batch_gm_rand(mmw_batch* b, const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
+                      int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+    return entry("mmw_batch", !b, "mmw_batch_gm_rand: null pointer", [&] { return b->gm_rand(take, Z, nattempt, stop_at_first, seeds, z_out, rem_out, used_out); });
+}
 // ---- the batched generator and scorer (batch_env_handle.h): the online sweeps' state per time point
 int mmw_batch_env_create(mmw_batch_env** out, int device, int32_t B, const int32_t* K, const int32_t* A, const double* const* ap_xy, double fre_Hz,
                          double txp_offset, double min_s_n_ratio, double min_sinr, double noise_floor_dbm) {
@@ -450,6 +460,10 @@ int mmw_batch_env_gm(mmw_batch_env* e, int kind, const int32_t* take, const int3
                      int32_t* rem_out, double* key_out) {
     return entry("mmw_batch_env", !e || !Z || !z_out || !zz_out || !rem_out, "null pointer",
                  [&] { return e->gm(kind, take, Z, nattempt, z_out, zz_out, rem_out, key_out); });
+}
+int mmw_batch_env_gm_rand(mmw_batch_env* e, const int32_t* take, const int32_t* Z, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
+                          int32_t* z_out, int32_t* rem_out, int32_t* used_out) {
+    return entry("mmw_batch_env", !e, "mmw_batch_env_gm_rand: null pointer", [&] { return e->gm_rand(take, Z, nattempt, stop_at_first, seeds, z_out, rem_out, used_out); });
 }
 int mmw_batch_round_env(mmw_batch* b, mmw_batch_env* e, const int32_t* take, int32_t nattempt, int stop_at_first, const uint64_t* seeds,
                         int32_t* z_out, int32_t* rem_out, int32_t* used_out) {

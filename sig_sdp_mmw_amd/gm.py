@@ -9,6 +9,9 @@ A device-resident state of a generator (`DeviceEnv.device_state()`) gets its han
 and its keys from the handle itself (`GreedyHandle.key`): the state is never copied to the host.  A `DeviceState` of CSR
 arrays still hands out its host copy.
 
+MAX_RAND's `draws="device"` (opt-in) leaves NumPy's two `randn` draws out: the user order and the slot preferences are drawn,
+ranked and used on the device (`GreedyHandle.rand`, mmw_gm_rand; csrc/kernels_gm_rand.h), keyed by one integer from the global stream.
+
 Visiting order (MAX_GAIN / MAX_ASSO), chosen by the keyword `order` or the environment variable MMW_GM_ORDER:
   * "reference" (default): every slot visits the unassigned users in `kindx[np.argsort(-key[not_assigned])]`, evaluated on the
     host exactly as the reference does (gm.py:31-32); one device pass per slot.  On the same host this is the reference's result.
@@ -157,7 +160,14 @@ class MAX_RAND:
     """gm.MAX_RAND (gm.py:131-200): random user order, random slot preference, the rounding's user-major greedy."""
 
     @staticmethod
-    def run(Z, state, nattempt=1, device=None):
+    def run(Z, state, nattempt=1, device=None, draws="host", seed=None):
+        """draws="host" (default): the two `randn` draws of gm.py:148-150 from NumPy's global stream, sorted on the host and uploaded.
+        draws="device": `GreedyHandle.rand` -- the order keys and the preference values are drawn, ranked and used where the state
+        lies (include/mmw_hip.h, mmw_gm_rand), `nattempt` attempts of which the first that leaves nobody over counts, else the last;
+        `seed` keys the draw, None takes one 64-bit integer from NumPy's global stream, so a seeded script stays reproducible.  The fill
+        of users left over stays `np.random.randint` either way."""
+        if draws not in ("host", "device"):
+            raise ValueError("MAX_RAND draws must be 'host' or 'device', got %r" % (draws,))
         if _on_env(state, device):
             g = _env_handle(state)
             K = g.K
@@ -165,10 +175,15 @@ class MAX_RAND:
             state = _host_state(state)
             K = state[0].shape[0]
             g = _handle(state, device)
-        inprod = np.random.randn(Z, K)  # gm.py:148-150, same draws in the same order
-        sorted_indices = np.argsort(-inprod, axis=0)
-        rank = np.argsort(np.random.randn(K))
-        slot, _ = g.assign(rank, np.ascontiguousarray(sorted_indices.T))
+        if draws == "device":
+            if seed is None:
+                seed = int(np.random.randint(0, 1 << 64, dtype=np.uint64))
+            slot, _, _ = g.rand(Z, max(1, int(nattempt)), int(seed))
+        else:
+            inprod = np.random.randn(Z, K)  # gm.py:148-150, same draws in the same order
+            sorted_indices = np.argsort(-inprod, axis=0)
+            rank = np.argsort(np.random.randn(K))
+            slot, _ = g.assign(rank, np.ascontiguousarray(sorted_indices.T))
         not_assigned = slot < 0
         z_vec = np.where(not_assigned, 0, slot).astype(np.float64)
         if not_assigned.any():  # gm.py:196-199

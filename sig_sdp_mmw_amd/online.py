@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .batch import METHODS, OPT_IN_METHODS, _check_warm, _fill, probe_seed, warm_iterations
+from .batch import ALL_METHODS, METHODS, OPT_IN_METHODS, _check_warm, _fill, probe_seed, warm_iterations
 from .binary_search import binary_search_relaxation
 from .graphs import _NOISE_FLOOR_DBM, min_sinr_dec
 from .mmw import factor_rank_seed, mmw
@@ -304,13 +304,14 @@ def compare(drop_or_geometry, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio
     colouring is the one the search ends with.  Then the `methods`, in the order given:
     "rand": `Solver.factor_random(Z * rank_radio, key, resident=True, index_order=True)` on the search's handle, then
     `Solver.round_attempts(Z, block, nattempt, key)`; "spectral" (only when named): `Solver.factor_spectral(Z, resident=True,
-    index_order=True)` and the same rounding; "mgain" / "masso": `GreedyHandle.key(0 / 1)` then `run(key, Z, 1)`.  Users left over are
+    index_order=True)` and the same rounding; "mgain" / "masso": `GreedyHandle.key(0 / 1)` then `run(key, Z, 1)`; "mrand" (only when
+    named): `GreedyHandle.rand(Z, 1, key)`, gm.MAX_RAND with its draws made on the device.  Users left over are
     drawn from `np.random.default_rng(key).integers(0, Z, n)`.  key = batch.probe_seed(seed, 0, 0x40000 | m), m the method's index in
-    batch.METHODS + OPT_IN_METHODS: `batch.baselines_many`'s keys at instance 0.  One `env.evaluate` per method.
+    batch.ALL_METHODS (= METHODS + OPT_IN_METHODS + ("mrand",)): `batch.baselines_many`'s keys at instance 0.  One `env.evaluate` per method.
     Returns {"Z", "probes", "z_vec": {method: float64[K]}, "remainder": {method: int}, "bler": {method: float64[K]}}, "mmw"
     included.  timings: a dict that receives {"search_s", "baselines_s", "evaluate_s"} and "arm_s": {method: seconds}.  A method
-    that is not one of METHODS + OPT_IN_METHODS raises ValueError by name before any device work."""
-    names = METHODS + OPT_IN_METHODS
+    that is not one of batch.ALL_METHODS raises ValueError by name before any device work."""
+    names = ALL_METHODS
     methods = tuple(methods)
     for name in methods:
         if name not in names:
@@ -338,7 +339,11 @@ def compare(drop_or_geometry, nit=150, eta=0.04, seed=0, nattempt=10, rank_radio
             else:
                 if greedy is None:
                     greedy = _lib.GreedyHandle.from_env(env)
-                slot, _, rem = greedy.run(greedy.key(m - 1), Z, 1)
+                if name == "mrand":
+                    slot, rems, _ = greedy.rand(Z, 1, key)
+                    rem = int(rems[0])
+                else:
+                    slot, _, rem = greedy.run(greedy.key(m - 1), Z, 1)
                 z_vec[name], remainder[name] = _fill(slot, rem, Z, key)
             arm_s[name] = time.perf_counter() - ta
         t2 = time.perf_counter()
